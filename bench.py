@@ -69,6 +69,10 @@ def parse_args(argv=None):
                          "host parser emits (h263mi_batch_decode_events)")
     ap.add_argument("--no-pipeline", action="store_true",
                     help="two launches per frame index (k_recon, then k_post) instead of the frame-pipelined single launch")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (a fixed, seeded sample of every stream's "
+                         "Y, Cb, Cr planes and RGBA frame) as DIR/<name>.npy in float32, the sampled positions as "
+                         "DIR/<name>_index.npy in float64, for output-for-output comparison of two builds")
     ap.add_argument("--overlap", action="store_true",
                     help="k_post on a second stream (post of picture i beside recon of picture i+1); measured: no gain")
     return ap.parse_args(argv)
@@ -216,6 +220,35 @@ def run_frames(batch, wl, d_rgba, n_frames, pipeline=False, checked=True):
         else:
             batch.submit(fr["ptype"], fr["mbs"].ptr, fr["co"].ptr, fr["base"].ptr)
             batch.render_rgba(STRENGTH, d_rgba.ptr, None)
+
+
+DUMP_SEED = 20260
+DUMP_SAMPLES = {"y": 32768, "cb": 8192, "cr": 8192, "rgba": 131072}    # positions per stream and array
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(h263mi, batch, d_rgba, n, out_dir, prefix=""):
+    """The arrays a caller of the timed path receives after its last step -- each stream's decoded Y, Cb, Cr planes
+    (h263mi_batch_copy_yuv) and its RGBA frame -- sampled at fixed positions (DUMP_SEED, the same positions for every
+    stream and every run) and written as float32 <prefix><name>.npy of shape (n, k); <prefix><name>_index.npy (float64)
+    holds the byte positions sampled within one stream's array.  Outside the timed region."""
+    import numpy as np
+    sizes = {"y": Y_BYTES, "cb": C_BYTES, "cr": C_BYTES, "rgba": RGBA_BYTES}
+    rng = np.random.default_rng(DUMP_SEED)
+    index = {k: np.sort(rng.choice(sizes[k], DUMP_SAMPLES[k], replace=False)) for k in sizes}
+    total = sum(n * len(i) * 4 + len(i) * 8 for i in index.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes for %d streams exceeds the %d byte limit" % (total, n, DUMP_MAX_BYTES))
+    out = {k: np.empty((n, len(i)), np.float32) for k, i in index.items()}
+    for s in range(n):
+        for k, plane in zip(("y", "cb", "cr"), batch.copy_yuv(s)):
+            out[k][s] = plane[index[k]]
+        out["rgba"][s] = d_rgba.download(RGBA_BYTES, s * RGBA_BYTES)[index["rgba"]]
+    os.makedirs(out_dir, exist_ok=True)
+    for k in sizes:
+        np.save(os.path.join(out_dir, prefix + k + ".npy"), out[k])
+        np.save(os.path.join(out_dir, prefix + k + "_index.npy"), index[k].astype(np.float64))
+    return sorted(prefix + k + sfx + ".npy" for k in sizes for sfx in ("", "_index"))
 
 
 def parity_gate(h263mi, batch, d_rgba, first_stream, n, gop, streams=PARITY_STREAMS, stream_stride=1):
@@ -769,6 +802,8 @@ def stub_main(args, rank, world):
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     args = parse_args(argv)
+    if args.dump_outputs and args.steps < 1:
+        raise SystemExit("--dump-outputs needs --steps >= 1: it writes what the last timed step computed")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return launch_ranks(args, argv)                 # first thing, before torch.cuda.* or any h263mi call
 
@@ -857,6 +892,11 @@ def main(argv=None):
         gate_bad = int(t.item())
     if gate_bad and gate == "ok":
         gate = "failed on another rank"
+
+    # ---- what the last timed step computed, before any later leg reuses the batch
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(h263mi, batch, d_rgba, n, args.dump_outputs, prefix="rank%d_" % rank if world > 1 else "")
 
     # ---- roofline of the dominant kernel (HIP events on the launch stream, timed region only)
     g = len(wl.frames)
@@ -1156,6 +1196,8 @@ def main(argv=None):
     }
     if extra:
         out["extra"] = extra
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(h263mi)
     elif rank == 0:

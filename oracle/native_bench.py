@@ -3,12 +3,14 @@
 TEST / BENCH INFRASTRUCTURE ONLY (like everything under oracle/): used by bench.py's `cpu_baseline` leg and by
 tests/.  BASELINE.md section 3 / SURVEY 8(d): `-O3 -march=native -ffp-contract=off`, (i) one thread, (ii) T threads
 with one stream each, T = physical cores.  The build happens where the timing happens (`-march=native` code must
-not travel between machines), into oracle/_native/, keyed by the CPU's flag set.
+not travel between machines), into oracle/_native/, keyed by the CPU's flag set -- or, where the checkout is read-only
+for the user who times, into a per-user directory under the system's temporary directory.
 """
 import ctypes as C
 import hashlib
 import os
 import subprocess
+import tempfile
 
 import numpy as np
 
@@ -32,18 +34,46 @@ def _cpu_key():
     return hashlib.sha256((flags + model).encode()).hexdigest()[:12]
 
 
-class NativeOracle:
-    def __init__(self):
-        out_dir = os.path.join(_HERE, "_native")
-        os.makedirs(out_dir, exist_ok=True)
-        srcs = [os.path.join(_HERE, "h263_oracle.c"), os.path.join(_HERE, "bench_streams.c"), os.path.join(_HERE, "simd_stages.c")]
-        self.srcs = srcs
-        self.path = os.path.join(out_dir, "libh263oracle_native_%s.so" % _cpu_key())
-        if not os.path.exists(self.path) or any(os.path.getmtime(self.path) < os.path.getmtime(s) for s in srcs):
+def _out_dirs():
+    """where the native build may live: oracle/_native/ in the checkout (what build() fills), then a per-user cache for a
+    checkout the current user cannot write to"""
+    uid = os.getuid() if hasattr(os, "getuid") else 0
+    return [os.path.join(_HERE, "_native"), os.path.join(tempfile.gettempdir(), "h263mi_oracle_native_%d" % uid)]
+
+
+def _writable_dir(d):
+    try:
+        os.makedirs(d, exist_ok=True)
+    except OSError:
+        return False
+    return os.access(d, os.W_OK | os.X_OK)
+
+
+def native_lib_path(srcs):
+    """the native oracle library for this CPU: an up-to-date build where one exists, else a fresh one in the first
+    writable place"""
+    name = "libh263oracle_native_%s.so" % _cpu_key()
+    fresh = lambda p: os.path.exists(p) and all(os.path.getmtime(p) >= os.path.getmtime(s) for s in srcs)
+    for d in _out_dirs():
+        if fresh(os.path.join(d, name)):
+            return os.path.join(d, name)
+    for d in _out_dirs():
+        if _writable_dir(d):
+            path = os.path.join(d, name)
             # (built under a private name and moved into place: several test workers may get here at the same time)
-            tmp = "%s.%d.tmp" % (self.path, os.getpid())
+            tmp = "%s.%d.tmp" % (path, os.getpid())
             subprocess.check_call(["gcc"] + FLAGS + ["-shared", "-o", tmp] + srcs)
-            os.replace(tmp, self.path)
+            os.replace(tmp, path)
+            return path
+    raise RuntimeError("native oracle: no writable directory among %s" % _out_dirs())
+
+
+class NativeOracle:
+    SRCS = [os.path.join(_HERE, "h263_oracle.c"), os.path.join(_HERE, "bench_streams.c"), os.path.join(_HERE, "simd_stages.c")]
+
+    def __init__(self):
+        self.srcs = self.SRCS
+        self.path = native_lib_path(self.srcs)
         self.flags = "gcc " + " ".join(FLAGS)
         L = C.CDLL(self.path)
         orc.bind(L)

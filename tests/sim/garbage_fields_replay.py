@@ -7,7 +7,9 @@ reference frame and in I pictures, dense and event transport, with the bounds a 
 given such input (its parser never makes it), so there is no expected picture for a stream that was hit: the contract is that
 nothing outside the caller's arrays and the frame store is touched, and that the streams left alone decode exactly.
 usage: python garbage_fields_replay.py <seed> <cases>"""
-import sys; sys.path[:0]=['/root/repo','/root/repo/tests','/root/repo/h263-rs_amd']
+import os, sys
+_R=os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path[:0]=[_R,os.path.join(_R,'tests'),os.path.join(_R,'h263-rs_amd')]
 import numpy as np, ctypes as C, simlib, recgen, h263mi
 from oracle import oracle as orc
 lib=simlib.lib(asan=True)

@@ -5,7 +5,9 @@ h263mi_batch_decode_events has (n_events and pool size = what the caller's alloc
 faulted on the MI355X in round 6: a block offset of 0xffffffff (`first + lane` wrapped) and a base of 2^64 - 2^20.  Exact-size
 numpy arrays stand for the caller's allocations: one word beyond them is a report.
 usage: python hostile_replay.py <seed> <cases>"""
-import sys; sys.path[:0]=['/root/repo','/root/repo/tests','/root/repo/h263-rs_amd']
+import os, sys
+_R=os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path[:0]=[_R,os.path.join(_R,'tests'),os.path.join(_R,'h263-rs_amd')]
 import numpy as np, ctypes as C, simlib, recgen, h263mi
 from oracle import oracle as orc
 lib=simlib.lib(asan=True)
