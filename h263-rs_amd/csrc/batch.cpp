@@ -45,7 +45,17 @@ int h263mi_batch::alloc(uint32_t n_streams, uint32_t w, uint32_t h)
     HIP_TRY(hipMemsetAsync(d_status, 0, (size_t)n * sizeof(uint32_t), stream));
     ss.assign(n, StreamState());
     pending.set.assign(n, -1);
+    layout = RgbaLayout();
+    layout.bytes = (uint64_t)n * w * h * 4;
     return H263MI_OK;
+}
+
+bool h263mi_batch::layout_ptrs(uint8_t *d_rgba, std::vector<uint8_t *> &ptrs) const
+{
+    if (!layout.placed() || !d_rgba) return false;
+    ptrs.resize(n);
+    for (uint32_t i = 0; i < n; i++) ptrs[i] = d_rgba + layout.offsets[i];
+    return true;
 }
 
 bool h263mi_batch::any_picture() const
@@ -251,6 +261,7 @@ int h263mi_batch::submit(uint8_t picture_type, const MbRecord *d_mbs, const h263
     PostArgs pa{};
     if (with_post) pa = post_args(0, pending.strength.of(0), pending.rgba, pending.planes);
     if (with_post) pa.rgba_ptrs = pending.rgba_ptrs;       // (read in the per-stream branch of the kernel only)
+    if (with_post) pa.rgba_scale = pending.out.scale, pa.rgba_pitch = pending.out.pitch;
     // one strength for every picture of the launch, or one per stream (then it travels in the streams' words)
     const bool all_same = uniform() && (!with_post || (pending_uniform() && pending.set[0] >= 0 && !pending.rgba_ptrs &&
                                                        pending.strength.same_for_all()));
@@ -334,7 +345,7 @@ PostArgs h263mi_batch::post_args(int set, uint8_t strength, uint8_t *d_rgba, uin
 }
 
 int h263mi_batch::launch_post_sets(const std::vector<int8_t> &sets, const Strengths &strength, uint8_t *d_rgba, uint8_t *d_planes,
-                                   hipStream_t on, uint8_t *const *rgba_ptrs)
+                                   hipStream_t on, uint8_t *const *rgba_ptrs, OutLayout out)
 {
     bool same = rgba_ptrs == nullptr && strength.same_for_all(), any = false;
     for (int8_t v : sets) {
@@ -344,6 +355,8 @@ int h263mi_batch::launch_post_sets(const std::vector<int8_t> &sets, const Streng
     if (!any) return H263MI_OK;
     PostArgs a = post_args(sets[0] >= 0 ? sets[0] : 0, strength.of(0), d_rgba, d_planes);
     a.rgba_ptrs = rgba_ptrs;
+    a.rgba_scale = out.scale;
+    a.rgba_pitch = out.pitch;
     std::vector<uint32_t> words;
     const bool words_inline = n <= STREAM_WORDS_INLINE;
     if (!same) {
@@ -366,6 +379,10 @@ int h263mi_batch::note_pending(const Strengths &strength, uint8_t *d_rgba, uint8
 {
     pending.valid = false;
     pending.rgba_ptrs = nullptr;
+    // (an output layout places each stream's picture through a per-stream pointer; the layout is captured here, at the request)
+    std::vector<uint8_t *> placed;
+    if (!host_ptrs && layout_ptrs(d_rgba, placed)) host_ptrs = placed.data();
+    pending.out = layout.kernel;
     if (host_ptrs) RC_TRY(push_rgba_ptrs(host_ptrs, &pending.rgba_ptrs, stream));
     pending.valid = d_rgba || d_planes || host_ptrs;
     pending.strength = strength;
@@ -380,13 +397,15 @@ int h263mi_batch::flush_pending()
 {
     if (!pending.valid) return H263MI_OK;
     pending.valid = false;
-    return launch_post_sets(pending.set, pending.strength, pending.rgba, pending.planes, stream, pending.rgba_ptrs);
+    return launch_post_sets(pending.set, pending.strength, pending.rgba, pending.planes, stream, pending.rgba_ptrs, pending.out);
 }
 
 int h263mi_batch::render(const Strengths &strength, uint8_t *d_rgba, uint8_t *d_planes, bool only_active, uint8_t *const *host_ptrs)
 {
     if (!any_picture()) return H263MI_ERR_NO_PICTURE;
     RC_TRY(flush_pending());
+    std::vector<uint8_t *> placed;
+    if (!host_ptrs && layout_ptrs(d_rgba, placed)) host_ptrs = placed.data();
     std::vector<int8_t> sets(n);
     bool reads[2] = {false, false};
     for (uint32_t i = 0; i < n; i++) {
@@ -396,7 +415,7 @@ int h263mi_batch::render(const Strengths &strength, uint8_t *d_rgba, uint8_t *d_
     if (overlap_post) HIP_TRY(hipStreamWaitEvent(post_stream, ev_recon_done, 0));
     uint8_t *const *d_out_ptrs = nullptr;
     if (host_ptrs) RC_TRY(push_rgba_ptrs(host_ptrs, &d_out_ptrs, stream_of(1)));
-    RC_TRY(launch_post_sets(sets, strength, d_rgba, d_planes, stream_of(1), d_out_ptrs));
+    RC_TRY(launch_post_sets(sets, strength, d_rgba, d_planes, stream_of(1), d_out_ptrs, layout.kernel));
     // a later reconstruction may overwrite a frame set only when every post-processing that reads it is done: streams
     // that have drifted apart read both sets
     if (overlap_post)
@@ -608,7 +627,7 @@ static int bound_device_arrays(const h263mi_batch *b, const h263mi_mb_record *d_
 static int bound_output_buffers(const h263mi_batch *b, const uint8_t *d_rgba, const uint8_t *d_deblocked)
 {
     if (b->trusted_arrays) return H263MI_OK;
-    const size_t rgba_bytes = (size_t)b->n * b->L.width * b->L.height * 4;
+    const size_t rgba_bytes = b->layout.bytes;      // (n * w*h*4 unless the batch has an output layout)
     const size_t plane_bytes = (size_t)b->n * ((size_t)b->L.width * b->L.height + 2 * (size_t)b->L.cwidth * b->L.cheight);
     size_t left = 0;
     if (d_rgba) {
@@ -618,6 +637,54 @@ static int bound_output_buffers(const h263mi_batch *b, const uint8_t *d_rgba, co
     if (d_deblocked) {
         const int rc = bytes_behind(d_deblocked, &left);
         if (rc == H263MI_ERR_OUT_OF_MEMORY || (rc == H263MI_OK && left < plane_bytes)) return rc == H263MI_OK ? H263MI_ERR_INVALID_ARGUMENT : rc;
+    }
+    return H263MI_OK;
+}
+
+int rgba_layout_extent(uint32_t n_streams, uint32_t w, uint32_t h, const h263mi_rgba_layout *lay, uint32_t *out_w, uint32_t *out_h,
+                       uint64_t *bytes, h263mi_batch::OutLayout *out_kernel)
+{
+    if (!n_streams || !w || !h) return H263MI_ERR_INVALID_ARGUMENT;
+    const uint32_t scale = lay ? lay->scale_log2 : 0u;
+    if (scale > 2) return H263MI_ERR_INVALID_ARGUMENT;
+    if (lay)
+        for (uint8_t r : lay->reserved)
+            if (r) return H263MI_ERR_INVALID_ARGUMENT;
+    const uint32_t ow = (w + (1u << scale) - 1) >> scale, oh = (h + (1u << scale) - 1) >> scale;
+    const uint64_t row = 4ull * ow, pitch = (lay && lay->row_pitch) ? lay->row_pitch : row;
+    if (pitch < row || pitch % 4) return H263MI_ERR_INVALID_ARGUMENT;
+    const uint64_t span = (uint64_t)(oh - 1) * pitch + row;              // bytes from a picture's first byte to behind its last
+    if (oh > 1 && pitch >= (1ull << 32)) return H263MI_ERR_INVALID_ARGUMENT;
+    if (span >= (1ull << 32)) return H263MI_ERR_INVALID_ARGUMENT;         // lane offsets are 32-bit
+    uint64_t total = 0;
+    const uint64_t *off = lay ? lay->offsets : nullptr;
+    if (!off) {
+        const unsigned __int128 t = (unsigned __int128)(n_streams - 1) * oh * pitch + span;
+        if (t > UINT64_MAX) return H263MI_ERR_INVALID_ARGUMENT;
+        total = (uint64_t)t;
+    } else {
+        // every picture on its own rows and byte columns: rows [o / pitch, + H'), columns [o % pitch, + 4W')
+        struct Rect { uint64_t r0, c0; };
+        std::vector<Rect> rs(n_streams);
+        for (uint32_t i = 0; i < n_streams; i++) {
+            const uint64_t o = off[i];
+            if (o % 4 || o % pitch + row > pitch || o > UINT64_MAX - span) return H263MI_ERR_INVALID_ARGUMENT;
+            total = std::max(total, o + span);
+            rs[i] = {o / pitch, o % pitch};
+        }
+        std::sort(rs.begin(), rs.end(), [](const Rect &x, const Rect &y) { return x.r0 < y.r0 || (x.r0 == y.r0 && x.c0 < y.c0); });
+        for (uint32_t i = 0; i < n_streams; i++)
+            for (uint32_t j = i + 1; j < n_streams && rs[j].r0 < rs[i].r0 + oh; j++)      // (sorted by first row: later ones start lower)
+                if (rs[j].c0 < rs[i].c0 + row && rs[i].c0 < rs[j].c0 + row) return H263MI_ERR_INVALID_ARGUMENT;
+    }
+    if (out_w) *out_w = ow;
+    if (out_h) *out_h = oh;
+    if (bytes) *bytes = total;
+    if (out_kernel) {
+        // the default layout (full size, tight rows, pictures back to back) keeps the default kernels
+        const bool dflt = scale == 0 && pitch == row && !off;
+        out_kernel->scale = dflt ? 0u : scale;
+        out_kernel->pitch = dflt ? 0u : (uint32_t)(oh > 1 ? pitch : row);     // (one row: the pitch is never used)
     }
     return H263MI_OK;
 }
@@ -726,6 +793,31 @@ int h263mi_batch_render_rgba_ps(h263mi_batch *b, uint8_t strength, const uint8_t
     DeviceGuard g(b->device);
     RC_TRY(bound_output_buffers(b, d_rgba, d_deblocked));
     return b->render(st, d_rgba, d_deblocked);
+}
+
+int h263mi_rgba_layout_extent(uint32_t n_streams, uint16_t width, uint16_t height, const h263mi_rgba_layout *layout,
+                              uint16_t *out_w, uint16_t *out_h, uint64_t *bytes)
+{
+    uint32_t ow = 0, oh = 0;
+    RC_TRY(rgba_layout_extent(n_streams, width, height, layout, &ow, &oh, bytes));
+    if (out_w) *out_w = (uint16_t)ow;
+    if (out_h) *out_h = (uint16_t)oh;
+    return H263MI_OK;
+}
+
+int h263mi_batch_set_rgba_layout(h263mi_batch *b, const h263mi_rgba_layout *layout)
+{
+    if (!b) return H263MI_ERR_INVALID_ARGUMENT;
+    h263mi_batch::RgbaLayout lay;
+    uint32_t ow = 0, oh = 0;
+    RC_TRY(rgba_layout_extent(b->n, b->L.width, b->L.height, layout, &ow, &oh, &lay.bytes, &lay.kernel));
+    if (lay.placed()) {
+        lay.offsets.resize(b->n);
+        const uint64_t pitch = (layout->row_pitch ? layout->row_pitch : 4ull * ow);
+        for (uint32_t i = 0; i < b->n; i++) lay.offsets[i] = layout->offsets ? layout->offsets[i] : (uint64_t)i * oh * pitch;
+    }
+    b->layout = std::move(lay);
+    return H263MI_OK;
 }
 
 int h263mi_batch_render_rgba(h263mi_batch *b, uint8_t strength, uint8_t *d_rgba, uint8_t *d_deblocked)

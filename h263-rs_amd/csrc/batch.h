@@ -30,6 +30,11 @@ struct h263mi_coeff_source {
     const uint64_t *mb_base = nullptr;           // ... each picture's first record
 };
 
+// What the kernels are told of an RGBA output layout (PostArgs::rgba_scale, rgba_pitch; pitch 0 = today's layout)
+struct h263mi_rgba_out {
+    uint32_t scale = 0, pitch = 0;
+};
+
 struct h263mi_batch {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -62,9 +67,20 @@ struct h263mi_batch {
             return true;
         }
     };
+    // The output layout of the RGBA (h263mi_batch_set_rgba_layout).  `kernel`: what the kernels are told (pitch 0: the default
+    // kernels); `offsets` (empty = s * H' * pitch): where stream s's picture
+    // starts in the caller's buffer -- handed to the kernels as per-stream pointers (push_rgba_ptrs).
+    typedef h263mi_rgba_out OutLayout;
+    struct RgbaLayout {
+        OutLayout kernel;
+        std::vector<uint64_t> offsets;
+        uint64_t bytes = 0;                    // what d_rgba must hold (h263mi_rgba_layout_extent)
+        bool placed() const { return kernel.pitch != 0; }
+    } layout;
     struct PendingPost {
         bool valid = false;
         Strengths strength;
+        OutLayout out;                         // the layout in force when the rendering was requested
         uint8_t *rgba = nullptr, *planes = nullptr;
         uint8_t *const *rgba_ptrs = nullptr;   // DEVICE array of per-stream output pointers (a batch inside a mixed-size set)
         std::vector<int8_t> set;               // per stream: frame set it reads, -1 = nothing to post-process
@@ -190,7 +206,10 @@ struct h263mi_batch {
     // k_post over `sets` (per stream: the frame set to read, -1 = skip the stream); rgba_ptrs: DEVICE array of per-stream
     // output pointers instead of d_rgba (or nullptr)
     int launch_post_sets(const std::vector<int8_t> &sets, const Strengths &strength, uint8_t *d_rgba, uint8_t *d_planes, hipStream_t on,
-                         uint8_t *const *rgba_ptrs = nullptr);
+                         uint8_t *const *rgba_ptrs = nullptr, OutLayout out = OutLayout());
+    // the batch's layout applied to d_rgba: false = the default layout (d_rgba as it is); true = `ptrs` holds n DEVICE pointers,
+    // stream s's picture at d_rgba + its offset
+    bool layout_ptrs(uint8_t *d_rgba, std::vector<uint8_t *> &ptrs) const;
     // pipeline mode: the post-processing of the pictures just submitted is deferred to the next launch.
     // host_ptrs (or nullptr): n DEVICE pointers, the RGBA buffer of each stream (nullptr = none for it) instead of d_rgba.
     int note_pending(const Strengths &strength, uint8_t *d_rgba, uint8_t *d_planes, uint8_t *const *host_ptrs = nullptr);
@@ -207,6 +226,9 @@ struct h263mi_batch {
 
 namespace h263mi {
 
+// h263mi_rgba_layout_extent; out_kernel (may be null): what the kernels are told (pitch 0 = today's layout)
+int rgba_layout_extent(uint32_t n_streams, uint32_t w, uint32_t h, const h263mi_rgba_layout *layout, uint32_t *out_w,
+                       uint32_t *out_h, uint64_t *bytes, h263mi_batch::OutLayout *out_kernel = nullptr);
 int batch_create(uint32_t n_streams, uint32_t w, uint32_t h, const h263mi_backend_cfg *cfg, h263mi_batch **out);
 // where the host side of device `dev`'s work belongs (worker_pool.h): the PCI addresses of the visible devices -> sysfs
 HostPlacement placement_of_device(int dev);

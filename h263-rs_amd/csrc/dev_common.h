@@ -180,6 +180,11 @@ struct PostArgs {
     uint32_t words_inline;       // 1: the per-stream words are the launch's StreamWords argument (set by the launcher)
     uint8_t *const *rgba_ptrs;   // with stream_state only (or nullptr): picture p's RGBA goes to rgba_ptrs[p] instead of
                                  // rgba + p * w*h*4 -- streams whose outputs are separate buffers (a batch of mixed sizes)
+    // output layout (h263mi_rgba_layout).  rgba_pitch == 0: today's, w x h tightly packed, picture p at + p*w*h*4.  Else
+    // the pictures are ceil(w / 2^rgba_scale) x ceil(h / 2^rgba_scale) box averages, rows rgba_pitch bytes apart, picture p
+    // at + p * H' * rgba_pitch (or rgba_ptrs[p]); the launchers then pick the LAYOUT instantiations of the kernels.
+    uint32_t rgba_scale;         // 0, 1, 2
+    uint32_t rgba_pitch;         // bytes from one output row to the next (a multiple of 4; (H'-1) * pitch + 4W' < 2^32)
 };
 
 // ---------------------------------------------------------------------------

@@ -456,7 +456,7 @@ hipError_t launch_recon(const ReconArgs &args, hipStream_t stream, const uint32_
 // neighbouring tiles at any moment: the cache lines that the 4-pixel tile offset makes two tiles
 // share are then fetched once per L2 instead of once per XCD.
 // ---------------------------------------------------------------------------------------
-template <bool FETCH_AHEAD, bool STREAM_RGBA, bool INTERIOR>
+template <bool FETCH_AHEAD, bool STREAM_RGBA, bool INTERIOR, int SCALE>
 __device__ __forceinline__ void post_strip(const PostArgs &a, PostStrip &s, PostFetch &pf, int lane, int sx, int sy, int pic)
 {
     // `ln`: the lane index behind an opaque asm, re-derived per strip so that lane-only expressions (LDS
@@ -488,18 +488,18 @@ __device__ __forceinline__ void post_strip(const PostArgs &a, PostStrip &s, Post
 #if H263MI_STOP_POST == 3
     return;
 #endif
-    post_phase_store<STREAM_RGBA, INTERIOR>(a, s, ln, sx, sy, pic);
+    post_phase_store<STREAM_RGBA, INTERIOR, SCALE>(a, s, ln, sx, sy, pic);
     ISA_MARK2(INTERIOR, "interior_", "edge_", "store_end");
 }
 
 // Two strips of a tile.  FETCH_AHEAD: queue the loads of the strips two further down right after each
 // commit, so that they are in flight while this pair is filtered and stored.
-template <bool FETCH_AHEAD, bool STREAM_RGBA, bool INTERIOR>
+template <bool FETCH_AHEAD, bool STREAM_RGBA, bool INTERIOR, int SCALE>
 __device__ __forceinline__ void post_strip_pair(const PostArgs &a, PostStrip &s, PostFetch &pf0, PostFetch &pf1, int lane,
                                                 int sx, int sy, int pic)
 {
-    post_strip<FETCH_AHEAD, STREAM_RGBA, INTERIOR>(a, s, pf0, lane, sx, sy, pic);
-    post_strip<FETCH_AHEAD, STREAM_RGBA, INTERIOR>(a, s, pf1, lane, sx, sy + 1, pic);
+    post_strip<FETCH_AHEAD, STREAM_RGBA, INTERIOR, SCALE>(a, s, pf0, lane, sx, sy, pic);
+    post_strip<FETCH_AHEAD, STREAM_RGBA, INTERIOR, SCALE>(a, s, pf1, lane, sx, sy + 1, pic);
 }
 
 // One wave's share of the post-processing: the 128x32 tile (sx, ty) of picture `pic` = 4 strips.
@@ -508,7 +508,7 @@ __device__ __forceinline__ void post_strip_pair(const PostArgs &a, PostStrip &s,
 // rows to store), which keeps the code straight-line.  INTERIOR (post_tile_is_interior, 82 % of the tiles of a 1080p
 // picture): no bounds handling at all and a fixed number of vector memory operations per strip, so that every wait is
 // an exact s_waitcnt vmcnt(N) that leaves the younger loads and stores in flight.
-template <bool STREAM_RGBA, bool INTERIOR>
+template <bool STREAM_RGBA, bool INTERIOR, int SCALE>
 __device__ __forceinline__ void post_tile(const PostArgs &a, PostStrip &s, int lane, int sx, int ty, int pic)
 {
     const int sy0 = ty * POST_STRIPS;
@@ -519,11 +519,12 @@ __device__ __forceinline__ void post_tile(const PostArgs &a, PostStrip &s, int l
     PostFetch pf0, pf1;
     post_phase_fetch<INTERIOR>(a, pf0, lane, sx, sy0, pic);
     post_phase_fetch<INTERIOR>(a, pf1, lane, sx, sy0 + 1, pic);
-    post_strip_pair<true, STREAM_RGBA, INTERIOR>(a, s, pf0, pf1, lane, sx, sy0, pic);          // strips 0,1; queues the loads of 2,3
-    post_strip_pair<false, STREAM_RGBA, INTERIOR>(a, s, pf0, pf1, lane, sx, sy0 + 2, pic);     // strips 2,3
+    post_strip_pair<true, STREAM_RGBA, INTERIOR, SCALE>(a, s, pf0, pf1, lane, sx, sy0, pic);          // strips 0,1; queues the loads of 2,3
+    post_strip_pair<false, STREAM_RGBA, INTERIOR, SCALE>(a, s, pf0, pf1, lane, sx, sy0 + 2, pic);     // strips 2,3
 }
 
-template <bool STREAM_RGBA>
+// SCALE: -1 = the default kernels (today's output), 0..2 = the LAYOUT instantiations (post_phase_store)
+template <bool STREAM_RGBA, int SCALE = -1>
 __device__ __forceinline__ void post_wave(const PostArgs &a0, PostStrip &s, int lane, int sx, int ty, int pic, ScalarPtr32 kernarg_words)
 {
     if (ty >= (int)a0.tiles_y) return;
@@ -538,15 +539,15 @@ __device__ __forceinline__ void post_wave(const PostArgs &a0, PostStrip &s, int 
         a.strength = (st >> STREAM_STRENGTH_SHIFT) & STREAM_STRENGTH_MASK;      // this picture's own (deblock.rs:5-8)
         // per-stream output buffers: the phases address picture `pic` at a.rgba + pic * w*h*4 -- hand them the base that
         // puts it at its own pointer (uniform: two scalar loads)
-        if (a0.rgba_ptrs) a.rgba = a0.rgba_ptrs[pic] - (size_t)pic * a0.L.width * a0.L.height * 4u;
+        if (a0.rgba_ptrs) a.rgba = a0.rgba_ptrs[pic] - (SCALE < 0 ? (size_t)pic * a0.L.width * a0.L.height * 4u : (size_t)pic * post_out_picture_bytes<SCALE>(a0));
     }
-    if (post_tile_is_interior(a, sx, ty)) post_tile<STREAM_RGBA, true>(a, s, lane, sx, ty, pic);       // wave-uniform
-    else post_tile<STREAM_RGBA, false>(a, s, lane, sx, ty, pic);
+    if (post_tile_is_interior(a, sx, ty)) post_tile<STREAM_RGBA, true, SCALE>(a, s, lane, sx, ty, pic);       // wave-uniform
+    else post_tile<STREAM_RGBA, false, SCALE>(a, s, lane, sx, ty, pic);
 }
 
-__global__ __launch_bounds__(POST_THREADS) void k_post(StreamWords, PostArgs a)
+template <int SCALE>
+__device__ __forceinline__ void post_kernel(const PostArgs &a, PostStrip *strips)      // k_post, k_post_layout
 {
-    __shared__ __attribute__((aligned(16))) PostStrip strips[POST_WAVES];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));    // wave index: scalar
     // one wave = one 128x32 tile = 4 strips; a workgroup = 4 vertically adjacent tiles (a 128x128 block), and
     // workgroups follow each other along x in the XCD-ordered list.  Horizontal neighbours -- which share the
@@ -566,7 +567,21 @@ __global__ __launch_bounds__(POST_THREADS) void k_post(StreamWords, PostArgs a)
     const int pic = (int)blockIdx.y;
     const uint32_t gy = div_tiles_x(wg, a.tiles_x, a.inv_tiles_x);
     const int sx = (int)(wg - gy * a.tiles_x + a.wrap), ty = (int)gy * POST_GROUP + gw;      // (wrap: the first tile column is 1)
-    post_wave<false>(a, strips[wave], lane, sx, ty, pic, kernarg_stream_words());
+    post_wave<false, SCALE>(a, strips[wave], lane, sx, ty, pic, kernarg_stream_words());
+}
+
+__global__ __launch_bounds__(POST_THREADS) void k_post(StreamWords, PostArgs a)
+{
+    __shared__ __attribute__((aligned(16))) PostStrip strips[POST_WAVES];
+    post_kernel<-1>(a, strips);
+}
+
+// the same for an output layout (a.rgba_pitch != 0): scale 2^SCALE, rows a.rgba_pitch bytes apart (post_phase_store)
+template <int SCALE>
+__global__ __launch_bounds__(POST_THREADS) void k_post_layout(StreamWords, PostArgs a)
+{
+    __shared__ __attribute__((aligned(16))) PostStrip strips[POST_WAVES];
+    post_kernel<SCALE>(a, strips);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -579,14 +594,18 @@ __global__ __launch_bounds__(POST_THREADS) void k_post(StreamWords, PostArgs a)
 // at the same time on the same XCD: the planes are fetched from HBM once per frame instead of twice, and waves
 // bound by arithmetic and address work (reconstruction) share every CU with waves bound by stores (RGBA).
 // ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_frame(StreamWords, ReconArgs ra, PostArgs pa, FrameGeom fg)
-{
+union FrameLds {
 #if defined(H263MI_LDS_PAD)
     // experiment: what a larger LDS footprint per wave (fewer resident waves) costs
-    __shared__ __attribute__((aligned(16))) union { ReconWave r; PostStrip p; uint8_t pad[H263MI_LDS_PAD]; } lds;
+    ReconWave r; PostStrip p; uint8_t pad[H263MI_LDS_PAD];
 #else
-    __shared__ __attribute__((aligned(16))) union { ReconWave r; PostStrip p; } lds;
+    ReconWave r; PostStrip p;
 #endif
+};
+
+template <int SCALE>
+__device__ __forceinline__ void frame_kernel(const ReconArgs &ra, const PostArgs &pa, const FrameGeom &fg, FrameLds &lds)   // k_frame, k_frame_layout
+{
     const int lane = threadIdx.x & 63;
     const uint32_t per_group = fg.recon_per_group + fg.post_per_group;
     const uint32_t upp = fg.groups * per_group;
@@ -634,11 +653,25 @@ __global__ __launch_bounds__(64) void k_frame(StreamWords, ReconArgs ra, PostArg
     } else {
         if (H263MI_PRIO_POST) __builtin_amdgcn_s_setprio(H263MI_PRIO_POST);
 #if defined(H263MI_EXP_PLAIN_RGBA)
-        post_wave<false>(pa, lds.p, lane, (int)(r - fg.recon_per_group + pa.wrap), (int)group, pic, kernarg_stream_words());
+        post_wave<false, SCALE>(pa, lds.p, lane, (int)(r - fg.recon_per_group + pa.wrap), (int)group, pic, kernarg_stream_words());
 #else
-        post_wave<true>(pa, lds.p, lane, (int)(r - fg.recon_per_group + pa.wrap), (int)group, pic, kernarg_stream_words());
+        post_wave<true, SCALE>(pa, lds.p, lane, (int)(r - fg.recon_per_group + pa.wrap), (int)group, pic, kernarg_stream_words());
 #endif
     }
+}
+
+__global__ __launch_bounds__(64) void k_frame(StreamWords, ReconArgs ra, PostArgs pa, FrameGeom fg)
+{
+    __shared__ __attribute__((aligned(16))) FrameLds lds;
+    frame_kernel<-1>(ra, pa, fg, lds);
+}
+
+// the same for an output layout (pa.rgba_pitch != 0), as k_post_layout
+template <int SCALE>
+__global__ __launch_bounds__(64) void k_frame_layout(StreamWords, ReconArgs ra, PostArgs pa, FrameGeom fg)
+{
+    __shared__ __attribute__((aligned(16))) FrameLds lds;
+    frame_kernel<SCALE>(ra, pa, fg, lds);
 }
 
 hipError_t launch_frame(const ReconArgs &rargs, const PostArgs &pargs, hipStream_t stream, bool descending, const uint32_t *words)
@@ -663,8 +696,12 @@ hipError_t launch_frame(const ReconArgs &rargs, const PostArgs &pargs, hipStream
     StreamWords sw{};
     ra.words_inline = pa.words_inline = inline_words(words, rargs.n_pictures, sw) ? 1u : 0u;
     const uint32_t chunk = (fg.groups * per_group + fg.bands - 1) / fg.bands, side_by_side = 8 / fg.bands;
-    hipLaunchKernelGGL(k_frame, dim3(chunk * 8, (rargs.n_pictures + side_by_side - 1) / side_by_side), dim3(64), 0, stream, sw,
-                       ra, pa, fg);
+    const dim3 grid(chunk * 8, (rargs.n_pictures + side_by_side - 1) / side_by_side);
+    if (!pa.rgba_pitch) hipLaunchKernelGGL(k_frame, grid, dim3(64), 0, stream, sw, ra, pa, fg);
+    else if (pa.rgba_scale == 0) hipLaunchKernelGGL(k_frame_layout<0>, grid, dim3(64), 0, stream, sw, ra, pa, fg);
+    else if (pa.rgba_scale == 1) hipLaunchKernelGGL(k_frame_layout<1>, grid, dim3(64), 0, stream, sw, ra, pa, fg);
+    else if (pa.rgba_scale == 2) hipLaunchKernelGGL(k_frame_layout<2>, grid, dim3(64), 0, stream, sw, ra, pa, fg);
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 
@@ -679,7 +716,12 @@ hipError_t launch_post(const PostArgs &args, hipStream_t stream, const uint32_t 
     a.inv_tiles_x = reciprocal_u32(args.tiles_x);
     const uint32_t groups_y = (args.tiles_y + POST_GROUP - 1) / POST_GROUP;
     const uint32_t upp = args.tiles_x * groups_y * (POST_GROUP / POST_WAVES), chunk = (upp + 7) / 8;
-    hipLaunchKernelGGL(k_post, dim3(chunk * 8, args.n_pictures), dim3(POST_THREADS), 0, stream, sw, a);
+    const dim3 grid(chunk * 8, args.n_pictures);
+    if (!a.rgba_pitch) hipLaunchKernelGGL(k_post, grid, dim3(POST_THREADS), 0, stream, sw, a);
+    else if (a.rgba_scale == 0) hipLaunchKernelGGL(k_post_layout<0>, grid, dim3(POST_THREADS), 0, stream, sw, a);
+    else if (a.rgba_scale == 1) hipLaunchKernelGGL(k_post_layout<1>, grid, dim3(POST_THREADS), 0, stream, sw, a);
+    else if (a.rgba_scale == 2) hipLaunchKernelGGL(k_post_layout<2>, grid, dim3(POST_THREADS), 0, stream, sw, a);
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

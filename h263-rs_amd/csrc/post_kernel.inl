@@ -532,27 +532,171 @@ H263_DEV uint32_t bt601_pack(int r, int g, int b)
 #endif
 }
 
+// ---- phase 3 of the LAYOUT instantiations: scaled, pitched output (h263mi_rgba_layout) -----------------------------
+// Output picture of the layout: W' x H' = ceil(w / f) x ceil(h / f), f = 2^scale
+H263_HD uint32_t post_out_w(const PostArgs &a, int scale) { return (a.L.width + (1u << scale) - 1) >> scale; }
+H263_HD uint32_t post_out_h(const PostArgs &a, int scale) { return (a.L.height + (1u << scale) - 1) >> scale; }
+// bytes from picture p to picture p + 1 of an output buffer without per-stream pointers
+template <int SCALE>
+H263_HD size_t post_out_picture_bytes(const PostArgs &a)
+{
+    return SCALE < 0 ? (size_t)a.L.width * a.L.height * 4u : (size_t)post_out_h(a, SCALE) * a.rgba_pitch;
+}
+
+// RGBA of pixel k (0..3) of strip row `row`, strip columns 4g .. 4g + 3; t0 / t1: the chroma terms of columns 0,1 / 2,3
+H263_DEV uint32_t post_convert_px(const PostStrip &s, int row, int g, int k, const ChromaTerms &t0, const ChromaTerms &t1)
+{
+    const uint32_t yv = *reinterpret_cast<const uint32_t *>(&s.y[row * POST_TW + 4 * g]);
+    int gray = (int)((yv >> (8 * k)) & 0xff) * 76309;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(gray));                 // (one 24-bit multiply + plain adds, as in post_phase_store)
+#endif
+    const ChromaTerms &t = (k < 2) ? t0 : t1;
+    return bt601_pack(gray + t.r, gray + t.g, gray + t.b);
+}
+
+// Sums of the bytes 0, 2 (rb) and 1, 3 (ga) of RGBA pixels in 16-bit halves: 16 pixels sum to <= 4080 per channel.
+struct BoxSum {
+    uint32_t rb, ga;
+};
+H263_DEV void box_add(BoxSum &b, uint32_t px)
+{
+    b.rb += px & 0x00ff00ffu;
+    b.ga += (px >> 8) & 0x00ff00ffu;
+}
+// (S + n/2) / n per channel, packed as RGBA; alpha: 255 * n averages to 255 exactly.  FULL: n = 2^(2 SCALE), a shift of
+// both halves at once (the bits the shift moves from the upper half into the lower one land above bit 7 and are masked).
+template <int SCALE, bool FULL>
+H263_DEV uint32_t box_average(const BoxSum &b, uint32_t n)
+{
+    if (FULL) {
+        constexpr uint32_t half = (1u << (2 * SCALE)) >> 1, bias = half * 0x00010001u;
+        return (((b.rb + bias) >> (2 * SCALE)) & 0x00ff00ffu) | ((((b.ga + bias) >> (2 * SCALE)) & 0x00ff00ffu) << 8);
+    }
+    const uint32_t r = ((b.rb & 0xffffu) + n / 2) / n, bl = ((b.rb >> 16) + n / 2) / n, g = ((b.ga & 0xffffu) + n / 2) / n;
+    return r | (g << 8) | (bl << 16) | 0xff000000u;
+}
+
+// 4 bytes / 8 bytes to an address that is a multiple of 4 (STREAM: non-temporal, as store16_align4)
+template <bool STREAM>
+H263_DEV void store4(uint8_t *dst, uint32_t a)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (STREAM) __builtin_nontemporal_store(a, reinterpret_cast<uint32_t *>(dst));
+    else *reinterpret_cast<uint32_t *>(dst) = a;
+#else
+    memcpy(dst, &a, 4);
+#endif
+}
+template <bool STREAM>
+H263_DEV void store8_align4(uint8_t *dst, uint32_t a, uint32_t b)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    typedef u32x2 __attribute__((aligned(4))) u32x2_a4;
+    const u32x2 v = {a, b};
+    if (STREAM) __builtin_nontemporal_store(v, reinterpret_cast<u32x2_a4 *>(dst));
+    else *reinterpret_cast<u32x2_a4 *>(dst) = v;
+#else
+    const uint32_t v[2] = {a, b};
+    memcpy(dst, v, 8);
+#endif
+}
+
+// The boxes of a strip.  The strip origin is x = 4 (mod 128), y = 4 (mod 8), so its columns split into 32 groups of 4 and
+// its rows into 4 pairs / 2 quads, all aligned to the picture's box grid; the 4 wrap columns (post_wrap_x) are one such
+// group.  SCALE 1: lane = the 4 x 2 block that post_phase_store converts (columns 4(lane & 31), rows 2q, 2q + 1 for the two
+// chroma rows q = (lane >> 5) + 2 it) = two 2 x 2 boxes, one 8-byte store per block.  SCALE 2: lane = the 4 x 4 box at
+// columns 4(lane & 31), rows 4(lane >> 5) -- the same 16 pixels per lane, one 4-byte store; 32 lanes write 128 contiguous
+// bytes of an output row.  No lane needs another lane's pixels.  A box that reaches beyond the right or bottom picture
+// edge averages the pixels inside (n of them).
+template <bool STREAM_RGBA, bool INTERIOR, int SCALE>
+H263_DEV void post_store_scaled(const PostArgs &a, const PostStrip &s, uint8_t *rgba, int lane, int xl, int yl)
+{
+    const int w = (int)a.L.width, h = (int)a.L.height;
+    const uint32_t pitch = a.rgba_pitch;
+    const int g = lane & 31, gx = INTERIOR ? xl + 4 * g : post_wrap_x(a, xl + 4 * g);
+    if (!INTERIOR && !(gx >= 0 && gx < w)) return;                  // a group outside the picture: no box
+    const int ncols = INTERIOR ? 4 : (w - gx < 4 ? w - gx : 4);     // picture columns of the group
+    if (SCALE == 1) {
+#pragma unroll
+        for (int it = 0; it < 2; it++) {
+            const int q = (lane >> 5) + 2 * it, gy0 = yl + 2 * q;
+            if (!INTERIOR && (uint32_t)gy0 >= (uint32_t)h) continue;   // (gy0 is even: the box's first row decides)
+            const int nrows = INTERIOR ? 2 : (h - gy0 < 2 ? h - gy0 : 2);
+            const uint32_t cbv = *reinterpret_cast<const uint16_t *>(&s.c[0][q * POST_CW + 2 * g]);
+            const uint32_t crv = *reinterpret_cast<const uint16_t *>(&s.c[1][q * POST_CW + 2 * g]);
+            const ChromaTerms t0 = bt601_chroma_terms(cbv & 0xff, crv & 0xff);
+            const ChromaTerms t1 = bt601_chroma_terms(cbv >> 8, crv >> 8);
+            BoxSum b[2] = {{0u, 0u}, {0u, 0u}};
+#pragma unroll
+            for (int rr = 0; rr < 2; rr++) {
+                if (!INTERIOR && rr >= nrows) continue;
+#pragma unroll
+                for (int k = 0; k < 4; k++)
+                    if (INTERIOR || k < ncols) box_add(b[k >> 1], post_convert_px(s, 2 * q + rr, g, k, t0, t1));
+            }
+            const uint32_t off = (uint32_t)(gy0 >> 1) * pitch + (uint32_t)(gx >> 1) * 4u;
+            if (INTERIOR || (nrows == 2 && ncols == 4)) {
+                store8_align4<STREAM_RGBA>(rgba + off, box_average<1, true>(b[0], 4), box_average<1, true>(b[1], 4));
+            } else {
+                const uint32_t n0 = (uint32_t)nrows * (ncols < 2 ? 1u : 2u), n1 = (uint32_t)nrows * (uint32_t)(ncols - 2);
+                if (ncols > 2) store8_align4<STREAM_RGBA>(rgba + off, box_average<1, false>(b[0], n0), box_average<1, false>(b[1], n1));
+                else store4<STREAM_RGBA>(rgba + off, box_average<1, false>(b[0], n0));
+            }
+        }
+    } else {
+        const int qq = lane >> 5, gy0 = yl + 4 * qq;                    // rows 4 qq .. 4 qq + 3 of the strip = chroma rows 2 qq, 2 qq + 1
+        if (!INTERIOR && (uint32_t)gy0 >= (uint32_t)h) return;
+        const int nrows = INTERIOR ? 4 : (h - gy0 < 4 ? h - gy0 : 4);
+        BoxSum b = {0u, 0u};
+#pragma unroll
+        for (int it = 0; it < 2; it++) {
+            const int q = 2 * qq + it;
+            if (!INTERIOR && 2 * it >= nrows) continue;
+            const uint32_t cbv = *reinterpret_cast<const uint16_t *>(&s.c[0][q * POST_CW + 2 * g]);
+            const uint32_t crv = *reinterpret_cast<const uint16_t *>(&s.c[1][q * POST_CW + 2 * g]);
+            const ChromaTerms t0 = bt601_chroma_terms(cbv & 0xff, crv & 0xff);
+            const ChromaTerms t1 = bt601_chroma_terms(cbv >> 8, crv >> 8);
+#pragma unroll
+            for (int rr = 0; rr < 2; rr++) {
+                if (!INTERIOR && 2 * it + rr >= nrows) continue;
+#pragma unroll
+                for (int k = 0; k < 4; k++)
+                    if (INTERIOR || k < ncols) box_add(b, post_convert_px(s, 2 * q + rr, g, k, t0, t1));
+            }
+        }
+        const uint32_t off = (uint32_t)(gy0 >> 2) * pitch + (uint32_t)(gx >> 2) * 4u;
+        if (INTERIOR || (nrows == 4 && ncols == 4)) store4<STREAM_RGBA>(rgba + off, box_average<2, true>(b, 16));
+        else store4<STREAM_RGBA>(rgba + off, box_average<2, false>(b, (uint32_t)(nrows * ncols)));
+    }
+}
+
 // STREAM_RGBA: the RGBA stores are non-temporal.  k_frame sets it: the 8.3 MB of RGBA per picture then no longer push
 // the planes that the reconstruction half of the same launch (and the next one) reads out of the L2 / infinity cache --
 // 10 % on a frame index (profiles/README.md).  k_post on its own keeps plain stores: alone, it is 10 % faster with them.
-template <bool STREAM_RGBA, bool INTERIOR = false>
+// SCALE: -1 (the default kernels) = today's output, w x h tightly packed; 0, 1, 2 = the LAYOUT instantiations: rows
+// a.rgba_pitch bytes apart, boxes of 2^SCALE x 2^SCALE pixels averaged (post_store_scaled).
+template <bool STREAM_RGBA, bool INTERIOR = false, int SCALE = -1>
 H263_DEV void post_phase_store(const PostArgs &a, PostStrip &s, int lane, int sx, int sy, int pic)
 {
     const int xl = sx * POST_TW - POST_OX, yl = sy * POST_SH - 4;
     const int w = (int)a.L.width, h = (int)a.L.height, cw = (int)a.L.cwidth, ch = (int)a.L.cheight;
 
-    if (INTERIOR || a.rgba) {
+    if (SCALE > 0) {
+        if (INTERIOR || a.rgba) post_store_scaled<STREAM_RGBA, INTERIOR, SCALE>(a, s, a.rgba + (size_t)pic * post_out_picture_bytes<SCALE>(a), lane, xl, yl);
+    } else if (INTERIOR || a.rgba) {
         // uniform 64-bit base of the picture + 32-bit lane offsets (w * h * 4 < 2^32: layout_fits)
 #if defined(H263MI_TIMING_RGBA_FOLD)
         uint8_t *rgba = a.rgba;
 #else
-        uint8_t *rgba = a.rgba + (size_t)pic * w * h * 4;
+        uint8_t *rgba = SCALE < 0 ? a.rgba + (size_t)pic * w * h * 4 : a.rgba + (size_t)pic * post_out_picture_bytes<SCALE>(a);
 #endif
         const int g = lane & 31, gx = INTERIOR ? xl + 4 * g : post_wrap_x(a, xl + 4 * g);
         // the lane's four pixels: all inside the picture (the only case away from the left / right picture edge),
         // or some of them (a picture whose width is not a multiple of 4), or none
         const bool col_full = INTERIOR || (gx >= 0 && gx + 4 <= w), col_some = INTERIOR || (gx >= 0 && gx < w);
-        const uint32_t row_bytes = (uint32_t)w * 4u;
+        const uint32_t row_bytes = SCALE < 0 ? (uint32_t)w * 4u : a.rgba_pitch;     // (SCALE 0: the layout's pitch, full size)
 #pragma unroll
         for (int it = 0; it < 2; it++) {
             // a lane converts a 4x2 block: two rows that share one chroma row (nearest-neighbour
@@ -564,7 +708,7 @@ H263_DEV void post_phase_store(const PostArgs &a, PostStrip &s, int lane, int sx
             const ChromaTerms t1 = bt601_chroma_terms(cbv >> 8, crv >> 8);
             const int gy0 = yl + 2 * q;
             // byte offset of pixel (gx, gy0), modulo 2^32: gy0 may be -1 with row gy0 + 1 inside the picture
-            const uint32_t off0 = ((uint32_t)gy0 * (uint32_t)w + (uint32_t)gx) * 4u;
+            const uint32_t off0 = SCALE < 0 ? ((uint32_t)gy0 * (uint32_t)w + (uint32_t)gx) * 4u : (uint32_t)gy0 * row_bytes + (uint32_t)gx * 4u;
 #pragma unroll
             for (int rr = 0; rr < 2; rr++) {
                 const int row = 2 * q + rr, gy = gy0 + rr;

@@ -391,6 +391,41 @@ int h263mi_render_rgba(const h263mi_state *cs, uint8_t strength, uint8_t *rgba)
     return H263MI_OK;
 }
 
+int h263mi_render_rgba_layout(const h263mi_state *cs, uint8_t strength, const h263mi_rgba_layout *layout, uint8_t *rgba)
+{
+    h263mi_state *s = const_cast<h263mi_state *>(cs);
+    if (!s || !rgba || (layout && layout->offsets)) return H263MI_ERR_INVALID_ARGUMENT;
+    if (!s->has_last || !s->b) return H263MI_ERR_NO_PICTURE;
+    h263mi_batch *b = s->b;
+    uint32_t ow = 0, oh = 0;
+    uint64_t extent = 0;
+    RC_TRY(rgba_layout_extent(1, b->L.width, b->L.height, layout, &ow, &oh, &extent));
+    h263mi_batch::Strengths st;
+    RC_TRY(state_strength(s, strength, st));
+    DeviceGuard g(s->cfg.device_id);
+    // rendered tightly (W' x H') into the device scratch, then copied out row by row when the caller's pitch is wider
+    const size_t row = (size_t)ow * 4, bytes = row * oh, pitch = layout && layout->row_pitch ? (size_t)layout->row_pitch : row;
+    if (bytes > s->cap_rgba) {
+        if (s->d_rgba) (void)hipFree(s->d_rgba);
+        s->d_rgba = nullptr; s->cap_rgba = 0;
+        HIP_TRY(hipMalloc((void **)&s->d_rgba, bytes));
+        s->cap_rgba = bytes;
+    }
+    h263mi_rgba_layout tight{};
+    tight.scale_log2 = layout ? layout->scale_log2 : 0;
+    h263mi_batch::RgbaLayout saved = std::move(b->layout), lay;
+    RC_TRY(rgba_layout_extent(1, b->L.width, b->L.height, &tight, nullptr, nullptr, &lay.bytes, &lay.kernel));
+    if (lay.placed()) lay.offsets.assign(1, 0);
+    b->layout = std::move(lay);
+    const int rc = b->render(st, s->d_rgba, nullptr);
+    b->layout = std::move(saved);
+    RC_TRY(rc);
+    if (pitch == row) HIP_TRY(hipMemcpyAsync(rgba, s->d_rgba, bytes, hipMemcpyDeviceToHost, b->stream));
+    else HIP_TRY(hipMemcpy2DAsync(rgba, pitch, s->d_rgba, row, row, oh, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    return H263MI_OK;
+}
+
 int h263mi_render_rgba_pinned(const h263mi_state *cs, uint8_t strength, uint8_t *rgba_pinned)
 {
     h263mi_state *s = const_cast<h263mi_state *>(cs);

@@ -85,6 +85,8 @@ EXPORTS = [
     "h263mi_batch_decode_ps", "h263mi_batch_decode_events_ps", "h263mi_batch_render_rgba_ps",
     "h263mi_batch_decode_next_pictures_ps", "h263mi_mixed_decode_next_pictures_ps",
     "h263mi_set_ranks_per_node", "h263mi_batch_host_placement", "h263mi_debug_host_placement",
+    # ABI 7, additive: scaled RGBA with a row pitch and per-stream placement
+    "h263mi_rgba_layout_extent", "h263mi_batch_set_rgba_layout", "h263mi_render_rgba_layout",
 ]
 STRENGTH_FROM_HEADER = 0xFF
 CFG_OVERLAP_POST, CFG_PIPELINE_POST, CFG_TRUSTED_ARRAYS = 1, 2, 4
@@ -113,6 +115,38 @@ class FrameView(C.Structure):
                 ("pquant", C.c_uint8), ("use_deblocker", C.c_uint8), ("reserved", C.c_uint8 * 3),
                 ("dev_y", C.c_void_p), ("dev_cb", C.c_void_p), ("dev_cr", C.c_void_p),
                 ("dev_pitch_y", C.c_uint32), ("dev_pitch_c", C.c_uint32)]
+
+
+class RgbaLayout(C.Structure):
+    """h263mi_rgba_layout: output picture ceil(w / 2^scale_log2) x ceil(h / 2^scale_log2) box averages, rows row_pitch bytes
+    apart (0 = tight), stream s's picture at byte offsets[s] (NULL = s * H' * pitch)."""
+    _fields_ = [("scale_log2", C.c_uint8), ("reserved", C.c_uint8 * 7), ("row_pitch", C.c_uint64),
+                ("offsets", C.POINTER(C.c_uint64))]
+
+
+def make_rgba_layout(scale_log2=0, row_pitch=0, offsets=None):
+    """-> (RgbaLayout, the offsets array it points into: keep it alive with the struct)"""
+    lay = RgbaLayout()
+    lay.scale_log2 = scale_log2
+    lay.row_pitch = row_pitch
+    keep = None
+    if offsets is not None:
+        keep = np.ascontiguousarray(offsets, dtype=np.uint64)
+        lay.offsets = keep.ctypes.data_as(C.POINTER(C.c_uint64))
+    return lay, keep
+
+
+def rgba_layout_extent(n_streams, width, height, scale_log2=0, row_pitch=0, offsets=None, layout=None):
+    """h263mi_rgba_layout_extent -> (W', H', bytes the output buffer must hold); H263Error when the layout is refused.
+    layout: an RgbaLayout to pass as it is (else one is made of the other arguments)."""
+    keep = None
+    if layout is None:
+        layout, keep = make_rgba_layout(scale_log2, row_pitch, offsets)
+    ow, oh, nb = C.c_uint16(), C.c_uint16(), C.c_uint64()
+    _check(lib().h263mi_rgba_layout_extent(n_streams, width, height, C.byref(layout), C.byref(ow), C.byref(oh), C.byref(nb)),
+           "rgba_layout_extent")
+    del keep
+    return ow.value, oh.value, nb.value
 
 
 class KernelTimes(C.Structure):
@@ -244,6 +278,9 @@ def lib():
         L.h263mi_set_ranks_per_node.restype = None
         L.h263mi_batch_host_placement.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(u32), vp, u32]
         L.h263mi_debug_host_placement.argtypes = [vp, u32, i32, u32, C.c_char_p, C.POINTER(i32), vp, u32, C.POINTER(u32)]
+        L.h263mi_rgba_layout_extent.argtypes = [u32, u16, u16, vp, C.POINTER(u16), C.POINTER(u16), C.POINTER(C.c_uint64)]
+        L.h263mi_batch_set_rgba_layout.argtypes = [vp, vp]
+        L.h263mi_render_rgba_layout.argtypes = [vp, u8, vp, vp]
         L.h263mi_default_parser_threads.restype = u32
         L.h263mi_default_parser_threads.argtypes = [u32, C.POINTER(u32)]
         _lib = L
@@ -414,6 +451,20 @@ class H263State:
             raise H263Error(ERR_NO_PICTURE, "render_rgba")
         out = np.empty(v.width * v.height * 4, np.uint8)
         _check(lib().h263mi_render_rgba(self._h, strength, _p(out)), "render_rgba")
+        return out
+
+    def render_rgba_layout(self, strength, scale_log2=0, row_pitch=0):
+        """h263mi_render_rgba_layout: H' * pitch bytes (rows of 4W' bytes; what lies between rows is zero here)"""
+        v = self._view(lib().h263mi_get_last_picture, "get_last_picture")
+        if v is None:
+            raise H263Error(ERR_NO_PICTURE, "render_rgba_layout")
+        ow, oh, nb = rgba_layout_extent(1, v.width, v.height, scale_log2, row_pitch)
+        out = np.zeros(nb + (row_pitch - 4 * ow if row_pitch else 0), np.uint8)
+        return self.render_rgba_layout_into(strength, out, scale_log2, row_pitch)
+
+    def render_rgba_layout_into(self, strength, out, scale_log2=0, row_pitch=0):
+        lay, _ = make_rgba_layout(scale_log2, row_pitch)
+        _check(lib().h263mi_render_rgba_layout(self._h, strength, C.byref(lay), _p(out)), "render_rgba_layout")
         return out
 
     def render_rgba_pinned(self, strength, pinned):
@@ -647,6 +698,15 @@ class Batch:
         nb = (C.c_uint32 * n)(*[len(f) - 1 for f in fs])
         ne = (C.c_uint32 * n)(*[len(e) for e in evs])
         _check(lib().h263mi_batch_submit_host_events(self._h, picture_type, pm, nm, pf, nb, pe, ne), "batch_submit_host_events")
+
+    def set_rgba_layout(self, scale_log2=0, row_pitch=0, offsets=None, default=False):
+        """h263mi_batch_set_rgba_layout (default=True: back to today's layout)"""
+        if default:
+            _check(lib().h263mi_batch_set_rgba_layout(self._h, None), "batch_set_rgba_layout")
+            return
+        lay, keep = make_rgba_layout(scale_log2, row_pitch, offsets)
+        _check(lib().h263mi_batch_set_rgba_layout(self._h, C.byref(lay)), "batch_set_rgba_layout")
+        del keep
 
     def render_rgba(self, strength, d_rgba, d_deblocked=None, strengths=None):
         keep, ps = self._strengths(strengths)

@@ -136,6 +136,20 @@ public:
         check(h263mi_render_rgba(s_, strength, rgba.data()));
         return rgba;
     }
+    // the same in an output layout (h263mi_rgba_layout, offsets NULL): H' rows of 4W' bytes, row_pitch apart -- H' * pitch
+    // bytes, the ones between rows zero
+    std::vector<uint8_t> render_rgba(uint8_t strength, const h263mi_rgba_layout &layout) const
+    {
+        h263mi_frame_view v;
+        check(h263mi_get_last_picture(s_, &v));
+        uint16_t ow = 0, oh = 0;
+        uint64_t bytes = 0;
+        check(h263mi_rgba_layout_extent(1, v.width, v.height, &layout, &ow, &oh, &bytes));
+        const uint64_t pitch = layout.row_pitch ? layout.row_pitch : 4ull * ow;
+        std::vector<uint8_t> rgba((size_t)(pitch * oh));
+        check(h263mi_render_rgba_layout(s_, strength, &layout, rgba.data()));
+        return rgba;
+    }
 
     // the same straight into page-locked memory of the caller (h263mi_host_alloc / h263mi_host_register): the buffer a
     // renderer reuses for every picture instead of the fresh Vec<u8> of bt601.rs:128; `rgba` holds width * height * 4 bytes

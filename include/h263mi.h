@@ -367,6 +367,34 @@ int h263mi_batch_decode_events_ps(h263mi_batch *b, uint8_t picture_type, const h
                                   const uint32_t *d_block_first_event, const uint32_t *d_events, const uint64_t *d_coeff_base,
                                   uint64_t coeff_pool_blocks, uint64_t n_events, uint8_t strength, const uint8_t *strengths,
                                   uint8_t *d_rgba, uint8_t *d_deblocked);
+/*
+ * RGBA OUTPUT LAYOUT (additive, ABI 7): the output picture is W' x H' = ceil(w / f) x ceil(h / f), f = 1 << scale_log2,
+ * each pixel the average of the f x f box of full-size RGBA it covers (only the part inside the picture, n pixels:
+ * (sum + n/2) / n per channel, alpha 255; f = 1 is the full-size picture bit for bit), its rows row_pitch bytes apart,
+ * stream s's picture at byte offsets[s] of the output buffer.  The deblocked planes (d_deblocked) stay full size.
+ */
+typedef struct h263mi_rgba_layout {
+    uint8_t  scale_log2;        /* 0: w x h, 1: ceil(w/2) x ceil(h/2), 2: ceil(w/4) x ceil(h/4) */
+    uint8_t  reserved[7];       /* zero */
+    uint64_t row_pitch;         /* bytes from one output row to the next; 0 = W' * 4 */
+    const uint64_t *offsets;    /* HOST array: byte offset of stream s's picture in the output buffer; NULL = s * H' * pitch */
+} h263mi_rgba_layout;
+
+/* Pure host function, no HIP call: validates and returns W', H' and the bytes the output buffer must hold (layout NULL:
+ * today's, n * w*h*4).  H263MI_ERR_INVALID_ARGUMENT: scale_log2 > 2 or a reserved byte set; row_pitch below 4W' or not a
+ * multiple of 4; an offset not a multiple of 4; a picture row that crosses a pitch boundary (offset mod pitch + 4W' > pitch);
+ * (H'-1) * pitch + 4W' >= 2^32; two streams' rectangles (row range x byte-column range) sharing a byte. */
+int h263mi_rgba_layout_extent(uint32_t n_streams, uint16_t width, uint16_t height, const h263mi_rgba_layout *layout,
+                              uint16_t *out_w, uint16_t *out_h, uint64_t *bytes);
+/* Every later call on this batch that writes d_rgba follows the layout (h263mi_batch_decode[_ps], _decode_events[_ps],
+ * _render_rgba[_ps], _decode_next_pictures[_ex|_ps]; a deferred rendering of H263MI_CFG_PIPELINE_POST keeps the layout
+ * that was in force when it was requested); NULL = the default (today's).  Offsets are copied.  A checked batch holds d_rgba
+ * to the layout's extent. */
+int h263mi_batch_set_rgba_layout(h263mi_batch *b, const h263mi_rgba_layout *layout);
+/* One state, into HOST memory: H' rows of 4*W' bytes at rgba + r * pitch.  Bytes between rows are untouched; offsets must
+ * be NULL. */
+int h263mi_render_rgba_layout(const h263mi_state *s, uint8_t strength, const h263mi_rgba_layout *layout, uint8_t *rgba);
+
 /* deblock (strength 0 = off) + BT.601 of every stream's last picture into d_rgba
  * (DEVICE, n_streams * w*h*4 bytes, stream-major); d_deblocked (DEVICE, may be NULL)
  * additionally receives the filtered planes, n_streams * (w*h + 2*cw*ch) bytes as
