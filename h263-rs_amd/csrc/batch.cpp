@@ -35,14 +35,9 @@ int h263mi_batch::alloc(uint32_t n_streams, uint32_t w, uint32_t h)
             fprintf(stderr, "h263mi frame store: %p .. +%zu\n", (void *)frames[0], 2 * set_bytes);
         HIP_TRY(hipMemsetAsync(frames[0], 0, 2 * set_bytes, stream));
     }
-    if (!d_status) {
-        HIP_TRY(hipMalloc((void **)&d_status, (size_t)n * sizeof(uint32_t)));
-        HIP_TRY(hipHostMalloc((void **)&h_status, (size_t)n * sizeof(uint32_t), hipHostMallocDefault));
-        HIP_TRY(hipMalloc((void **)&d_state, (size_t)n * kStateSlots * sizeof(uint32_t)));
-        HIP_TRY(hipHostMalloc((void **)&h_state, (size_t)n * kStateSlots * sizeof(uint32_t), hipHostMallocDefault));
-        for (hipEvent_t &e : state_copied) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    HIP_TRY(hipMemsetAsync(d_status, 0, (size_t)n * sizeof(uint32_t), stream));
+    RC_TRY(status.reserve(n, 0, placement));
+    RC_TRY(word_ring.make(n, placement));
+    HIP_TRY(hipMemsetAsync(status.d, 0, (size_t)n * sizeof(uint32_t), stream));
     ss.assign(n, StreamState());
     pending.set.assign(n, -1);
     layout = RgbaLayout();
@@ -77,63 +72,6 @@ bool h263mi_batch::pending_uniform() const
     for (int8_t v : pending.set)
         if (v != pending.set[0]) return false;
     return true;
-}
-
-int h263mi_batch::push_stream_words(const std::vector<uint32_t> &words, const uint32_t **d_out, hipStream_t on)
-{
-    const unsigned slot = state_slot++ % kStateSlots;
-    HIP_TRY(hipEventSynchronize(state_copied[slot]));         // (its previous copy has left the host buffer)
-    uint32_t *h = h_state + (size_t)slot * n, *d = d_state + (size_t)slot * n;
-    memcpy(h, words.data(), (size_t)n * sizeof(uint32_t));
-    RC_TRY(time_close());                                      // a copy is not part of any kernel's time
-    HIP_TRY(hipMemcpyAsync(d, h, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, on));
-    HIP_TRY(hipEventRecord(state_copied[slot], on));
-    *d_out = d;
-    return H263MI_OK;
-}
-
-int h263mi_batch::make_ptr_ring()
-{
-    HIP_TRY(hipHostMalloc((void **)&h_ptrs, (size_t)n * kPtrSlots * sizeof(uint8_t *), hipHostMallocDefault));
-    HIP_TRY(hipMalloc((void **)&d_ptrs, (size_t)n * kPtrSlots * sizeof(uint8_t *)));
-    for (hipEvent_t &e : ptrs_copied) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    return H263MI_OK;
-}
-
-void h263mi_batch::release_ptr_ring()
-{
-    if (d_ptrs) (void)hipFree(d_ptrs);
-    if (h_ptrs) (void)hipHostFree(h_ptrs);
-    d_ptrs = nullptr;
-    h_ptrs = nullptr;
-    for (hipEvent_t &e : ptrs_copied) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-    }
-    ptrs_ready = false;
-}
-
-int h263mi_batch::push_rgba_ptrs(uint8_t *const *host_ptrs, uint8_t *const **d_out, hipStream_t on)
-{
-    if (!ptrs_ready) {
-        // all or nothing: a failure half-way (the host block is there, the device block or an event is not) frees what
-        // was made, so that the next call starts over instead of synchronising on an event that does not exist
-        const int rc = make_ptr_ring();
-        if (rc != H263MI_OK) {
-            release_ptr_ring();
-            return rc;
-        }
-        ptrs_ready = true;
-    }
-    const unsigned slot = ptrs_slot++ % kPtrSlots;
-    HIP_TRY(hipEventSynchronize(ptrs_copied[slot]));
-    uint8_t **h = h_ptrs + (size_t)slot * n, **d = d_ptrs + (size_t)slot * n;
-    memcpy(h, host_ptrs, (size_t)n * sizeof(uint8_t *));
-    RC_TRY(time_close());
-    HIP_TRY(hipMemcpyAsync(d, h, (size_t)n * sizeof(uint8_t *), hipMemcpyHostToDevice, on));
-    HIP_TRY(hipEventRecord(ptrs_copied[slot], on));
-    *d_out = d;
-    return H263MI_OK;
 }
 
 int h263mi_batch::forget_pictures()
@@ -181,15 +119,8 @@ h263mi_batch::~h263mi_batch()
     if (ev_recon_done) (void)hipEventDestroy(ev_recon_done);
     for (hipEvent_t e : ev_post_done)
         if (e) (void)hipEventDestroy(e);
-    if (d_status) (void)hipFree(d_status);
-    if (h_status) (void)hipHostFree(h_status);
-    if (d_state) (void)hipFree(d_state);
-    if (h_state) (void)hipHostFree(h_state);
-    release_ptr_ring();
-    for (hipEvent_t e : state_copied)
-        if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ev_pool) (void)hipEventDestroy(e);
-    release_staging();
+    // (the staging memory, the rings and the status words go with the members)
 }
 
 // =========================================================================================
@@ -249,7 +180,7 @@ int h263mi_batch::submit(uint8_t picture_type, const MbRecord *d_mbs, const h263
     a.mb_base = src.mb_base;
     a.groups_per_picture = recon_tiles_x(L) * L.mbh;
     a.coeff_base = src.coeff_base;
-    a.status = d_status;
+    a.status = status.d;
     a.coeff_pool_blocks = src.pool_blocks;
     a.coeff_checked = src.checked ? 1u : 0u;
     a.n_pictures = n;
@@ -288,7 +219,7 @@ int h263mi_batch::submit(uint8_t picture_type, const MbRecord *d_mbs, const h263
         }
         // (a batch of more than STREAM_WORDS_INLINE streams: the words go to device memory, a small copy in front of the launch)
         const uint32_t *d_words = nullptr;
-        if (!words_inline) RC_TRY(push_stream_words(words, &d_words, stream));
+        if (!words_inline) RC_TRY(upload(word_ring, words.data(), &d_words, stream));
         a.stream_state = d_words;
         a.ref = frames[0];                   // (never used with per-stream words; never null)
         a.cur = frames[1];
@@ -365,7 +296,7 @@ int h263mi_batch::launch_post_sets(const std::vector<int8_t> &sets, const Streng
             words[i] = STREAM_RECON_SKIP | (sets[i] < 0 ? STREAM_POST_SKIP : (sets[i] == 1 ? STREAM_POST_SET1 : 0u)) |
                        ((uint32_t)strength.of(i) << STREAM_STRENGTH_SHIFT);
         const uint32_t *d_words = nullptr;
-        if (!words_inline) RC_TRY(push_stream_words(words, &d_words, on));
+        if (!words_inline) RC_TRY(upload(word_ring, words.data(), &d_words, on));
         a.stream_state = d_words;
         a.frame_set[0] = frames[0];
         a.frame_set[1] = frames[1];
@@ -383,7 +314,7 @@ int h263mi_batch::note_pending(const Strengths &strength, uint8_t *d_rgba, uint8
     std::vector<uint8_t *> placed;
     if (!host_ptrs && layout_ptrs(d_rgba, placed)) host_ptrs = placed.data();
     pending.out = layout.kernel;
-    if (host_ptrs) RC_TRY(push_rgba_ptrs(host_ptrs, &pending.rgba_ptrs, stream));
+    if (host_ptrs) RC_TRY(upload(ptr_ring, host_ptrs, &pending.rgba_ptrs, stream));
     pending.valid = d_rgba || d_planes || host_ptrs;
     pending.strength = strength;
     pending.rgba = d_rgba;
@@ -414,7 +345,7 @@ int h263mi_batch::render(const Strengths &strength, uint8_t *d_rgba, uint8_t *d_
     }
     if (overlap_post) HIP_TRY(hipStreamWaitEvent(post_stream, ev_recon_done, 0));
     uint8_t *const *d_out_ptrs = nullptr;
-    if (host_ptrs) RC_TRY(push_rgba_ptrs(host_ptrs, &d_out_ptrs, stream_of(1)));
+    if (host_ptrs) RC_TRY(upload(ptr_ring, host_ptrs, &d_out_ptrs, stream_of(1)));
     RC_TRY(launch_post_sets(sets, strength, d_rgba, d_planes, stream_of(1), d_out_ptrs, layout.kernel));
     // a later reconstruction may overwrite a frame set only when every post-processing that reads it is done: streams
     // that have drifted apart read both sets
@@ -429,12 +360,12 @@ int h263mi_batch::sync(int *stream_rc)
     RC_TRY(flush_pending());
     RC_TRY(time_close());
     if (overlap_post) HIP_TRY(hipStreamSynchronize(post_stream));
-    HIP_TRY(hipMemcpyAsync(h_status, d_status, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(status.h, status.d, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     int first_error = H263MI_OK;
     for (uint32_t i = 0; i < n; i++) {
         StreamState &t = ss[i];
-        const uint32_t st = h_status[i];
+        const uint32_t st = status.h[i];
         int rc = H263MI_OK;
         if (st) {
             // A picture the device rejected must not become the stream's last / reference picture.  One picture since
@@ -455,7 +386,7 @@ int h263mi_batch::sync(int *stream_rc)
         t.unsynced = 0;
         if (stream_rc) stream_rc[i] = rc;
     }
-    if (first_error != H263MI_OK) HIP_TRY(hipMemsetAsync(d_status, 0, (size_t)n * sizeof(uint32_t), stream));
+    if (first_error != H263MI_OK) HIP_TRY(hipMemsetAsync(status.d, 0, (size_t)n * sizeof(uint32_t), stream));
     return first_error;
 }
 

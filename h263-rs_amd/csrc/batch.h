@@ -3,9 +3,10 @@
 // timing, and the pinned staging slots of the entry points that take host data.
 //   batch.cpp          frame store, submit / render / sync, timing, the entry points over DEVICE records
 //   batch_staging.cpp  host records and bitstreams -> pinned staging -> one launch (h263mi_batch_submit_host*,
-//                      h263mi_batch_decode_next_pictures*)
+//                      h263mi_batch_decode_next_pictures*), and the checks of a caller's host arrays
 //   mixed_set.cpp      streams of different picture sizes: one batch per size class
-//   state.cpp          the H263State mirror: a batch of one stream fed with host records
+//   state.cpp          the H263State mirror: a batch of one stream fed with host records through batch_submit_host
+//   pinned.h           pinned host + device buffer pairs and the upload rings built from them
 #pragma once
 
 #include <memory>
@@ -13,6 +14,7 @@
 
 #include "../host/bitstream.hpp"
 #include "host_common.h"
+#include "pinned.h"
 #include "worker_pool.h"
 
 // Where the coefficients of one submit live, how far they may be read, and -- sparse records -- where the records are.
@@ -38,7 +40,6 @@ struct h263mi_rgba_out {
 struct h263mi_batch {
     int device = 0;
     hipStream_t stream = nullptr;
-    static constexpr unsigned kPtrSlots = 4;
     // H263MI_CFG_OVERLAP_POST: k_post runs on a second stream so that the post-processing of picture i overlaps
     // the reconstruction of picture i+1 (k_recon is VALU-heavy, k_post store-heavy).  Legal with two frame sets:
     // post(i) reads set i; recon(i+1) reads set i and overwrites the set of picture i-1, which post(i-1) must have
@@ -69,7 +70,7 @@ struct h263mi_batch {
     };
     // The output layout of the RGBA (h263mi_batch_set_rgba_layout).  `kernel`: what the kernels are told (pitch 0: the default
     // kernels); `offsets` (empty = s * H' * pitch): where stream s's picture
-    // starts in the caller's buffer -- handed to the kernels as per-stream pointers (push_rgba_ptrs).
+    // starts in the caller's buffer -- handed to the kernels as per-stream pointers (ptr_ring).
     typedef h263mi_rgba_out OutLayout;
     struct RgbaLayout {
         OutLayout kernel;
@@ -85,11 +86,8 @@ struct h263mi_batch {
         uint8_t *const *rgba_ptrs = nullptr;   // DEVICE array of per-stream output pointers (a batch inside a mixed-size set)
         std::vector<int8_t> set;               // per stream: frame set it reads, -1 = nothing to post-process
     } pending;
-    // per-stream output pointers for the kernels: ring of pinned host slots + device arrays, like the state words
-    uint8_t **h_ptrs = nullptr, **d_ptrs = nullptr;
-    hipEvent_t ptrs_copied[kPtrSlots] = {nullptr, nullptr, nullptr, nullptr};
-    unsigned ptrs_slot = 0;
-    bool ptrs_ready = false;            // the ring above exists completely (push_rgba_ptrs makes it on first use)
+    // per-stream output pointers for the kernels (made on first use)
+    h263mi::UploadRing<uint8_t *> ptr_ring;
     uint32_t n = 0;
     h263mi::FrameLayout L{};
     uint8_t *frames[2] = {nullptr, nullptr};   // ping-pong frame sets, n * frame_bytes each
@@ -105,13 +103,9 @@ struct h263mi_batch {
         bool active = true;                    // takes part in the next submit (h263mi_batch_set_active)
     };
     std::vector<StreamState> ss;
-    uint32_t *d_status = nullptr;              // one word per stream
-    uint32_t *h_status = nullptr;              // pinned
-    // per-stream words for the kernels: a small ring of pinned host slots + one device array per slot
-    static constexpr unsigned kStateSlots = 4;
-    uint32_t *h_state = nullptr, *d_state = nullptr;
-    hipEvent_t state_copied[kStateSlots] = {nullptr, nullptr, nullptr, nullptr};
-    unsigned state_slot = 0;
+    h263mi::PinnedPair<uint32_t> status;       // one word per stream
+    // per-stream words for the kernels (made in alloc())
+    h263mi::UploadRing<uint32_t> word_ring;
     // (what sync() falls back to when the device reports an error -- state.rs:142, 464-487: an error leaves the state
     // unchanged -- is each stream's good_cur / good_has_ref, valid as long as at most one picture was submitted for the
     // stream since: the frame set it names is the one the ping-pong has not overwritten yet)
@@ -119,19 +113,21 @@ struct h263mi_batch {
     // host-record staging for h263mi_batch_submit_host: two slots (pinned host + device) used alternately, so
     // that packing picture i+1 overlaps the copy and the kernel of picture i
     struct HostStaging {
-        h263mi::MbRecord *h_mbs = nullptr, *d_mbs = nullptr;
-        int16_t *h_coeffs = nullptr, *d_coeffs = nullptr;
-        // ONE buffer (pinned host + device) for everything small that goes with a call, so that it crosses the link in one copy:
+        h263mi::PinnedPair<h263mi::MbRecord> mbs;
+        h263mi::PinnedPair<int16_t> coeffs;    // dense blocks, 64 each
+        // ONE buffer for everything small that goes with a call, so that it crosses the link in one copy:
         // [base: 2n x u64 -- [0, n) coefficient base per stream, [n, 2n) record base (sparse records)]
         // [index: n x groups per picture x u32 -- sparse records, one word per group of 8 macroblocks]
         // [events: rebased block offsets, then the events -- sparse coefficient transport]
-        uint32_t *h_words = nullptr, *d_words = nullptr;
-        size_t cap_words = 0;
-        uint64_t *h_base = nullptr, *d_base = nullptr;       // (into h_words / d_words)
+        h263mi::PinnedPair<uint32_t> words;
+        uint64_t *h_base = nullptr, *d_base = nullptr;       // (into words)
         uint32_t *h_index = nullptr, *d_index = nullptr;
         uint32_t *h_events = nullptr, *d_events = nullptr;
-        size_t cap_blocks = 0;
         hipEvent_t done = nullptr;             // recorded after the kernel that reads the slot
+        ~HostStaging()
+        {
+            if (done) (void)hipEventDestroy(done);
+        }
     } host_stg[2];
     unsigned host_slot = 0;
     // h263mi_batch_decode_next_pictures: what each stream remembers of its last picture header (state.rs:143-167)
@@ -172,13 +168,15 @@ struct h263mi_batch {
     // every stream takes part and all agree on (cur, has_ref): the kernels need no per-stream words
     bool uniform() const;
     bool pending_uniform() const;
-    // hand the kernels one word per stream: fills the next slot of the ring and queues its copy
-    // `on`: the stream whose kernel reads the words (the copy is ordered in front of that kernel by being on its stream)
-    int push_stream_words(const std::vector<uint32_t> &words, const uint32_t **d_out, hipStream_t on);
-    int make_ptr_ring();
-    void release_ptr_ring();
-    // hand the post-processing one output pointer per stream (host array of n DEVICE pointers): next ring slot + its copy
-    int push_rgba_ptrs(uint8_t *const *host_ptrs, uint8_t *const **d_out, hipStream_t on);
+    // hand the kernels one element per stream (stream words, output pointers): the ring's next slot and its copy, queued on
+    // `on`, the stream of the kernel that reads them
+    template <typename T>
+    int upload(h263mi::UploadRing<T> &ring, const T *host, const T **d_out, hipStream_t on)
+    {
+        RC_TRY(ring.make(n, placement));
+        RC_TRY(time_close());                  // a copy is not part of any kernel's time
+        return ring.push(host, d_out, on);
+    }
     int forget_pictures();
     // one stream forgets its pictures (the seeking rule of state.rs:134-137 for a single H263State of the batch)
     int forget_stream(uint32_t i);
@@ -190,7 +188,6 @@ struct h263mi_batch {
     // words in front of the events in HostStaging::h_words: the two base arrays and the sparse-record index
     size_t head_words() const { return 4 * (size_t)n + (size_t)n * h263mi::recon_tiles_x(L) * L.mbh; }
     int ensure_host_staging(HostStaging &g2, size_t n_blocks, size_t n_event_words = 0);
-    void release_staging();
 
     // ---- launch timing (h263mi_batch_timing_begin / _end); kernel ids: 0 k_recon, 1 k_post, 2 k_frame
     hipStream_t stream_of(int kernel_id) const { return (kernel_id == 1 && overlap_post) ? post_stream : stream; }
@@ -248,11 +245,19 @@ struct DirectWords {
     size_t pitch_blocks, pitch_events;
 };
 
+// The checks of a caller's host arrays (batch_staging.cpp); the device trusts what passes them.
+// records: known types, quantisers 1..31, no bits beyond the six blocks, and the coded blocks of a record inside the n_blocks
+bool records_valid(const h263mi_mb_record *mbs, size_t n_mbs, size_t n_blocks);
+// block offsets that start at 0, never fall and end at n_events; at most 64 events per block, naming each position once (the
+// device places them in no particular order).  No blocks: nothing to check.
+bool events_valid(const uint32_t *first_event, size_t n_blocks, const uint32_t *events, size_t n_events);
+
 // one picture per stream from per-stream host arrays; coefficients dense (`coeffs`) or as events (`first_event`,
-// `events`, `n_events`) -- batch_staging.cpp
+// `events`, `n_events`) -- batch_staging.cpp.  validated: the arrays have passed the checks above already (a parser wrote
+// them, or h263mi_submit_picture checked them), so they are not checked again
 int batch_submit_host(h263mi_batch *b, uint8_t picture_type, const h263mi_mb_record *const *mbs, const uint32_t *n_mbs,
                       const int16_t *const *coeffs, const uint32_t *n_coeff_blocks, const uint32_t *const *first_event,
-                      const uint32_t *const *events, const uint32_t *n_events, bool from_parser = false, uint32_t pack_threads = 0,
+                      const uint32_t *const *events, const uint32_t *n_events, bool validated = false, uint32_t pack_threads = 0,
                       const uint8_t *types = nullptr, bool deferred_post = false, const uint32_t *const *group_index = nullptr,
                       const DirectWords *direct = nullptr);
 

@@ -18,70 +18,58 @@ using namespace h263mi;
 // =========================================================================================
 int h263mi_batch::ensure_record_staging(HostStaging &g2)
 {
-    const size_t total = (size_t)n * L.mbw * L.mbh;
-    PlacementScope near_device(placement);       // pinned memory on the NUMA node of this batch's GPU (worker_pool.h)
-    // each piece on its own, so that a failed allocation leaves nothing half-initialised for the next call
-    if (!g2.h_mbs) HIP_TRY(hipHostMalloc((void **)&g2.h_mbs, total * sizeof(MbRecord), hipHostMallocDefault));
-    if (!g2.d_mbs) HIP_TRY(hipMalloc((void **)&g2.d_mbs, total * sizeof(MbRecord)));
-    if (!g2.done) HIP_TRY(hipEventCreateWithFlags(&g2.done, hipEventDisableTiming));
+    RC_TRY(g2.mbs.reserve((size_t)n * L.mbw * L.mbh, 0, placement));
+    if (!g2.done) RC_TRY(make_event(g2.done));
     return H263MI_OK;
 }
 
 int h263mi_batch::ensure_host_staging(HostStaging &g2, size_t n_blocks, size_t n_event_words)
 {
-    PlacementScope near_device(placement);
     const size_t head = head_words();
-    if (head + n_event_words > g2.cap_words) {
-        if (g2.h_words) (void)hipHostFree(g2.h_words);
-        if (g2.d_words) (void)hipFree(g2.d_words);
-        g2.h_words = nullptr; g2.d_words = nullptr; g2.cap_words = 0;
-        const size_t cap = head + n_event_words + n_event_words / 2 + 256;
-        HIP_TRY(hipHostMalloc((void **)&g2.h_words, cap * sizeof(uint32_t), hipHostMallocDefault));
-        HIP_TRY(hipMalloc((void **)&g2.d_words, cap * sizeof(uint32_t)));
-        g2.cap_words = cap;
-    }
-    g2.h_base = reinterpret_cast<uint64_t *>(g2.h_words);  g2.d_base = reinterpret_cast<uint64_t *>(g2.d_words);
-    g2.h_index = g2.h_words + 4 * (size_t)n;               g2.d_index = g2.d_words + 4 * (size_t)n;
-    g2.h_events = g2.h_words + head;                       g2.d_events = g2.d_words + head;
+    RC_TRY(g2.words.reserve(head + n_event_words, n_event_words / 2 + 256, placement));
+    uint32_t *const h = g2.words.h, *const d = g2.words.d;
+    g2.h_base = reinterpret_cast<uint64_t *>(h);  g2.d_base = reinterpret_cast<uint64_t *>(d);
+    g2.h_index = h + 4 * (size_t)n;               g2.d_index = d + 4 * (size_t)n;
+    g2.h_events = h + head;                       g2.d_events = d + head;
     RC_TRY(ensure_record_staging(g2));
     // with sparse transport there are no dense blocks anywhere: the reconstruction waves read the events
-    if (!n_event_words && (n_blocks > g2.cap_blocks || !g2.h_coeffs)) {
-        if (g2.h_coeffs) (void)hipHostFree(g2.h_coeffs);
-        if (g2.d_coeffs) (void)hipFree(g2.d_coeffs);
-        g2.h_coeffs = nullptr; g2.d_coeffs = nullptr;
-        size_t cap = std::max(n_blocks, g2.cap_blocks);
-        cap = cap + cap / 2 + 64;
-        g2.cap_blocks = 0;
-        HIP_TRY(hipHostMalloc((void **)&g2.h_coeffs, cap * 128, hipHostMallocDefault));
-        if (hipMalloc((void **)&g2.d_coeffs, cap * 128) != hipSuccess) {
-            if (g2.h_coeffs) (void)hipHostFree(g2.h_coeffs);
-            g2.h_coeffs = nullptr;
-            return H263MI_ERR_OUT_OF_MEMORY;
-        }
-        g2.cap_blocks = cap;
-    }
+    if (!n_event_words) RC_TRY(g2.coeffs.reserve(n_blocks * 64, (n_blocks / 2 + 64) * 64, placement));
     return H263MI_OK;
-}
-
-void h263mi_batch::release_staging()
-{
-    for (HostStaging &g2 : host_stg) {
-        if (g2.h_mbs) (void)hipHostFree(g2.h_mbs);
-        if (g2.d_mbs) (void)hipFree(g2.d_mbs);
-        if (g2.h_coeffs) (void)hipHostFree(g2.h_coeffs);
-        if (g2.d_coeffs) (void)hipFree(g2.d_coeffs);
-        if (g2.h_words) (void)hipHostFree(g2.h_words);
-        if (g2.d_words) (void)hipFree(g2.d_words);
-        if (g2.done) (void)hipEventDestroy(g2.done);
-        g2 = HostStaging();
-    }
 }
 
 namespace h263mi {
 
+bool records_valid(const h263mi_mb_record *mbs, size_t n_mbs, size_t n_blocks)
+{
+    for (size_t k = 0; k < n_mbs; k++) {
+        const h263mi_mb_record &m = mbs[k];
+        if (m.mb_type > H263MI_MB_INTER4V_Q || m.quant < 1 || m.quant > 31 || (m.cbp & 0xC0) || (m.kill & 0xC0)) return false;
+        // (a record without coded blocks does not use its coeff_index)
+        if (m.cbp && (uint64_t)m.coeff_index + (uint64_t)__builtin_popcount(m.cbp) > n_blocks) return false;
+    }
+    return true;
+}
+
+bool events_valid(const uint32_t *first_event, size_t n_blocks, const uint32_t *events, size_t n_events)
+{
+    if (!n_blocks) return true;
+    if (first_event[0] != 0 || first_event[n_blocks] != n_events) return false;
+    for (size_t k = 0; k < n_blocks; k++) {
+        const uint32_t e0 = first_event[k], e1 = first_event[k + 1];
+        if (e0 > e1 || e1 > n_events || e1 - e0 > 64) return false;
+        uint64_t seen = 0;
+        for (uint32_t e = e0; e < e1; e++) {
+            const uint64_t bit = 1ull << (events[e] & 63u);
+            if (seen & bit) return false;
+            seen |= bit;
+        }
+    }
+    return true;
+}
+
 int batch_submit_host(h263mi_batch *b, uint8_t picture_type, const h263mi_mb_record *const *mbs, const uint32_t *n_mbs,
                       const int16_t *const *coeffs, const uint32_t *n_coeff_blocks, const uint32_t *const *first_event,
-                      const uint32_t *const *events, const uint32_t *n_events, bool from_parser, uint32_t pack_threads,
+                      const uint32_t *const *events, const uint32_t *n_events, bool validated, uint32_t pack_threads,
                       const uint8_t *types, bool deferred_post, const uint32_t *const *group_index, const DirectWords *direct)
 {
     // group_index (from the parser only): SPARSE RECORDS -- mbs[i] holds the n_mbs[i] records of stream i's coded macroblocks
@@ -93,9 +81,9 @@ int batch_submit_host(h263mi_batch *b, uint8_t picture_type, const h263mi_mb_rec
     // the waves read the records out of the pinned slot over the link, no copy at all: +-0.  In the steady state a call IS its
     // parse phase: 0.43-0.53 ms on 16 threads against 0.03 ms of packing and 0.01 ms of enqueueing
     // (profiles/r05_j_e2e_per_call_packed_records.txt, r05_m_*).  The packing went last: `direct`, below.)
-    const bool sparse_rec = group_index != nullptr && from_parser;
-    // from_parser: the arrays are what bits::parse_picture just wrote (h263mi_batch_decode_next_pictures) -- valid by
-    // construction, so the per-record checks a caller's arrays get are skipped; pack_threads: the caller's thread budget
+    // (sparse records and direct words come from the parser only: validated)
+    const bool sparse_rec = group_index != nullptr && validated;
+    // pack_threads: the caller's thread budget
     const bool sparse = first_event != nullptr;
     if (!b || !mbs || !n_mbs || !n_coeff_blocks || (!sparse && !coeffs) || (sparse && (!events || !n_events)) ||
         picture_type > H263MI_PICTURE_RESERVED)
@@ -106,12 +94,9 @@ int batch_submit_host(h263mi_batch *b, uint8_t picture_type, const h263mi_mb_rec
         if (n_mbs[i] > per || (n_mbs[i] && !mbs[i])) return H263MI_ERR_INVALID_ARGUMENT;
         if (n_coeff_blocks[i] && !direct) {
             if (!sparse && !coeffs[i]) return H263MI_ERR_INVALID_ARGUMENT;
-            if (sparse && (!first_event[i] || first_event[i][0] != 0 || first_event[i][n_coeff_blocks[i]] != n_events[i] ||
-                           (n_events[i] && !events[i])))
-                return H263MI_ERR_INVALID_ARGUMENT;
+            if (sparse && (!first_event[i] || (n_events[i] && !events[i]))) return H263MI_ERR_INVALID_ARGUMENT;
         }
-        // block offsets inside a stream's share of the pool are 32-bit byte offsets on the device (recon_block_limit)
-        if (n_coeff_blocks[i] > (1u << 25)) return H263MI_ERR_INVALID_ARGUMENT;
+        if (n_coeff_blocks[i] > kMaxStreamBlocks) return H263MI_ERR_INVALID_ARGUMENT;
         blocks += n_coeff_blocks[i];
         if (sparse) n_ev += n_events[i];
     }
@@ -119,10 +104,10 @@ int batch_submit_host(h263mi_batch *b, uint8_t picture_type, const h263mi_mb_rec
     DeviceGuard g(b->device);
     if (!g.ok) return H263MI_ERR_NO_DEVICE;
     h263mi_batch::HostStaging &g2 = b->host_stg[b->host_slot & 1];
-    if (direct && !(from_parser && sparse && group_index)) return H263MI_ERR_INVALID_ARGUMENT;
+    if (direct && !(validated && sparse && group_index)) return H263MI_ERR_INVALID_ARGUMENT;
     // (direct: the slot was sized before the parser wrote into it, batch_decode_next_pictures)
     const size_t event_words = direct ? (size_t)b->n * (direct->pitch_blocks + direct->pitch_events) : sparse ? blocks + 1 + n_ev : 0;
-    if (direct && (b->head_words() + event_words > g2.cap_words || event_words > kMaxEventWords)) return H263MI_ERR_INVALID_ARGUMENT;
+    if (direct && (b->head_words() + event_words > g2.words.cap || event_words > kMaxEventWords)) return H263MI_ERR_INVALID_ARGUMENT;
     if (!direct) RC_TRY(b->ensure_host_staging(g2, blocks ? blocks : 1, event_words));
     const auto t_wait0 = std::chrono::steady_clock::now();
     HIP_TRY(hipEventSynchronize(g2.done));       // the kernel that read this slot two pictures ago is done
@@ -148,48 +133,28 @@ int batch_submit_host(h263mi_batch *b, uint8_t picture_type, const h263mi_mb_rec
     }
     const size_t records_sent = sparse_rec ? rec_at : 0;         // records of the stream that has the most
     uint32_t *h_first = g2.h_events, *h_ev = sparse ? g2.h_events + blocks + 1 : nullptr;
-    std::atomic<bool> offsets_ok{true}, records_ok{true};
+    std::atomic<bool> arrays_ok{true};
     // packing is a host memcpy of every record byte: a few threads, or one core caps the rate below the PCIe link
     auto pack = [&](uint32_t first, uint32_t last, uint32_t step) {
         for (uint32_t i = first; i < last; i += step) {
             if (!b->ss[i].active) continue;      // sits the call out: its records are never read (STREAM_RECON_SKIP)
-            MbRecord *dst = g2.h_mbs + (size_t)i * per;
+            MbRecord *dst = g2.mbs.h + (size_t)i * per;
             if (sparse_rec) {
                 if (group_index[i]) memcpy(g2.h_index + (size_t)i * groups_pp, group_index[i], groups_pp * sizeof(uint32_t));
                 else memset(g2.h_index + (size_t)i * groups_pp, 0, groups_pp * sizeof(uint32_t));      // (no record at all)
             }
-            for (uint32_t k = 0; k < n_mbs[i] && !from_parser; k++) {   // the same checks as h263mi_submit_picture
-                const MbRecord &m = mbs[i][k];
-                // (a record without coded blocks does not use its coeff_index)
-                if (m.mb_type > H263MI_MB_INTER4V_Q || m.quant < 1 || m.quant > 31 || (m.cbp & 0xC0) || (m.kill & 0xC0) ||
-                    (m.cbp && (uint64_t)m.coeff_index + (uint64_t)__builtin_popcount(m.cbp) > n_coeff_blocks[i]))
-                    records_ok.store(false, std::memory_order_relaxed);
-            }
+            if (!validated && !(records_valid(mbs[i], n_mbs[i], n_coeff_blocks[i]) &&
+                                (!sparse || events_valid(first_event[i], n_coeff_blocks[i], events[i], n_events[i]))))
+                arrays_ok.store(false, std::memory_order_relaxed);
             // (h263mi_batch_decode_next_pictures has its parser write the records straight into this slot)
             if (n_mbs[i] && mbs[i] != dst) memcpy(dst, mbs[i], (size_t)n_mbs[i] * sizeof(MbRecord));
             for (size_t k = n_mbs[i]; k < per && !sparse_rec; k++) dst[k] = pad;      // (sparse records: no record = not coded)
             if (!n_coeff_blocks[i]) continue;
             if (!sparse) {
-                memcpy(g2.h_coeffs + g2.h_base[i] * 64, coeffs[i], (size_t)n_coeff_blocks[i] * 128);
+                memcpy(g2.coeffs.h + g2.h_base[i] * 64, coeffs[i], (size_t)n_coeff_blocks[i] * 128);
             } else {
                 uint32_t *fo = h_first + g2.h_base[i];
-                bool ascending = true;
-                for (uint32_t k = 0; k < n_coeff_blocks[i]; k++) {
-                    ascending = ascending && first_event[i][k] <= first_event[i][k + 1] && first_event[i][k + 1] <= n_events[i];
-                    fo[k] = first_event[i][k] + ev_base[i];
-                }
-                // a caller's events: at most 64 per block, every position once (the device places them in no particular order)
-                for (uint32_t k = 0; k < n_coeff_blocks[i] && ascending && !from_parser; k++) {
-                    uint64_t seen = 0;
-                    const uint32_t e0 = first_event[i][k], e1 = first_event[i][k + 1];
-                    if (e1 - e0 > 64) ascending = false;
-                    for (uint32_t e = e0; e < e1 && ascending; e++) {
-                        const uint64_t bit = 1ull << (events[i][e] & 63u);
-                        if (seen & bit) ascending = false;
-                        seen |= bit;
-                    }
-                }
-                if (!ascending) offsets_ok.store(false, std::memory_order_relaxed);
+                for (uint32_t k = 0; k < n_coeff_blocks[i]; k++) fo[k] = first_event[i][k] + ev_base[i];
                 if (n_events[i]) memcpy(h_ev + ev_base[i], events[i], (size_t)n_events[i] * sizeof(uint32_t));
             }
         }
@@ -205,7 +170,7 @@ int batch_submit_host(h263mi_batch *b, uint8_t picture_type, const h263mi_mb_rec
         // (thread t packs the streams t, t + T, ...: the ones it has just parsed, see StreamDeal)
         b->workers(n_thr).run(n_thr, [&](unsigned t) { pack(t, b->n, n_thr); }, b->pool_spin_us);
     }
-    if (!offsets_ok.load() || !records_ok.load()) return H263MI_ERR_INVALID_ARGUMENT;      // nothing has been queued yet
+    if (!arrays_ok.load()) return H263MI_ERR_INVALID_ARGUMENT;      // nothing has been queued yet
     const auto t_enq0 = std::chrono::steady_clock::now();
     RC_TRY(b->time_close());                     // the copies below are not part of any kernel's time
     // (A stream of their own for these copies -- beside the kernel of the call before -- was measured in round 5 and dropped:
@@ -217,7 +182,7 @@ int batch_submit_host(h263mi_batch *b, uint8_t picture_type, const h263mi_mb_rec
         if (sparse_rec) {
             // sparse records: the head of every stream's part in one 2-D copy (the index words travel with the small things below)
             if (records_sent)
-                HIP_TRY(hipMemcpy2DAsync(g2.d_mbs, per * sizeof(MbRecord), g2.h_mbs, per * sizeof(MbRecord), records_sent * sizeof(MbRecord),
+                HIP_TRY(hipMemcpy2DAsync(g2.mbs.d, per * sizeof(MbRecord), g2.mbs.h, per * sizeof(MbRecord), records_sent * sizeof(MbRecord),
                                          b->n, hipMemcpyHostToDevice, cs));
         }
         // the records of the streams that take part, one copy per run of neighbouring streams (all of them: one copy)
@@ -225,14 +190,14 @@ int batch_submit_host(h263mi_batch *b, uint8_t picture_type, const h263mi_mb_rec
             if (!b->ss[i].active) { i++; continue; }
             uint32_t j = i + 1;
             while (j < b->n && b->ss[j].active) j++;
-            HIP_TRY(hipMemcpyAsync(g2.d_mbs + (size_t)i * per, g2.h_mbs + (size_t)i * per, (size_t)(j - i) * per * sizeof(MbRecord),
+            HIP_TRY(hipMemcpyAsync(g2.mbs.d + (size_t)i * per, g2.mbs.h + (size_t)i * per, (size_t)(j - i) * per * sizeof(MbRecord),
                                    hipMemcpyHostToDevice, cs));
             i = j;
         }
         if (direct) {
             // the bases and the record index in one copy, the used heads of the streams' block offsets and events in a 2-D
             // copy each
-            HIP_TRY(hipMemcpyAsync(g2.d_words, g2.h_words, b->head_words() * sizeof(uint32_t), hipMemcpyHostToDevice, cs));
+            HIP_TRY(hipMemcpyAsync(g2.words.d, g2.words.h, b->head_words() * sizeof(uint32_t), hipMemcpyHostToDevice, cs));
             if (blocks) {
                 uint32_t *const h_ev0 = g2.h_events + (size_t)b->n * direct->pitch_blocks;
                 uint32_t *const d_ev0 = g2.d_events + (size_t)b->n * direct->pitch_blocks;
@@ -246,10 +211,10 @@ int batch_submit_host(h263mi_batch *b, uint8_t picture_type, const h263mi_mb_rec
         }
         // the bases, the record index and the events: one copy (HostStaging::h_words)
         if (sparse && blocks) h_first[blocks] = (uint32_t)n_ev;
-        HIP_TRY(hipMemcpyAsync(g2.d_words, g2.h_words, (b->head_words() + (sparse && blocks ? event_words : 0)) * sizeof(uint32_t),
+        HIP_TRY(hipMemcpyAsync(g2.words.d, g2.words.h, (b->head_words() + (sparse && blocks ? event_words : 0)) * sizeof(uint32_t),
                                hipMemcpyHostToDevice, cs));
         if (!sparse && blocks) {
-            HIP_TRY(hipMemcpyAsync(g2.d_coeffs, g2.h_coeffs, blocks * 128, hipMemcpyHostToDevice, cs));
+            HIP_TRY(hipMemcpyAsync(g2.coeffs.d, g2.coeffs.h, blocks * 128, hipMemcpyHostToDevice, cs));
         }
         return H263MI_OK;
     };
@@ -264,7 +229,7 @@ int batch_submit_host(h263mi_batch *b, uint8_t picture_type, const h263mi_mb_rec
     }
     // where the launch finds it all (the waves bounds-check what they read: the sizes are known here)
     h263mi_coeff_source src;
-    src.coeffs = g2.d_coeffs;
+    src.coeffs = g2.coeffs.d;
     src.coeff_base = g2.d_base;
     if (sparse && blocks) {
         // the reconstruction waves read the events themselves (recon_kernel.inl: coeff_row_from_events); round 2 had a
@@ -281,7 +246,7 @@ int batch_submit_host(h263mi_batch *b, uint8_t picture_type, const h263mi_mb_rec
     }
     {
         const auto t_sub0 = std::chrono::steady_clock::now();
-        const int src_rc = b->submit(picture_type, g2.d_mbs, src, /*with_post=*/deferred_post && b->pending.valid, types);
+        const int src_rc = b->submit(picture_type, g2.mbs.d, src, /*with_post=*/deferred_post && b->pending.valid, types);
         if (b->trace_host) b->host_ms[5] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_sub0).count();
         if (src_rc != H263MI_OK) {
             (void)hipStreamSynchronize(cs);      // (no copy left behind that reads this slot)
@@ -382,7 +347,7 @@ static int batch_decode_next_pictures(h263mi_batch *b, uint32_t decoder_options,
             pic.want_dense = false;                              // the coefficients travel as events
             pic.size_fits = &picture_size_fits;
             pic.sparse_records = sparse_rec;                     // records for the coded macroblocks only (round 5)
-            pic.mbs_ext = g2.h_mbs + (size_t)i * per;
+            pic.mbs_ext = g2.mbs.h + (size_t)i * per;
             pic.mbs_ext_cap = per;
             pic.events_ext = direct ? g2.h_events + (size_t)n * dw.pitch_blocks + (size_t)i * dw.pitch_events : nullptr;
             pic.events_ext_cap = direct ? dw.pitch_events : 0;
@@ -434,7 +399,7 @@ static int batch_decode_next_pictures(h263mi_batch *b, uint32_t decoder_options,
     static const uint32_t kNoEvents[1] = {0};
     for (uint32_t i = 0; i < n; i++) {
         const bits::ParsedPicture &pic = b->parsed[i];
-        mbs[i] = g2.h_mbs + (size_t)i * per;
+        mbs[i] = g2.mbs.h + (size_t)i * per;
         first[i] = kNoEvents;
         events[i] = nullptr;
         if (!takes_part[i]) continue;
@@ -456,7 +421,7 @@ static int batch_decode_next_pictures(h263mi_batch *b, uint32_t decoder_options,
         for (uint32_t i = 0; i < n; i++) st.per_stream[i] = takes_part[i] ? strength_from_header(b->parsed[i].desc) : (uint8_t)0;
     const bool deferred = b->pipeline_post && (d_rgba || d_deblocked);
     int rc = batch_submit_host(b, H263MI_PICTURE_P, mbs.data(), n_mbs.data(), nullptr, n_blocks.data(), first.data(), events.data(),
-                               n_events.data(), /*from_parser=*/true, n_thr, types.data(), deferred, sparse_rec ? gidx.data() : nullptr,
+                               n_events.data(), /*validated=*/true, n_thr, types.data(), deferred, sparse_rec ? gidx.data() : nullptr,
                                direct ? &dw : nullptr);
     int render_rc = H263MI_OK;
     if (rc == H263MI_OK) {
@@ -539,7 +504,7 @@ int h263mi_batch_host_placement(const h263mi_batch *b, int *device_numa_node, in
     if (device_numa_node) *device_numa_node = b->placement.node;
     if (staging_numa_node) {
         const h263mi_batch::HostStaging &g2 = b->host_stg[0];
-        *staging_numa_node = g2.h_mbs ? numa_node_of_address(g2.h_mbs) : -1;
+        *staging_numa_node = g2.mbs.h ? numa_node_of_address(g2.mbs.h) : -1;
     }
     uint32_t k = 0;
     if (b->pool) {

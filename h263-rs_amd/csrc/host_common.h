@@ -75,6 +75,9 @@ inline uint32_t post_tiles_y(const FrameLayout &L) { return (post_strips_y(L.hei
 // Event indices are 32-bit on the device, 0xffffffff stands for "the caller did not say how many" (ReconArgs::n_events), and a
 // lane looks up to 64 words past its first event before it compares with the block's end: the count stays clear of the top.
 constexpr uint64_t kMaxEventWords = 0xffffff00ull;
+// Block offsets inside a stream's share of the pool are 32-bit byte offsets on the device (recon_block_limit): the blocks of one
+// stream in one call.
+constexpr uint64_t kMaxStreamBlocks = 1ull << 25;
 // what the parser asks right behind a picture header (bits::ParsedPicture::size_fits): can the frame store hold such a picture?
 inline bool picture_size_fits(uint32_t w, uint32_t h) { return layout_fits(w, h); }
 // tile geometry of k_post for the layout in a.L (post_kernel.inl: post_tile_columns)

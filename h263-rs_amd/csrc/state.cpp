@@ -17,83 +17,21 @@ struct h263mi_state {
     bool has_last = false;
     bits::ParserContext parser_ctx;   // header + format of the last picture decoded from a bitstream (state.rs:143-167)
     bits::ParsedPicture parsed;       // parse results of h263mi_decode_next_picture: kept, so that its buffers are reused
-    // staging: two slots (pinned host + device) used alternately, so that filling slot i+1 on the host
-    // overlaps the H2D copy and the kernel of slot i
-    struct Staging {
-        MbRecord *h_mbs = nullptr;  int16_t *h_coeffs = nullptr;     // pinned
-        MbRecord *d_mbs = nullptr;  int16_t *d_coeffs = nullptr;
-        uint32_t *h_events = nullptr, *d_events = nullptr;           // sparse transport: block offsets, then events
-        size_t cap_mbs = 0, cap_blocks = 0, cap_events = 0;
-        hipEvent_t done = nullptr;  // recorded after the kernel that reads the slot
-    } stg[2];
-    unsigned next_slot = 0;
-    uint8_t *d_rgba = nullptr;  size_t cap_rgba = 0;
-
-    void free_staging()
-    {
-        for (Staging &g : stg) {
-            if (g.h_mbs) (void)hipHostFree(g.h_mbs);
-            if (g.h_coeffs) (void)hipHostFree(g.h_coeffs);
-            if (g.d_mbs) (void)hipFree(g.d_mbs);
-            if (g.d_coeffs) (void)hipFree(g.d_coeffs);
-            if (g.h_events) (void)hipHostFree(g.h_events);
-            if (g.d_events) (void)hipFree(g.d_events);
-            if (g.done) (void)hipEventDestroy(g.done);
-            g = Staging();
-        }
-        if (d_rgba) (void)hipFree(d_rgba);
-        d_rgba = nullptr;
-        cap_rgba = 0;
-    }
+    uint8_t *d_rgba = nullptr;  size_t cap_rgba = 0;   // rendering scratch of h263mi_render_rgba[_layout]
     ~h263mi_state()
     {
         DeviceGuard g(cfg.device_id);
         if (b) (void)hipStreamSynchronize(b->stream);
-        free_staging();
+        if (d_rgba) (void)hipFree(d_rgba);
         delete b;
     }
 };
 
-// n_event_words > 0: sparse transport -- no dense blocks anywhere, the reconstruction waves read the events
-static int state_ensure_staging(h263mi_state::Staging &g, size_t n_mbs, size_t n_blocks, size_t n_event_words, const HostPlacement &where)
-{
-    PlacementScope near_device(where);           // pinned memory on the NUMA node of the state's GPU (worker_pool.h)
-    if (n_mbs > g.cap_mbs) {
-        if (g.h_mbs) (void)hipHostFree(g.h_mbs);
-        if (g.d_mbs) (void)hipFree(g.d_mbs);
-        g.h_mbs = nullptr; g.d_mbs = nullptr; g.cap_mbs = 0;
-        HIP_TRY(hipHostMalloc((void **)&g.h_mbs, n_mbs * sizeof(MbRecord), hipHostMallocDefault));
-        HIP_TRY(hipMalloc((void **)&g.d_mbs, n_mbs * sizeof(MbRecord)));
-        g.cap_mbs = n_mbs;
-    }
-    if (!n_event_words && (n_blocks > g.cap_blocks || !g.h_coeffs)) {
-        if (g.h_coeffs) (void)hipHostFree(g.h_coeffs);
-        if (g.d_coeffs) (void)hipFree(g.d_coeffs);
-        g.h_coeffs = nullptr; g.d_coeffs = nullptr; g.cap_blocks = 0;
-        size_t cap = std::max(n_blocks, g.cap_blocks);
-        cap = cap + cap / 2 + 64;
-        if (!n_event_words) HIP_TRY(hipHostMalloc((void **)&g.h_coeffs, cap * 128, hipHostMallocDefault));
-        HIP_TRY(hipMalloc((void **)&g.d_coeffs, cap * 128));
-        g.cap_blocks = cap;
-    }
-    if (n_event_words > g.cap_events) {
-        if (g.h_events) (void)hipHostFree(g.h_events);
-        if (g.d_events) (void)hipFree(g.d_events);
-        g.h_events = nullptr; g.d_events = nullptr; g.cap_events = 0;
-        const size_t cap = n_event_words + n_event_words / 2 + 256;
-        HIP_TRY(hipHostMalloc((void **)&g.h_events, cap * sizeof(uint32_t), hipHostMallocDefault));
-        HIP_TRY(hipMalloc((void **)&g.d_events, cap * sizeof(uint32_t)));
-        g.cap_events = cap;
-    }
-    if (!g.done) HIP_TRY(hipEventCreateWithFlags(&g.done, hipEventDisableTiming));
-    return H263MI_OK;
-}
-
 // state.rs:421-483 from host records; the coefficients come either as dense blocks (`coeffs`) or as events
-// (`first_event` + `events`, expanded on the device)
+// (`first_event` + `events`, expanded on the device).  Staged and launched by the batch's host path (batch_submit_host).
 static int submit_records(h263mi_state *s, const h263mi_picture_desc *desc, const h263mi_mb_record *mbs, size_t n_mbs,
                           const int16_t *coeffs, size_t n_coeff_blocks, const uint32_t *first_event, const uint32_t *events,
-                          size_t n_events, bool from_parser = false);
+                          size_t n_events, bool validated = false);
 
 extern "C" {
 
@@ -139,28 +77,16 @@ int h263mi_state_cleanup_buffers(h263mi_state *s)
 
 static int submit_records(h263mi_state *s, const h263mi_picture_desc *desc, const h263mi_mb_record *mbs, size_t n_mbs,
                           const int16_t *coeffs, size_t n_coeff_blocks, const uint32_t *first_event, const uint32_t *events,
-                          size_t n_events, bool from_parser)
+                          size_t n_events, bool validated)
 {
-    // from_parser: the arrays are what bits::parse_picture just wrote -- valid by construction (quantisers, types, block
-    // indices, one event per position), so the per-record and per-event checks a caller's arrays get are skipped
+    // validated: the arrays are what bits::parse_picture just wrote -- valid by construction (quantisers, types, block
+    // indices, one event per position), so the checks a caller's arrays get are skipped
     const bool sparse = first_event != nullptr;
     if (!s || !desc || (!mbs && n_mbs) || (!sparse && !coeffs && n_coeff_blocks) || (sparse && !events && n_events))
         return H263MI_ERR_INVALID_ARGUMENT;
-    if (sparse && n_coeff_blocks && !from_parser) {
-        // offsets must be monotone and end at n_events: checked here, the kernel trusts them
-        if (first_event[0] != 0 || first_event[n_coeff_blocks] != n_events) return H263MI_ERR_INVALID_ARGUMENT;
-        // ... and a block's events name every position at most once (the device places them in no particular order)
-        for (size_t i = 0; i < n_coeff_blocks; i++) {
-            if (first_event[i] > first_event[i + 1] || first_event[i + 1] > n_events || first_event[i + 1] - first_event[i] > 64)
-                return H263MI_ERR_INVALID_ARGUMENT;
-            uint64_t seen = 0;
-            for (uint32_t e = first_event[i]; e < first_event[i + 1]; e++) {
-                const uint64_t bit = 1ull << (events[e] & 63u);
-                if (seen & bit) return H263MI_ERR_INVALID_ARGUMENT;
-                seen |= bit;
-            }
-        }
-    }
+    // what the batch's host path takes of one stream
+    if (n_coeff_blocks > kMaxStreamBlocks || n_events > kMaxEventWords) return H263MI_ERR_INVALID_ARGUMENT;
+    if (sparse && !validated && !events_valid(first_event, n_coeff_blocks, events, n_events)) return H263MI_ERR_INVALID_ARGUMENT;
     if (!desc->width || !desc->height || !layout_fits(desc->width, desc->height)) return H263MI_ERR_PICTURE_FORMAT_INVALID;
     if (desc->picture_type > H263MI_PICTURE_RESERVED) return H263MI_ERR_INVALID_ARGUMENT;
     const FrameLayout L = make_layout(desc->width, desc->height);
@@ -168,19 +94,9 @@ static int submit_records(h263mi_state *s, const h263mi_picture_desc *desc, cons
     if (n_mbs > total) return H263MI_ERR_INVALID_ARGUMENT;
 
     // ---- everything that can fail is checked before any state changes (state.rs:142, 464-487)
+    if (!validated && !records_valid(mbs, n_mbs, n_coeff_blocks)) return H263MI_ERR_INVALID_ARGUMENT;
     bool any_inter = n_mbs < total;   // missing macroblocks are padded as Inter (state.rs:421-427)
-    for (size_t i = 0; i < n_mbs; i++) {
-        const h263mi_mb_record &m = mbs[i];
-        if (mb_is_inter(m.mb_type)) any_inter = true;
-        if (from_parser) {
-            if (any_inter) break;                // (nothing else to learn from a parser's records)
-            continue;
-        }
-        if (m.mb_type > H263MI_MB_INTER4V_Q || m.quant < 1 || m.quant > 31 || (m.cbp & 0xC0) || (m.kill & 0xC0))
-            return H263MI_ERR_INVALID_ARGUMENT;
-        // (a record without coded blocks does not use its coeff_index)
-        if (m.cbp && (size_t)m.coeff_index + (size_t)__builtin_popcount(m.cbp) > n_coeff_blocks) return H263MI_ERR_INVALID_ARGUMENT;
-    }
+    for (size_t i = 0; i < n_mbs && !any_inter; i++) any_inter = mb_is_inter(mbs[i].mb_type);
     const bool same_size = s->b && s->b->L.width == L.width && s->b->L.height == L.height;
     const bool has_ref = s->b && s->b->ss[0].has_ref && s->b->ss[0].cur >= 0;
     if (any_inter && !has_ref) return H263MI_ERR_UNCODED_IFRAME_BLOCKS;              // gather.rs:149
@@ -199,46 +115,15 @@ static int submit_records(h263mi_state *s, const h263mi_picture_desc *desc, cons
         RC_TRY(batch_create(1, L.width, L.height, &s->cfg, &nb));
         fresh.reset(nb);
     }
-    h263mi_batch *b = same_size ? s->b : fresh.get();
-    h263mi_state::Staging &g2 = s->stg[s->next_slot & 1];
-    const size_t event_words = sparse ? n_coeff_blocks + 1 + n_events : 0;
-    RC_TRY(state_ensure_staging(g2, total, n_coeff_blocks ? n_coeff_blocks : 1, event_words, b->placement));
-    HIP_TRY(hipEventSynchronize(g2.done));       // the kernel that read this slot two pictures ago is done
-
-    // (h263mi_decode_next_picture has its parser write the records straight into this slot)
-    if (n_mbs && mbs != g2.h_mbs) memcpy(g2.h_mbs, mbs, n_mbs * sizeof(MbRecord));
-    for (size_t i = n_mbs; i < total; i++) {     // state.rs:421-427: Inter, mv (0,0), nothing coded
-        MbRecord pad;
-        memset(&pad, 0, sizeof pad);
-        pad.mb_type = H263MI_MB_INTER;
-        pad.quant = 1;
-        g2.h_mbs[i] = pad;
-    }
-    HIP_TRY(hipMemcpyAsync(g2.d_mbs, g2.h_mbs, total * sizeof(MbRecord), hipMemcpyHostToDevice, b->stream));
-    h263mi_coeff_source src;
-    if (sparse && n_coeff_blocks) {
-        memcpy(g2.h_events, first_event, (n_coeff_blocks + 1) * sizeof(uint32_t));
-        if (n_events) memcpy(g2.h_events + n_coeff_blocks + 1, events, n_events * sizeof(uint32_t));
-        HIP_TRY(hipMemcpyAsync(g2.d_events, g2.h_events, event_words * sizeof(uint32_t), hipMemcpyHostToDevice, b->stream));
-        src.first_event = g2.d_events;           // (read by the reconstruction waves themselves)
-        src.events = g2.d_events + n_coeff_blocks + 1;
-        src.n_events = (uint32_t)n_events;
-    } else if (n_coeff_blocks) {
-        memcpy(g2.h_coeffs, coeffs, n_coeff_blocks * 128);
-        HIP_TRY(hipMemcpyAsync(g2.d_coeffs, g2.h_coeffs, n_coeff_blocks * 128, hipMemcpyHostToDevice, b->stream));
-    }
-
-    src.coeffs = g2.d_coeffs;
-    src.pool_blocks = n_coeff_blocks;
-    src.checked = true;
-    RC_TRY(b->submit(desc->picture_type, g2.d_mbs, src));
+    // (the counts fit: n_mbs <= total, and the caps above)
+    const uint32_t n_mbs32 = (uint32_t)n_mbs, blocks32 = (uint32_t)n_coeff_blocks, events32 = (uint32_t)n_events;
+    RC_TRY(batch_submit_host(same_size ? s->b : fresh.get(), desc->picture_type, &mbs, &n_mbs32, &coeffs, &blocks32,
+                             sparse ? &first_event : nullptr, &events, &events32, /*validated=*/true));
     // ---- the launch is queued: from here on nothing fails any more, the state changes (state.rs:464-483)
     if (fresh) {
         delete s->b;
         s->b = fresh.release();
     }
-    if (hipEventRecord(g2.done, b->stream) != hipSuccess) (void)hipStreamSynchronize(b->stream);   // (the slot is reused two pictures on)
-    s->next_slot++;
     s->last_desc = *desc;
     s->has_last = true;
     return H263MI_OK;
@@ -272,15 +157,14 @@ int h263mi_decode_next_picture(h263mi_state *s, const uint8_t *data, size_t len,
     pic.mbs_ext = nullptr;
     pic.mbs_ext_cap = 0;
     if (s->b) {
-        // A stream rarely changes its size: the records are parsed straight into the pinned staging slot the next submit
+        // A stream rarely changes its size: the records are parsed straight into the batch's staging slot the next submit
         // copies from (sized for the last picture; a picture with more macroblocks falls back to the parser's own array).
         // The slot was last read by the copy of two pictures ago.
         DeviceGuard g(s->cfg.device_id);
-        h263mi_state::Staging &g2 = s->stg[s->next_slot & 1];
-        const size_t total = (size_t)s->b->L.mbw * s->b->L.mbh;
-        if (g.ok && state_ensure_staging(g2, total, 1, 1, s->b->placement) == H263MI_OK && hipEventSynchronize(g2.done) == hipSuccess) {
-            pic.mbs_ext = g2.h_mbs;
-            pic.mbs_ext_cap = total;
+        h263mi_batch::HostStaging &g2 = s->b->host_stg[s->b->host_slot & 1];
+        if (g.ok && s->b->ensure_record_staging(g2) == H263MI_OK && hipEventSynchronize(g2.done) == hipSuccess) {
+            pic.mbs_ext = g2.mbs.h;
+            pic.mbs_ext_cap = (size_t)s->b->L.mbw * s->b->L.mbh;
         }
     }
     RC_TRY(bits::parse_picture(data, len, s->options, &s->parser_ctx, pic));
@@ -288,7 +172,7 @@ int h263mi_decode_next_picture(h263mi_state *s, const uint8_t *data, size_t len,
     // far, so every error above leaves it unchanged, like the reader transaction of state.rs:142.
     if (pic.n_coded_blocks > 0xffffffffu / 8u) return H263MI_ERR_INVALID_ARGUMENT;
     RC_TRY(submit_records(s, &pic.desc, pic.records(), pic.n_records(), nullptr, pic.n_coded_blocks, pic.block_first_event.data(),
-                          pic.events.data(), pic.events.size(), /*from_parser=*/true));
+                          pic.events.data(), pic.events.size(), /*validated=*/true));
     s->parser_ctx = pic.next;
     if (consumed) *consumed = pic.bits_consumed / 8;     // reader.commit() drains whole bytes (reader.rs:391-394)
     return H263MI_OK;

@@ -85,7 +85,9 @@ def test_a_deliberately_broken_ordering_is_caught(drivers, corpus):
 def test_host_pipeline_is_clean_under_address_sanitizer(drivers, corpus, mode):
     """the same driver and scenarios under AddressSanitizer + UBSan: parse-into-staging at per-stream pitches, sparse records,
     the 2-D copies out of the slot, mixed-set slot moves -- over malloc'd "device" and "pinned" memory, where one byte beyond an
-    allocation is a report (the GPU tests run this code without a sanitizer; the parser alone has its own ASan fuzzer)"""
+    allocation is a report (the GPU tests run this code without a sanitizer; the parser alone has its own ASan fuzzer).  The
+    driver also sweeps an injected failure over every HIP call of the state's entries and of a batch's host path, with nothing
+    left allocated afterwards, and checks the error precedence of h263mi_submit_picture[_events] case by case"""
     e = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", H263MI_NUMA="0", H263MI_CGROUP_CPU_MAX=corpus[1])
     if mode == "packed":
         e["H263MI_DIRECT_WORDS"] = "0"

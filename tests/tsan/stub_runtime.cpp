@@ -12,7 +12,8 @@
 
 namespace {
 std::mutex g_m;
-std::map<uintptr_t, size_t> g_allocs;            // "device" allocations: base -> size (hipMemGetAddressRange)
+std::map<uintptr_t, size_t> g_allocs;            // "device" and pinned allocations: base -> size (hipMemGetAddressRange)
+std::atomic<long> g_events{0};                   // events created and not destroyed
 thread_local int tl_device = 0;
 std::atomic<uint64_t> g_sink{0};                 // what the stub kernels "compute": keeps their reads alive
 
@@ -75,12 +76,19 @@ hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned) { *s = nullptr; re
 hipError_t hipStreamDestroy(hipStream_t) { return hipSuccess; }
 hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
 hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }
-hipError_t hipEventCreate(hipEvent_t *e) { *e = (hipEvent_t)malloc(1); return hipSuccess; }
+hipError_t hipEventCreate(hipEvent_t *e) { *e = (hipEvent_t)malloc(1); g_events++; return hipSuccess; }
 hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) { return hipEventCreate(e); }
-hipError_t hipEventDestroy(hipEvent_t e) { free(e); return hipSuccess; }
+hipError_t hipEventDestroy(hipEvent_t e) { if (e) g_events--; free(e); return hipSuccess; }
 hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return hipSuccess; }
 hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
 hipError_t hipEventElapsedTime(float *ms, hipEvent_t, hipEvent_t) { *ms = 0.01f; return hipSuccess; }
+
+// what the library holds of the runtime right now: device and pinned blocks, events (tsan_driver: nothing may leak)
+long stub_live_allocations()
+{
+    std::lock_guard<std::mutex> l(g_m);
+    return (long)g_allocs.size() + g_events.load();
+}
 
 // ---- the "kernels": they read what a launch would read first -- the per-stream words, bases and the sparse-record index the
 // host threads have just written and the caller has just copied -- so that ThreadSanitizer sees those reads

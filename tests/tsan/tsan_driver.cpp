@@ -15,6 +15,10 @@
 //   * two batches, a mixed-size set and one H263State driven from four threads at the same time (distinct objects may be);
 //   * the packed (H263MI_DIRECT_WORDS=0) transport, and workers that never park (H263MI_SPIN_US = 50 ms, no quota, at most 6
 //     threads: every hand-over goes through the generation word alone, never through the mutex): further runs of the test.
+//   * a failure injected at every HIP call of h263mi_submit_picture[_events], h263mi_decode_next_picture and a 2-stream
+//     h263mi_batch_submit_host: the last picture stays as it was, and every pinned block, device block and event the objects
+//     held is given back (the stub runtime counts them);
+//   * the order in which h263mi_submit_picture[_events] names what is wrong with a call, one crafted case per rule.
 // Exit code 0 and no ThreadSanitizer report = pass.  The same driver built with -DH263MI_TSAN_BREAK_GENERATION_ORDER (the task is
 // published with a relaxed store: worker_pool.cpp) MUST make ThreadSanitizer report a race: tests/test_tsan.py checks both.
 // usage: tsan_driver <corpus.bin> [rounds [max threads]]      corpus: u32 streams, u32 frames, then per (stream, frame): u32 length, bytes
@@ -23,6 +27,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <initializer_list>
 #include <memory>
 #include <random>
@@ -30,6 +35,8 @@
 #include <vector>
 
 #include "../../include/h263mi.h"
+
+long stub_live_allocations();                                        // stub_runtime.cpp
 
 static std::vector<std::vector<std::vector<uint8_t>>> g_corpus;      // [stream][frame]
 static uint16_t g_w, g_h;
@@ -351,6 +358,271 @@ static void drive_host_garbage(unsigned seed, int tries)
     h263mi_state_free(st);
 }
 
+// a synthetic picture in both host forms: dense blocks and events (level << 16 | position)
+struct HostPicture {
+    h263mi_picture_desc desc{};
+    std::vector<h263mi_mb_record> mbs;
+    std::vector<int16_t> co;
+    std::vector<uint32_t> first, ev;
+    size_t blocks = 0;
+};
+static HostPicture host_picture(int kind, uint16_t w, uint16_t h, uint32_t seed, uint16_t temporal_reference)
+{
+    HostPicture p;
+    const size_t per = (size_t)((w + 15) / 16) * ((h + 15) / 16);
+    p.mbs.resize(per);
+    p.co.resize(per * 6 * 64);
+    CHECK(h263mi_synth_picture_host(kind, w, h, seed, 0, p.mbs.data(), p.co.data(), per * 6, &p.blocks) == H263MI_OK);
+    p.first.push_back(0);
+    for (size_t k = 0; k < p.blocks; k++) {
+        for (uint32_t pos = 0; pos < 64; pos++)
+            if (p.co[k * 64 + pos]) p.ev.push_back((uint32_t)(uint16_t)p.co[k * 64 + pos] << 16 | pos);
+        p.first.push_back((uint32_t)p.ev.size());
+    }
+    p.desc.width = w;
+    p.desc.height = h;
+    p.desc.picture_type = kind == H263MI_SYNTH_P ? H263MI_PICTURE_P : H263MI_PICTURE_I;
+    p.desc.pquant = 8;
+    p.desc.temporal_reference = temporal_reference;
+    return p;
+}
+static int submit_dense(h263mi_state *st, const HostPicture &p)
+{
+    return h263mi_submit_picture(st, &p.desc, p.mbs.data(), p.mbs.size(), p.co.data(), p.blocks);
+}
+static int submit_events(h263mi_state *st, const HostPicture &p)
+{
+    return h263mi_submit_picture_events(st, &p.desc, p.mbs.data(), p.mbs.size(), p.first.data(), p.blocks, p.ev.data(), p.ev.size());
+}
+// what a refused call must leave as it was: the last picture's size, planes and temporal reference
+static std::vector<uint64_t> last_picture(const h263mi_state *st)
+{
+    h263mi_frame_view v{};
+    const int rc = h263mi_get_last_picture(st, &v);
+    return {(uint64_t)(int64_t)rc, v.width, v.height, (uint64_t)(uintptr_t)v.dev_y, v.temporal_reference};
+}
+
+// h263mi_debug_fail_nth_hip_call at every HIP call of one call, each time on objects made afresh: the call reports the failure and
+// changes nothing that can be seen, and the same call then goes through (nothing was left half-made).  may_absorb: a failure the
+// call may get over by itself (h263mi_decode_next_picture parses into the staging slot only when that slot is to be had).
+struct SweepSubject {
+    virtual ~SweepSubject() {}
+    virtual int call() = 0;
+    virtual std::vector<uint64_t> view() = 0;
+};
+static void fault_sweep(const char *name, bool may_absorb, const std::function<SweepSubject *()> &make)
+{
+    int failures = 0;
+    for (int nth = 1; nth < 500; nth++) {
+        std::unique_ptr<SweepSubject> s(make());
+        const std::vector<uint64_t> before = s->view();
+        h263mi_debug_fail_nth_hip_call(nth);
+        const int rc = s->call();
+        const bool fired = h263mi_debug_fail_nth_hip_call(0) <= 0;
+        if (rc == H263MI_OK && !fired) {
+            fprintf(stderr, "  fault sweep %s: %d failures\n", name, failures);
+            CHECK(failures >= 3);
+            return;
+        }
+        if (rc == H263MI_OK) {
+            CHECK(may_absorb);
+            continue;
+        }
+        failures++;
+        CHECK(fired && rc == H263MI_ERR_OUT_OF_MEMORY);
+        CHECK(s->view() == before);
+        CHECK(s->call() == H263MI_OK);
+    }
+    CHECK(!"the call never went through");
+}
+
+static void drive_fault_sweeps()
+{
+    const long live0 = stub_live_allocations();
+    static HostPicture key, key2, p, p_short;
+    key = host_picture(H263MI_SYNTH_I_MIXED, g_w, g_h, 1, 7);
+    key2 = host_picture(H263MI_SYNTH_I_MIXED, 128, 96, 2, 9);
+    p = host_picture(H263MI_SYNTH_P, g_w, g_h, 3, 8);
+    p_short = p;
+    p_short.mbs.pop_back();                           // (the last macroblock is padded as Inter)
+    struct State : SweepSubject {
+        h263mi_state *st = nullptr;
+        std::function<int(h263mi_state *)> fn;
+        State(std::function<int(h263mi_state *)> f, bool from_bitstream) : fn(f)
+        {
+            CHECK(h263mi_state_new(H263MI_SORENSON_SPARK_BITSTREAM, nullptr, &st) == H263MI_OK);
+            if (from_bitstream) CHECK(h263mi_decode_next_picture(st, g_corpus[0][0].data(), g_corpus[0][0].size(), nullptr) == H263MI_OK);
+            else CHECK(submit_dense(st, key) == H263MI_OK);
+        }
+        ~State() { h263mi_state_free(st); }
+        int call() override { return fn(st); }
+        std::vector<uint64_t> view() override { return last_picture(st); }
+    };
+    fault_sweep("h263mi_submit_picture", false, [] { return new State([](h263mi_state *st) { return submit_dense(st, p); }, false); });
+    fault_sweep("h263mi_submit_picture (size change)", false,
+                [] { return new State([](h263mi_state *st) { return submit_dense(st, key2); }, false); });
+    fault_sweep("h263mi_submit_picture_events", false,
+                [] { return new State([](h263mi_state *st) { return submit_events(st, p_short); }, false); });
+    fault_sweep("h263mi_decode_next_picture", true, [] {
+        return new State([](h263mi_state *st) {
+            const std::vector<uint8_t> &pic = g_corpus[0][1];
+            return h263mi_decode_next_picture(st, pic.data(), pic.size(), nullptr);
+        }, true);
+    });
+    struct Batch : SweepSubject {
+        h263mi_batch *b = nullptr;
+        Batch()
+        {
+            h263mi_backend_cfg cfg{0, 0, nullptr};
+            CHECK(h263mi_batch_create(2, g_w, g_h, &cfg, &b) == H263MI_OK);
+            const h263mi_mb_record *m[2] = {key.mbs.data(), key.mbs.data()};
+            const int16_t *c[2] = {key.co.data(), key.co.data()};
+            const uint32_t n[2] = {(uint32_t)key.mbs.size(), (uint32_t)key.mbs.size()}, nb[2] = {(uint32_t)key.blocks, (uint32_t)key.blocks};
+            CHECK(h263mi_batch_submit_host(b, H263MI_PICTURE_I, m, n, c, nb) == H263MI_OK);
+            CHECK(h263mi_batch_sync(b) == H263MI_OK);
+        }
+        ~Batch() { h263mi_batch_destroy(b); }
+        int call() override
+        {
+            const h263mi_mb_record *m[2] = {p.mbs.data(), p_short.mbs.data()};
+            const int16_t *c[2] = {p.co.data(), p.co.data()};
+            const uint32_t n[2] = {(uint32_t)p.mbs.size(), (uint32_t)p_short.mbs.size()}, nb[2] = {(uint32_t)p.blocks, (uint32_t)p.blocks};
+            return h263mi_batch_submit_host(b, H263MI_PICTURE_P, m, n, c, nb);
+        }
+        std::vector<uint64_t> view() override
+        {
+            return {(uint64_t)h263mi_batch_stream_has_picture(b, 0), (uint64_t)h263mi_batch_stream_has_picture(b, 1)};
+        }
+    };
+    fault_sweep("h263mi_batch_submit_host (2 streams)", false, [] { return new Batch(); });
+    // every pinned and device block and every event of the objects above went with them
+    CHECK(stub_live_allocations() == live0);
+    CHECK(live0 == 0);
+}
+
+// The order in which h263mi_submit_picture[_events] names what is wrong with a call.  Every case breaks one rule and, where it
+// can, a later one with another code as well: a reordering of the checks changes the answer.
+static void drive_state_precedence()
+{
+    const HostPicture key = host_picture(H263MI_SYNTH_I_MIXED, g_w, g_h, 11, 1);
+    const HostPicture p = host_picture(H263MI_SYNTH_P, g_w, g_h, 12, 2);
+    const HostPicture p2 = host_picture(H263MI_SYNTH_P, 128, 96, 13, 3);
+    const size_t total = p.mbs.size();
+    enum Start { kFresh, kKeyed, kKeyedThenReset };
+    struct Case {
+        const char *name;
+        Start start;
+        int want;
+        std::function<int(h263mi_state *)> call;
+    };
+    auto no_size = [](HostPicture q) { q.desc.width = 0; return q; };
+    size_t dup_block = 0;                                // a block with two events or more
+    while (dup_block < p.blocks && p.first[dup_block + 1] - p.first[dup_block] < 2) dup_block++;
+    CHECK(dup_block < p.blocks);
+    size_t coded = 0;                                    // a record with coded blocks
+    while (coded < total && !p.mbs[coded].cbp) coded++;
+    CHECK(coded < total);
+    const int INV = H263MI_ERR_INVALID_ARGUMENT, PFI = H263MI_ERR_PICTURE_FORMAT_INVALID, UIB = H263MI_ERR_UNCODED_IFRAME_BLOCKS;
+    const std::vector<Case> cases = {
+        {"valid P, dense", kKeyed, H263MI_OK, [&](h263mi_state *st) { return submit_dense(st, p); }},
+        {"valid P, events", kKeyed, H263MI_OK, [&](h263mi_state *st) { return submit_events(st, p); }},
+        // 1. the _events entry: no block offsets, too many blocks
+        {"1 no block_first_event", kKeyed, INV, [&](h263mi_state *st) {
+             const HostPicture q = no_size(p);
+             return h263mi_submit_picture_events(st, &q.desc, q.mbs.data(), total, nullptr, q.blocks, q.ev.data(), q.ev.size());
+         }},
+        {"1 n_coeff_blocks > 2^32/8", kKeyed, INV, [&](h263mi_state *st) {
+             const HostPicture q = no_size(p);
+             return h263mi_submit_picture_events(st, &q.desc, q.mbs.data(), total, q.first.data(), 0xffffffffu / 8u + 1, q.ev.data(), q.ev.size());
+         }},
+        // 2. null arrays
+        {"2 no records", kKeyed, INV, [&](h263mi_state *st) {
+             const HostPicture q = no_size(p);
+             return h263mi_submit_picture(st, &q.desc, nullptr, total, q.co.data(), q.blocks);
+         }},
+        {"2 no coefficients", kKeyed, INV, [&](h263mi_state *st) {
+             const HostPicture q = no_size(p);
+             return h263mi_submit_picture(st, &q.desc, q.mbs.data(), total, nullptr, q.blocks);
+         }},
+        {"2 no events", kKeyed, INV, [&](h263mi_state *st) {
+             const HostPicture q = no_size(p);
+             return h263mi_submit_picture_events(st, &q.desc, q.mbs.data(), total, q.first.data(), q.blocks, nullptr, q.ev.size());
+         }},
+        // 3. the event lists
+        {"3 offsets not from 0", kKeyed, INV, [&](h263mi_state *st) {
+             HostPicture q = no_size(p);
+             q.first[0] = 1;
+             return submit_events(st, q);
+         }},
+        {"3 a position twice", kKeyed, INV, [&](h263mi_state *st) {
+             HostPicture q = no_size(p);
+             q.ev[q.first[dup_block] + 1] = q.ev[q.first[dup_block]];
+             return submit_events(st, q);
+         }},
+        // 4. the size
+        {"4 zero width", kKeyed, PFI, [&](h263mi_state *st) {
+             HostPicture q = no_size(p);
+             q.desc.picture_type = 99;
+             return submit_dense(st, q);
+         }},
+        {"4 too large", kKeyed, PFI, [&](h263mi_state *st) {
+             HostPicture q = p;
+             q.desc.width = q.desc.height = 65535;
+             q.desc.picture_type = 99;
+             return submit_dense(st, q);
+         }},
+        // 5. the picture type, 6. the record count, 7. the records -- before the reference (8)
+        {"5 picture type", kFresh, INV, [&](h263mi_state *st) {
+             HostPicture q = p;
+             q.desc.picture_type = H263MI_PICTURE_RESERVED + 1;
+             return submit_dense(st, q);
+         }},
+        {"6 more records than macroblocks", kFresh, INV, [&](h263mi_state *st) {
+             HostPicture q = p;
+             q.mbs.push_back(q.mbs[0]);
+             return submit_dense(st, q);
+         }},
+        {"7 quantiser 0", kFresh, INV, [&](h263mi_state *st) {
+             HostPicture q = p;
+             q.mbs[total - 1].quant = 0;
+             return submit_dense(st, q);
+         }},
+        {"7 blocks beyond the pool", kFresh, INV, [&](h263mi_state *st) {
+             HostPicture q = p;
+             q.mbs[coded].coeff_index = (uint32_t)q.blocks;
+             return submit_events(st, q);
+         }},
+        // 8. no reference -- before 9. a size change under prediction
+        {"8 inter without a reference", kKeyedThenReset, UIB, [&](h263mi_state *st) { return submit_dense(st, p2); }},
+        {"9 inter across a size change", kKeyed, PFI, [&](h263mi_state *st) { return submit_dense(st, p2); }},
+        // the caps of the batch's host path, ahead of the event lists: at most 2^25 blocks, kMaxEventWords events
+        {"cap blocks", kKeyed, INV, [&](h263mi_state *st) {
+             const HostPicture q = no_size(p);
+             return h263mi_submit_picture(st, &q.desc, q.mbs.data(), total, q.co.data(), ((size_t)1 << 25) + 1);
+         }},
+        {"cap events", kKeyed, INV, [&](h263mi_state *st) {
+             const HostPicture q = no_size(p);
+             return h263mi_submit_picture_events(st, &q.desc, q.mbs.data(), 0, q.first.data(), 0, q.ev.data(), 0xffffff01u);
+         }},
+        {"cap events, an otherwise valid picture", kKeyed, INV, [&](h263mi_state *st) {
+             return h263mi_submit_picture_events(st, &p.desc, p.mbs.data(), 0, p.first.data(), 0, p.ev.data(), 0xffffff01u);
+         }},
+    };
+    for (const Case &c : cases) {
+        h263mi_state *st = nullptr;
+        CHECK(h263mi_state_new(H263MI_SORENSON_SPARK_BITSTREAM, nullptr, &st) == H263MI_OK);
+        if (!st) return;
+        if (c.start != kFresh) CHECK(submit_dense(st, key) == H263MI_OK);
+        if (c.start == kKeyedThenReset) CHECK(h263mi_state_reset(st) == H263MI_OK);
+        const std::vector<uint64_t> before = last_picture(st);
+        const int rc = c.call(st);
+        fprintf(stderr, "  precedence %-40s %d\n", c.name, rc);
+        CHECK(rc == c.want);
+        if (rc != H263MI_OK) CHECK(last_picture(st) == before);
+        h263mi_state_free(st);
+    }
+}
+
 int main(int argc, char **argv)
 {
     if (argc < 2 || !load_corpus(argv[1])) {
@@ -360,6 +632,8 @@ int main(int argc, char **argv)
     const int rounds = argc > 2 ? atoi(argv[2]) : 2;
     if (argc > 3) g_max_threads = (uint32_t)atoi(argv[3]);
     const uint32_t n = (uint32_t)g_corpus.size();
+    drive_fault_sweeps();
+    drive_state_precedence();
     drive_device_arrays();
     drive_host_garbage(900, 400);
     for (int r = 0; r < rounds; r++) {
