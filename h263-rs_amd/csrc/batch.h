@@ -261,4 +261,30 @@ int batch_submit_host(h263mi_batch *b, uint8_t picture_type, const h263mi_mb_rec
                       const uint8_t *types = nullptr, bool deferred_post = false, const uint32_t *const *group_index = nullptr,
                       const DirectWords *direct = nullptr);
 
+// What the bitstream entries set before bits::parse_picture: events, no dense blocks, the frame store's size limit, sparse records
+// or not, and nothing parsed into a caller's memory (an entry with a staging slot to parse into sets the *_ext fields after this).
+inline void prepare_for_parse(bits::ParsedPicture &pic, bool sparse)
+{
+    pic.want_dense = false;
+    pic.size_fits = &picture_size_fits;
+    pic.sparse_records = sparse;
+    pic.mbs_ext = nullptr;
+    pic.events_ext = pic.first_event_ext = pic.group_index_ext = nullptr;
+    pic.mbs_ext_cap = pic.events_ext_cap = pic.first_event_ext_cap = pic.group_index_ext_cap = pic.event_base = 0;
+}
+// The serial half of decode_next_picture (state.rs:143-427): parse(i) for the n streams on plan.threads host threads
+// (StreamDeal), from the pool `workers` hands out when there are several.  timed (may be null): the batch whose
+// H263MI_TRACE_E2E timing counts the phase (host_ms[0]).
+void parse_streams(const HostThreadPlan &plan, const std::function<WorkerPool &(unsigned)> &workers, uint32_t n,
+                   const std::function<void(uint32_t)> &parse, h263mi_batch *timed = nullptr);
+// One launch of batch b from parsed pictures (batch_submit_host): slot s decodes *pics[s], nullptr = the slot sits the call out
+// (the slots' active flags are set for the call and restored).  Then the rendering, deferred on a pipelined batch, into d_rgba /
+// d_planes or rgba_ptrs (one DEVICE pointer per slot, nullptr = none), if there is any output.  from_header: st.per_stream
+// (sized) is filled in from the headers.  The launch's and the rendering's rc come back apart: a picture whose launch is queued
+// is decoded, whatever the rendering does.
+struct SubmitResult { int rc, render_rc; };
+SubmitResult submit_parsed(h263mi_batch *b, const bits::ParsedPicture *const *pics, uint32_t pack_threads, bool sparse_records,
+                           const DirectWords *direct, h263mi_batch::Strengths st, bool from_header, uint8_t *d_rgba,
+                           uint8_t *d_planes, uint8_t *const *rgba_ptrs = nullptr);
+
 }  // namespace h263mi

@@ -274,11 +274,69 @@ int batch_submit_host(h263mi_batch *b, uint8_t picture_type, const h263mi_mb_rec
     return H263MI_OK;
 }
 
+void parse_streams(const HostThreadPlan &plan, const std::function<WorkerPool &(unsigned)> &workers, uint32_t n,
+                   const std::function<void(uint32_t)> &parse, h263mi_batch *timed)
+{
+    const uint32_t n_thr = plan.threads;
+    StreamDeal deal(n);
+    auto work = [&](unsigned t) { deal.run(t, n_thr, parse); };
+    const auto t_parse0 = std::chrono::steady_clock::now();
+    if (n_thr == 1) work(0);
+    else workers(n_thr).run(n_thr, work, plan.spin_us);
+    if (timed && timed->trace_host) {
+        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_parse0).count();
+        timed->host_ms[0] += ms;
+        if (timed->trace_each) fprintf(stderr, "h263mi parse phase: %.3f ms on %u threads\n", ms, n_thr);
+    }
+}
+
+SubmitResult submit_parsed(h263mi_batch *b, const bits::ParsedPicture *const *pics, uint32_t pack_threads, bool sparse_records,
+                           const DirectWords *direct, h263mi_batch::Strengths st, bool from_header, uint8_t *d_rgba,
+                           uint8_t *d_planes, uint8_t *const *rgba_ptrs)
+{
+    const uint32_t n = b->n;
+    static const uint32_t kNoEvents[1] = {0};
+    std::vector<const h263mi_mb_record *> mbs(n, nullptr);
+    std::vector<const uint32_t *> first(n, kNoEvents), events(n, nullptr), gidx(n, nullptr);
+    std::vector<uint32_t> n_mbs(n, 0), n_blocks(n, 0), n_events(n, 0);
+    std::vector<uint8_t> types(n, H263MI_PICTURE_P), was_active(n);
+    bool any_out = d_rgba || d_planes;
+    for (uint32_t s = 0; s < n; s++) {
+        // the slots that take part in THIS call (restored below: h263mi_batch_set_active is the caller's)
+        was_active[s] = b->ss[s].active;
+        b->ss[s].active = pics[s] != nullptr;
+        if (from_header) st.per_stream[s] = pics[s] ? strength_from_header(pics[s]->desc) : (uint8_t)0;
+        if (!pics[s]) continue;
+        const bits::ParsedPicture &pic = *pics[s];
+        mbs[s] = pic.records();
+        n_mbs[s] = (uint32_t)pic.n_records();
+        gidx[s] = pic.group_index_words();
+        first[s] = pic.first_event_words();
+        events[s] = pic.event_words();
+        n_blocks[s] = (uint32_t)pic.n_coded_blocks;
+        n_events[s] = (uint32_t)pic.n_event_words();
+        types[s] = pic.desc.picture_type;
+        if (rgba_ptrs && rgba_ptrs[s]) any_out = true;
+    }
+    const bool deferred = b->pipeline_post && any_out;
+    SubmitResult r{H263MI_OK, H263MI_OK};
+    r.rc = batch_submit_host(b, H263MI_PICTURE_P, mbs.data(), n_mbs.data(), nullptr, n_blocks.data(), first.data(), events.data(),
+                             n_events.data(), /*validated=*/true, pack_threads, types.data(), deferred,
+                             sparse_records ? gidx.data() : nullptr, direct);
+    // (a failed rendering is reported, but it does not un-decode anything)
+    if (r.rc == H263MI_OK) {
+        if (deferred) r.render_rc = b->note_pending(st, d_rgba, d_planes, rgba_ptrs);
+        else if (any_out) r.render_rc = b->render(st, d_rgba, d_planes, /*only_active=*/true, rgba_ptrs);
+    }
+    for (uint32_t s = 0; s < n; s++) b->ss[s].active = was_active[s] != 0;
+    return r;
+}
+
 // N x decode_next_picture.  stream_rc == nullptr: all or nothing (any stream's error fails the call, nothing changes).
 // stream_rc != nullptr: every stream is its own H263State -- a stream that fails keeps its state (state.rs:142) and gets
 // its error code, a stream without data (data[i] == nullptr) is left alone, the others advance.
-// st: the post-filter strength of the pictures of this call; st.per_stream is filled in here when `from_header` is set:
-// each picture with what its own header asks for (host_common.h: strength_from_header).
+// st: the post-filter strength of the pictures of this call; st.per_stream is filled in when `from_header` is set: each
+// picture with what its own header asks for (host_common.h: strength_from_header).
 static int batch_decode_next_pictures(h263mi_batch *b, uint32_t decoder_options, const uint8_t *const *data, const size_t *len,
                                       size_t *consumed, uint32_t n_threads, int *stream_rc, h263mi_batch::Strengths st,
                                       bool from_header, uint8_t *d_rgba, uint8_t *d_deblocked)
@@ -313,8 +371,7 @@ static int batch_decode_next_pictures(h263mi_batch *b, uint32_t decoder_options,
         if (b->trace_host) b->host_ms[1] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_wait).count();
     }
     const size_t per = (size_t)b->L.mbw * b->L.mbh;
-    // H263MI_SPARSE_RECORDS=0: dense record arrays over the link, as rounds 2-4 sent them (A/B switch)
-    static const bool sparse_rec = !(getenv("H263MI_SPARSE_RECORDS") && getenv("H263MI_SPARSE_RECORDS")[0] == '0');
+    const bool sparse_rec = sparse_records_enabled();
     // DIRECT WORDS (see DirectWords): every stream's events, block offsets and group index are parsed straight into the
     // staging slot, at pitches that hold the worst case of this call's pictures -- as long as that worst case is a sensible
     // amount of pinned memory (a 1080p key frame of 100 KB: 1 MB per stream; the 2.3 MB test key frames take the packed form).
@@ -334,57 +391,44 @@ static int batch_decode_next_pictures(h263mi_batch *b, uint32_t decoder_options,
         if (direct) RC_TRY(b->ensure_host_staging(g2, 1, (size_t)n * (dw.pitch_blocks + dw.pitch_events)));
     }
     const size_t groups_pp = (size_t)recon_tiles_x(b->L) * b->L.mbh;
-    // ---- the serial half of decode_next_picture (state.rs:143-427), one stream per task, on n_threads host threads
+    // ---- the serial half of decode_next_picture, one stream per task
     std::vector<int> rcs(n, H263MI_OK);
     const HostThreadPlan plan = host_thread_plan(n, n_threads);
-    const uint32_t n_thr = plan.threads;
     b->pool_spin_us = plan.spin_us;
-    StreamDeal deal(n);
-    auto work = [&](unsigned t) {
-        deal.run(t, n_thr, [&](uint32_t i) {
-            if (!data[i] || !b->ss[i].active) return;            // no picture for this stream in this call
-            bits::ParsedPicture &pic = b->parsed[i];
-            pic.want_dense = false;                              // the coefficients travel as events
-            pic.size_fits = &picture_size_fits;
-            pic.sparse_records = sparse_rec;                     // records for the coded macroblocks only (round 5)
-            pic.mbs_ext = g2.mbs.h + (size_t)i * per;
-            pic.mbs_ext_cap = per;
-            pic.events_ext = direct ? g2.h_events + (size_t)n * dw.pitch_blocks + (size_t)i * dw.pitch_events : nullptr;
-            pic.events_ext_cap = direct ? dw.pitch_events : 0;
-            pic.first_event_ext = direct ? g2.h_events + (size_t)i * dw.pitch_blocks : nullptr;
-            pic.first_event_ext_cap = direct ? dw.pitch_blocks : 0;
-            pic.group_index_ext = direct ? g2.h_index + (size_t)i * groups_pp : nullptr;
-            pic.group_index_ext_cap = direct ? groups_pp : 0;
-            pic.event_base = direct ? (uint32_t)((size_t)i * dw.pitch_events) : 0u;
-            int rc = bits::parse_picture(data[i], len[i], decoder_options, &b->parser_ctx[i], pic);
-            if (rc == H263MI_OK && (pic.desc.width != b->L.width || pic.desc.height != b->L.height)) rc = H263MI_ERR_PICTURE_FORMAT_INVALID;
-            // (a picture of the batch's size fits the pitches by construction: anything else is a fault of this library)
-            if (rc == H263MI_OK && direct && !pic.words_ext_used) rc = H263MI_ERR_INTERNAL_DECODER_ERROR;
-            // gather.rs:149: an inter macroblock without a reference picture is Error::UncodedIFrameBlocks -- found here,
-            // before anything is queued, so that the stream (parser state included) stays as it was (macroblocks the picture
-            // does not code are padded as Inter, state.rs:421-427: the parser's any_inter covers them)
-            if (rc == H263MI_OK && !(b->ss[i].has_ref && b->ss[i].cur >= 0) && pic.any_inter) rc = H263MI_ERR_UNCODED_IFRAME_BLOCKS;
-            rcs[i] = rc;
-        });
-    };
-    const auto t_parse0 = std::chrono::steady_clock::now();
-    if (n_thr == 1) work(0);
-    else b->workers(n_thr).run(n_thr, work, plan.spin_us);
-    if (b->trace_host) {
-        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_parse0).count();
-        b->host_ms[0] += ms;
-        if (b->trace_each) fprintf(stderr, "h263mi parse phase: %.3f ms on %u threads\n", ms, n_thr);
-    }
-    std::vector<uint8_t> takes_part(n), types(n, H263MI_PICTURE_P);
+    parse_streams(plan, [b](unsigned k) -> WorkerPool & { return b->workers(k); }, n, [&](uint32_t i) {
+        if (!data[i] || !b->ss[i].active) return;                // no picture for this stream in this call
+        bits::ParsedPicture &pic = b->parsed[i];
+        prepare_for_parse(pic, sparse_rec);
+        pic.mbs_ext = g2.mbs.h + (size_t)i * per;
+        pic.mbs_ext_cap = per;
+        if (direct) {
+            pic.events_ext = g2.h_events + (size_t)n * dw.pitch_blocks + (size_t)i * dw.pitch_events;
+            pic.events_ext_cap = dw.pitch_events;
+            pic.first_event_ext = g2.h_events + (size_t)i * dw.pitch_blocks;
+            pic.first_event_ext_cap = dw.pitch_blocks;
+            pic.group_index_ext = g2.h_index + (size_t)i * groups_pp;
+            pic.group_index_ext_cap = groups_pp;
+            pic.event_base = (uint32_t)((size_t)i * dw.pitch_events);
+        }
+        int rc = bits::parse_picture(data[i], len[i], decoder_options, &b->parser_ctx[i], pic);
+        if (rc == H263MI_OK && (pic.desc.width != b->L.width || pic.desc.height != b->L.height)) rc = H263MI_ERR_PICTURE_FORMAT_INVALID;
+        // (a picture of the batch's size fits the pitches by construction: anything else is a fault of this library)
+        if (rc == H263MI_OK && direct && !pic.words_ext_used) rc = H263MI_ERR_INTERNAL_DECODER_ERROR;
+        // gather.rs:149: an inter macroblock without a reference picture is Error::UncodedIFrameBlocks -- found here,
+        // before anything is queued, so that the stream (parser state included) stays as it was (macroblocks the picture
+        // does not code are padded as Inter, state.rs:421-427: the parser's any_inter covers them)
+        if (rc == H263MI_OK && !(b->ss[i].has_ref && b->ss[i].cur >= 0) && pic.any_inter) rc = H263MI_ERR_UNCODED_IFRAME_BLOCKS;
+        rcs[i] = rc;
+    }, b);
+    std::vector<const bits::ParsedPicture *> pics(n, nullptr);
     int first_error = H263MI_OK;
     uint32_t n_ok = 0;
     for (uint32_t i = 0; i < n; i++) {
-        takes_part[i] = data[i] && b->ss[i].active && rcs[i] == H263MI_OK;
-        if (rcs[i] != H263MI_OK && first_error == H263MI_OK) first_error = rcs[i];
-        if (takes_part[i]) {
-            types[i] = b->parsed[i].desc.picture_type;
+        if (data[i] && b->ss[i].active && rcs[i] == H263MI_OK) {
+            pics[i] = &b->parsed[i];
             n_ok++;
         }
+        if (rcs[i] != H263MI_OK && first_error == H263MI_OK) first_error = rcs[i];
         if (stream_rc) stream_rc[i] = rcs[i];
     }
     // all or nothing: the batch -- frames, reference bookkeeping and what it remembers of the picture headers -- is
@@ -393,51 +437,17 @@ static int batch_decode_next_pictures(h263mi_batch *b, uint32_t decoder_options,
     if (consumed)
         for (uint32_t i = 0; i < n; i++) consumed[i] = 0;
     if (!n_ok) return first_error;
-    std::vector<const h263mi_mb_record *> mbs(n);
-    std::vector<const uint32_t *> first(n), events(n), gidx(n, nullptr);
-    std::vector<uint32_t> n_mbs(n, 0), n_blocks(n, 0), n_events(n, 0);
-    static const uint32_t kNoEvents[1] = {0};
+    const SubmitResult r = submit_parsed(b, pics.data(), plan.threads, sparse_rec, direct ? &dw : nullptr, std::move(st), from_header,
+                                         d_rgba, d_deblocked);
+    RC_TRY(r.rc);
+    // the pictures are decoded: what the streams remember of their headers moves on with them, whatever happened to the
+    // rendering
     for (uint32_t i = 0; i < n; i++) {
-        const bits::ParsedPicture &pic = b->parsed[i];
-        mbs[i] = g2.mbs.h + (size_t)i * per;
-        first[i] = kNoEvents;
-        events[i] = nullptr;
-        if (!takes_part[i]) continue;
-        mbs[i] = pic.records();
-        n_mbs[i] = (uint32_t)pic.n_records();
-        gidx[i] = pic.group_index_words();
-        first[i] = pic.first_event_words();
-        events[i] = pic.event_words();
-        n_blocks[i] = (uint32_t)pic.n_coded_blocks;
-        n_events[i] = (uint32_t)pic.n_event_words();
+        if (!pics[i]) continue;
+        b->parser_ctx[i] = pics[i]->next;
+        if (consumed) consumed[i] = pics[i]->bits_consumed / 8;      // reader.commit() drains whole bytes
     }
-    // the streams that take part in THIS call (restored below: h263mi_batch_set_active is the caller's)
-    std::vector<uint8_t> was_active(n);
-    for (uint32_t i = 0; i < n; i++) {
-        was_active[i] = b->ss[i].active;
-        b->ss[i].active = takes_part[i] != 0;
-    }
-    if (from_header)
-        for (uint32_t i = 0; i < n; i++) st.per_stream[i] = takes_part[i] ? strength_from_header(b->parsed[i].desc) : (uint8_t)0;
-    const bool deferred = b->pipeline_post && (d_rgba || d_deblocked);
-    int rc = batch_submit_host(b, H263MI_PICTURE_P, mbs.data(), n_mbs.data(), nullptr, n_blocks.data(), first.data(), events.data(),
-                               n_events.data(), /*validated=*/true, n_thr, types.data(), deferred, sparse_rec ? gidx.data() : nullptr,
-                               direct ? &dw : nullptr);
-    int render_rc = H263MI_OK;
-    if (rc == H263MI_OK) {
-        // the pictures are decoded: what the streams remember of their headers moves on with them, whatever happens to the
-        // rendering below (a failed rendering is reported, but it does not un-decode anything)
-        for (uint32_t i = 0; i < n; i++) {
-            if (!takes_part[i]) continue;
-            b->parser_ctx[i] = b->parsed[i].next;
-            if (consumed) consumed[i] = b->parsed[i].bits_consumed / 8;      // reader.commit() drains whole bytes
-        }
-        if (deferred) render_rc = b->note_pending(st, d_rgba, d_deblocked);
-        else if (d_rgba || d_deblocked) render_rc = b->render(st, d_rgba, d_deblocked, /*only_active=*/true);
-    }
-    for (uint32_t i = 0; i < n; i++) b->ss[i].active = was_active[i] != 0;
-    RC_TRY(rc);
-    RC_TRY(render_rc);
+    RC_TRY(r.render_rc);
     return stream_rc ? H263MI_OK : first_error;
 }
 

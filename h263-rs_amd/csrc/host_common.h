@@ -78,6 +78,12 @@ constexpr uint64_t kMaxEventWords = 0xffffff00ull;
 // Block offsets inside a stream's share of the pool are 32-bit byte offsets on the device (recon_block_limit): the blocks of one
 // stream in one call.
 constexpr uint64_t kMaxStreamBlocks = 1ull << 25;
+// H263MI_SPARSE_RECORDS=0: dense record arrays over the link, as rounds 2-4 sent them (A/B switch; read once)
+inline bool sparse_records_enabled()
+{
+    static const bool on = !(getenv("H263MI_SPARSE_RECORDS") && getenv("H263MI_SPARSE_RECORDS")[0] == '0');
+    return on;
+}
 // what the parser asks right behind a picture header (bits::ParsedPicture::size_fits): can the frame store hold such a picture?
 inline bool picture_size_fits(uint32_t w, uint32_t h) { return layout_fits(w, h); }
 // tile geometry of k_post for the layout in a.L (post_kernel.inl: post_tile_columns)

@@ -37,6 +37,15 @@ struct h263mi_mixed {
             for (int s : stream_of_slot) k += s >= 0 ? 1u : 0u;
             return k;
         }
+        // slot s is free again, its stream state forgotten (the frames are not touched: a rendering of its last picture that
+        // is still pending is delivered all the same)
+        void free_slot(int s)
+        {
+            const bool a = b->ss[s].active;
+            b->ss[s] = h263mi_batch::StreamState();
+            b->ss[s].active = a;
+            stream_of_slot[s] = -1;
+        }
     };
     std::vector<SizeClass> classes;
     struct Want { uint32_t w, h; };             // the size a stream's picture of the current call has
@@ -237,26 +246,16 @@ int h263mi_mixed_decode_next_pictures_ps(h263mi_mixed *m, uint32_t decoder_optio
         if (!data[i] && len[i]) return H263MI_ERR_INVALID_ARGUMENT;
     DeviceGuard g(m->cfg.device_id);
     if (!g.ok) return H263MI_ERR_NO_DEVICE;
-    // ---- the serial half of decode_next_picture (state.rs:143-427) per stream, on the host threads
-    static const bool mixed_sparse = !(getenv("H263MI_SPARSE_RECORDS") && getenv("H263MI_SPARSE_RECORDS")[0] == '0');
+    // ---- the serial half of decode_next_picture (state.rs:143-427) per stream, on the host threads (the class -- and with
+    // it the staging slot -- is known after the header: parsed into the set's own buffers)
+    const bool sparse = sparse_records_enabled();
     std::vector<int> rcs(n, H263MI_OK);
     const HostThreadPlan plan = host_thread_plan(n, n_threads);
-    const uint32_t n_thr = plan.threads;
-    StreamDeal deal(n);
-    auto work = [&](unsigned t) {
-        deal.run(t, n_thr, [&](uint32_t i) {
-            if (!data[i]) return;
-            bits::ParsedPicture &pic = m->parsed[i];
-            pic.want_dense = false;
-            pic.size_fits = &picture_size_fits;
-            pic.sparse_records = mixed_sparse;   // records for the coded macroblocks only (see batch_submit_host)
-            pic.mbs_ext = nullptr;               // (the class -- and with it the staging slot -- is known after the header)
-            pic.mbs_ext_cap = 0;
-            rcs[i] = bits::parse_picture(data[i], len[i], decoder_options, &m->parser_ctx[i], pic);
-        });
-    };
-    if (n_thr == 1) work(0);
-    else m->workers(n_thr).run(n_thr, work, plan.spin_us);
+    parse_streams(plan, [m](unsigned k) -> WorkerPool & { return m->workers(k); }, n, [&](uint32_t i) {
+        if (!data[i]) return;
+        prepare_for_parse(m->parsed[i], sparse);
+        rcs[i] = bits::parse_picture(data[i], len[i], decoder_options, &m->parser_ctx[i], m->parsed[i]);
+    });
 
     // ---- which size each picture has; what must be refused before anything is queued
     std::vector<int> target(n, -1);
@@ -329,98 +328,59 @@ int h263mi_mixed_decode_next_pictures_ps(h263mi_mixed *m, uint32_t decoder_optio
     // (a class that stands three quarters empty gives the room back in h263mi_mixed_sync -- where everything has been waited
     // for anyway -- not here: sizes come out of untrusted bitstreams, and streams that alternate between two sizes could
     // otherwise force a sync, device-to-device copies and an allocation out of every decode call)
-    for (h263mi_mixed::SizeClass &c : m->classes) c.submitted = false;
 
     // ---- one launch per class that has pictures
     // (a class whose RENDERING fails does not stop the others: every class that has pictures is decoded, and the first
     // rendering error is what the call returns at the end -- no stream is left with H263MI_OK and no decoded picture)
     int call_rc = H263MI_OK;
-    static const uint32_t kNoEvents[1] = {0};
     for (size_t k = 0; k < m->classes.size(); k++) {
         h263mi_mixed::SizeClass &c = m->classes[k];
         h263mi_batch *b = c.b;
+        c.submitted = false;
         if (!b) continue;                        // (a class that was given up)
         const uint32_t slots = b->n;
-        std::vector<const h263mi_mb_record *> mbs(slots, nullptr);
-        std::vector<const uint32_t *> first(slots, kNoEvents), events(slots, nullptr), gidx(slots, nullptr);
-        std::vector<uint32_t> n_mbs(slots, 0), n_blocks(slots, 0), n_events(slots, 0);
-        std::vector<uint8_t> types(slots, H263MI_PICTURE_P), was_active(slots, 0);
+        std::vector<const bits::ParsedPicture *> pics(slots, nullptr);
         std::vector<uint8_t *> out_ptrs(slots, nullptr);
         h263mi_batch::Strengths cst;             // ... of this class's slots
         if (from_header || strengths) cst.per_stream.assign(slots, 0);
         else cst.uniform = set_strength.uniform;
         uint32_t members = 0;
-        bool any_out = false;
         for (uint32_t s = 0; s < slots; s++) {
             const int i = c.stream_of_slot[s];
-            was_active[s] = b->ss[s].active;
-            b->ss[s].active = false;
             if (i < 0 || target[i] != (int)k) continue;
             const bool joins = m->cls[i] != (int)k;
             if (joins ? new_slot[i] != (int)s : m->slot[i] != (int)s) continue;
-            const bits::ParsedPicture &pic = m->parsed[i];
+            pics[s] = &m->parsed[i];
             members++;
-            mbs[s] = pic.records();
-            n_mbs[s] = (uint32_t)pic.n_records();
-            first[s] = pic.block_first_event.data();
-            events[s] = pic.events.data();
-            gidx[s] = pic.group_index.data();
-            n_blocks[s] = (uint32_t)pic.n_coded_blocks;
-            n_events[s] = (uint32_t)pic.events.size();
-            types[s] = pic.desc.picture_type;
-            if (d_rgba && d_rgba[i]) { out_ptrs[s] = d_rgba[i]; any_out = true; }
-            if (!cst.per_stream.empty()) cst.per_stream[s] = from_header ? strength_from_header(pic.desc) : set_strength.of((uint32_t)i);
+            if (d_rgba) out_ptrs[s] = d_rgba[i];
+            if (strengths) cst.per_stream[s] = set_strength.of((uint32_t)i);
             // a stream that arrives from another class starts afresh here (it brings an I picture)
             if (joins) b->ss[s] = h263mi_batch::StreamState();
-            b->ss[s].active = true;
         }
-        int rc = H263MI_OK;
-        if (members) {
-            const bool deferred = b->pipeline_post && any_out;
-            rc = batch_submit_host(b, H263MI_PICTURE_P, mbs.data(), n_mbs.data(), nullptr, n_blocks.data(), first.data(), events.data(),
-                                   n_events.data(), /*from_parser=*/true, n_thr, types.data(), deferred, mixed_sparse ? gidx.data() : nullptr);
-            if (rc == H263MI_OK) {
-                c.submitted = true;
-                // the pictures are decoded: the streams move to this class, their parser state moves on (state.rs:464-483)
-                for (uint32_t i = 0; i < n; i++) {
-                    if (target[i] != (int)k) continue;
-                    const int c_old = m->cls[i];
-                    if (c_old != (int)k) {
-                        if (c_old >= 0) {
-                            // the slot the stream leaves: given up now, not earlier (its last picture lived there)
-                            h263mi_mixed::SizeClass &oc = m->classes[c_old];
-                            const int os = m->slot[i];
-                            const bool a = oc.b->ss[os].active;
-                            oc.b->ss[os] = h263mi_batch::StreamState();
-                            oc.b->ss[os].active = a;
-                            oc.stream_of_slot[os] = -1;
-                            // (a rendering of the old picture that is still pending there is delivered all the same: it names
-                            // the frame set, and the frames themselves are not touched)
-                        }
-                        m->cls[i] = (int)k;
-                        m->slot[i] = new_slot[i];
-                    }
-                    m->parser_ctx[i] = m->parsed[i].next;
-                    if (consumed) consumed[i] = m->parsed[i].bits_consumed / 8;
-                    if (descs) descs[i] = m->parsed[i].desc;
-                }
-                int render_rc = H263MI_OK;
-                if (deferred) render_rc = b->note_pending(cst, nullptr, nullptr, out_ptrs.data());
-                else if (any_out) render_rc = b->render(cst, nullptr, nullptr, /*only_active=*/true, out_ptrs.data());
-                if (render_rc != H263MI_OK && call_rc == H263MI_OK) call_rc = render_rc;
-            } else {
+        if (!members) continue;
+        const SubmitResult r = submit_parsed(b, pics.data(), plan.threads, sparse, nullptr, std::move(cst), from_header, nullptr, nullptr,
+                                             out_ptrs.data());
+        c.submitted = r.rc == H263MI_OK;
+        for (uint32_t i = 0; i < n; i++) {
+            if (target[i] != (int)k) continue;
+            if (r.rc != H263MI_OK) {
                 // the class's launch did not happen: its members keep their state and get the error, the joiners their old place
-                for (uint32_t i = 0; i < n; i++) {
-                    if (target[i] != (int)k) continue;
-                    stream_rc[i] = rc;
-                    if (m->cls[i] != (int)k && new_slot[i] >= 0) {
-                        b->ss[new_slot[i]] = h263mi_batch::StreamState();
-                        c.stream_of_slot[new_slot[i]] = -1;
-                    }
-                }
+                stream_rc[i] = r.rc;
+                if (m->cls[i] != (int)k && new_slot[i] >= 0) c.free_slot(new_slot[i]);
+                continue;
             }
+            // the pictures are decoded: the streams move to this class, their parser state moves on (state.rs:464-483)
+            if (m->cls[i] != (int)k) {
+                // the slot the stream leaves: given up now, not earlier (its last picture lived there)
+                if (m->cls[i] >= 0) m->classes[m->cls[i]].free_slot(m->slot[i]);
+                m->cls[i] = (int)k;
+                m->slot[i] = new_slot[i];
+            }
+            m->parser_ctx[i] = m->parsed[i].next;
+            if (consumed) consumed[i] = m->parsed[i].bits_consumed / 8;
+            if (descs) descs[i] = m->parsed[i].desc;
         }
-        for (uint32_t s = 0; s < slots; s++) b->ss[s].active = was_active[s] != 0;
+        if (r.render_rc != H263MI_OK && call_rc == H263MI_OK) call_rc = r.render_rc;
     }
     // a class that is waiting to render its previous pictures and had nothing to decode in this call renders them now
     // (on a pipelined class the rendering rides in the NEXT launch of that class: without one it would wait for the sync)

@@ -152,10 +152,7 @@ int h263mi_decode_next_picture(h263mi_state *s, const uint8_t *data, size_t len,
     if (consumed) *consumed = 0;
     // serial half on the host (state.rs:143-427) ...
     bits::ParsedPicture &pic = s->parsed;                // (kept between calls: no allocation per picture)
-    pic.want_dense = false;                              // the coefficients travel as events
-    pic.size_fits = &picture_size_fits;
-    pic.mbs_ext = nullptr;
-    pic.mbs_ext_cap = 0;
+    prepare_for_parse(pic, /*sparse=*/false);
     if (s->b) {
         // A stream rarely changes its size: the records are parsed straight into the batch's staging slot the next submit
         // copies from (sized for the last picture; a picture with more macroblocks falls back to the parser's own array).

@@ -13,15 +13,22 @@
 //     with more threads than the quota take the parking plan (spin 0) and the others the spinning plan;
 //   * pools torn down in the middle of an idle spin and right after a call;
 //   * two batches, a mixed-size set and one H263State driven from four threads at the same time (distinct objects may be);
+//   * with a second corpus of another size: streams of the mixed-size set that move between the two classes at key frames, a P
+//     picture of the other size refused, a class that doubles when streams join it and shrinks at the sync that finds it at most
+//     a quarter full;
 //   * the packed (H263MI_DIRECT_WORDS=0) transport, and workers that never park (H263MI_SPIN_US = 50 ms, no quota, at most 6
 //     threads: every hand-over goes through the generation word alone, never through the mutex): further runs of the test.
-//   * a failure injected at every HIP call of h263mi_submit_picture[_events], h263mi_decode_next_picture and a 2-stream
-//     h263mi_batch_submit_host: the last picture stays as it was, and every pinned block, device block and event the objects
-//     held is given back (the stub runtime counts them);
+//   * a failure injected at every HIP call of h263mi_submit_picture[_events], h263mi_decode_next_picture, a 2-stream
+//     h263mi_batch_submit_host and h263mi_batch_decode_next_pictures_ps: the last picture stays as it was; and of a 3-stream,
+//     two-size h263mi_mixed_decode_next_pictures_ps in which a stream moves class; every pinned block, device block and event
+//     the objects held is given back (the stub runtime counts them);
 //   * the order in which h263mi_submit_picture[_events] names what is wrong with a call, one crafted case per rule.
 // Exit code 0 and no ThreadSanitizer report = pass.  The same driver built with -DH263MI_TSAN_BREAK_GENERATION_ORDER (the task is
 // published with a relaxed store: worker_pool.cpp) MUST make ThreadSanitizer report a race: tests/test_tsan.py checks both.
-// usage: tsan_driver <corpus.bin> [rounds [max threads]]      corpus: u32 streams, u32 frames, then per (stream, frame): u32 length, bytes
+// usage: tsan_driver <corpus.bin> [rounds [max threads [corpus2.bin]]]
+//   corpus: u32 streams, u32 frames, u32 width, u32 height, then per (stream, frame): u32 length, bytes; corpus2 (optional): the
+//   same at another picture size, for the mixed-size set's class moves, growth and shrinking
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -40,6 +47,9 @@ long stub_live_allocations();                                        // stub_run
 
 static std::vector<std::vector<std::vector<uint8_t>>> g_corpus;      // [stream][frame]
 static uint16_t g_w, g_h;
+// (optional) a second corpus of another picture size: the mixed-size set's second class
+static std::vector<std::vector<std::vector<uint8_t>>> g_corpus2;
+static uint16_t g_w2, g_h2;
 static std::atomic<int> g_failures{0};
 static uint32_t g_max_threads = 40;                                  // (third argument: runs whose workers SPIN keep within the CPUs)
 
@@ -51,16 +61,16 @@ static uint32_t g_max_threads = 40;                                  // (third a
         }                                                                            \
     } while (0)
 
-static bool load_corpus(const char *path)
+static bool load_corpus(const char *path, std::vector<std::vector<std::vector<uint8_t>>> &corpus, uint16_t &w, uint16_t &h)
 {
     FILE *f = fopen(path, "rb");
     if (!f) return false;
     uint32_t hdr[4];
     if (fread(hdr, 4, 4, f) != 4) return false;
-    g_w = (uint16_t)hdr[2];
-    g_h = (uint16_t)hdr[3];
-    g_corpus.assign(hdr[0], std::vector<std::vector<uint8_t>>(hdr[1]));
-    for (auto &s : g_corpus)
+    w = (uint16_t)hdr[2];
+    h = (uint16_t)hdr[3];
+    corpus.assign(hdr[0], std::vector<std::vector<uint8_t>>(hdr[1]));
+    for (auto &s : corpus)
         for (auto &p : s) {
             uint32_t n = 0;
             if (fread(&n, 4, 1, f) != 1) return false;
@@ -128,9 +138,10 @@ static void drive_mixed(unsigned seed, uint32_t n, int calls)
     CHECK(h263mi_mixed_create(n, &cfg, &m) == H263MI_OK);
     if (!m) return;
     std::vector<void *> bufs(n, nullptr);
-    std::vector<size_t> caps(n, (size_t)g_w * g_h * 4);
+    std::vector<size_t> caps(n, (size_t)std::max(g_w * g_h, g_w2 * g_h2) * 4);
     for (uint32_t s = 0; s < n; s++) CHECK(h263mi_device_malloc(0, caps[s], &bufs[s]) == H263MI_OK);
     std::vector<uint32_t> next(n, 0);
+    std::vector<uint8_t> small(n, 0);            // the stream's pictures come from the second corpus (moved there at a key frame)
     const uint32_t frames = (uint32_t)g_corpus[0].size();
     for (int c = 0; c < calls; c++) {
         std::vector<const uint8_t *> data(n, nullptr);
@@ -139,7 +150,8 @@ static void drive_mixed(unsigned seed, uint32_t n, int calls)
         for (uint32_t s = 0; s < n; s++) {
             if (next[s] && rng() % 3 == 0) continue;
             if (next[s] >= frames) next[s] = 0;
-            const std::vector<uint8_t> &p = g_corpus[(s + 3) % g_corpus.size()][next[s]];
+            if (next[s] == 0 && !g_corpus2.empty()) small[s] = rng() % 3 == 0;
+            const std::vector<uint8_t> &p = small[s] ? g_corpus2[s % g_corpus2.size()][next[s]] : g_corpus[(s + 3) % g_corpus.size()][next[s]];
             data[s] = p.data();
             len[s] = p.size();
         }
@@ -157,6 +169,129 @@ static void drive_mixed(unsigned seed, uint32_t n, int calls)
     CHECK(h263mi_mixed_sync(m, nullptr) == H263MI_OK);
     h263mi_mixed_destroy(m);
     for (void *p : bufs) CHECK(h263mi_device_free(0, p) == H263MI_OK);
+}
+
+// One call of a mixed-size set: pick[s] = {corpus (0: no picture, 1: the first, 2: the second), frame}.  rcs / used: per stream.
+struct MixedCall {
+    h263mi_mixed *m = nullptr;
+    std::vector<void *> bufs;
+    std::vector<size_t> caps;
+    MixedCall(uint32_t n, bool pipeline)
+    {
+        h263mi_backend_cfg cfg{0, pipeline ? H263MI_CFG_PIPELINE_POST : 0u, nullptr};
+        CHECK(h263mi_mixed_create(n, &cfg, &m) == H263MI_OK);
+        bufs.assign(n, nullptr);
+        caps.assign(n, (size_t)std::max(g_w * g_h, g_w2 * g_h2) * 4);
+        for (uint32_t s = 0; s < n; s++) CHECK(h263mi_device_malloc(0, caps[s], &bufs[s]) == H263MI_OK);
+    }
+    ~MixedCall()
+    {
+        h263mi_mixed_destroy(m);
+        for (void *p : bufs) CHECK(h263mi_device_free(0, p) == H263MI_OK);
+    }
+    struct Pick { int corpus; uint32_t frame; };
+    int call(const std::vector<Pick> &pick, std::vector<int> &rcs, std::vector<size_t> &used)
+    {
+        const size_t n = bufs.size();
+        std::vector<const uint8_t *> data(n, nullptr);
+        std::vector<size_t> len(n, 0);
+        rcs.assign(n, -1);
+        used.assign(n, 99);
+        for (size_t s = 0; s < n && s < pick.size(); s++) {
+            if (!pick[s].corpus) continue;
+            const auto &c = pick[s].corpus == 1 ? g_corpus : g_corpus2;
+            const std::vector<uint8_t> &p = c[s % c.size()][pick[s].frame % c[0].size()];
+            data[s] = p.data();
+            len[s] = p.size();
+        }
+        return h263mi_mixed_decode_next_pictures_ps(m, H263MI_SORENSON_SPARK_BITSTREAM, data.data(), len.data(), used.data(), 2, rcs.data(),
+                                                    H263MI_STRENGTH_FROM_HEADER, nullptr, (uint8_t *const *)bufs.data(), caps.data(), nullptr);
+    }
+    // per stream: (rc, width, height) of h263mi_mixed_stream_size
+    std::vector<uint64_t> sizes() const
+    {
+        std::vector<uint64_t> v;
+        for (uint32_t s = 0; s < bufs.size(); s++) {
+            uint16_t w = 0, h = 0;
+            v.push_back((uint64_t)(int64_t)h263mi_mixed_stream_size(m, s, &w, &h));
+            v.push_back(w);
+            v.push_back(h);
+        }
+        return v;
+    }
+};
+
+// A mixed-size set over both corpora: streams move between the two classes at key frames, a P picture of the other size is
+// refused and leaves the stream as it was, a class doubles when streams join a full one, and the sync that finds a class at most
+// a quarter full shrinks it.  (slots_bytes: a class of k slots holds 2k frames of its size.)
+static void drive_mixed_sizes(bool pipeline)
+{
+    const uint32_t n = 8;
+    MixedCall mc(n, pipeline);
+    if (!mc.m) return;
+    typedef MixedCall::Pick Pick;
+    std::vector<int> rcs;
+    std::vector<size_t> used;
+    std::vector<uint32_t> next(n, 0);
+    // every stream in `streams` sends its next picture of `corpus` (frame 0: a key frame); all must decode
+    auto step = [&](std::initializer_list<uint32_t> streams, int corpus) {
+        std::vector<Pick> pick(n, Pick{0, 0});
+        for (uint32_t s : streams) pick[s] = Pick{corpus, next[s]};
+        CHECK(mc.call(pick, rcs, used) == H263MI_OK);
+        for (uint32_t s : streams) {
+            CHECK(rcs[s] == H263MI_OK && used[s] > 0);
+            next[s]++;
+        }
+    };
+    auto size_is = [&](uint32_t s, uint16_t w, uint16_t h) {
+        uint16_t sw = 0, sh = 0;
+        CHECK(h263mi_mixed_stream_size(mc.m, s, &sw, &sh) == H263MI_OK && sw == w && sh == h);
+    };
+    step({0, 1}, 1);                                             // a class of the first size: 2 slots
+    CHECK(h263mi_mixed_size_classes(mc.m) == 1);
+    const uint64_t two = h263mi_mixed_frame_store_bytes(mc.m);
+    CHECK(two > 0);
+    step({2, 3}, 1);                                             // two join a full class: 4 slots
+    CHECK(h263mi_mixed_frame_store_bytes(mc.m) == 2 * two);
+    step({0, 1, 2, 3, 4, 5, 6, 7}, 1);                           // four more: 8 slots
+    CHECK(h263mi_mixed_frame_store_bytes(mc.m) == 4 * two);
+    for (uint32_t s = 0; s < n; s++) size_is(s, g_w, g_h);
+    // a P picture of the other size: refused, nothing consumed, the stream keeps its size (and its picture)
+    {
+        std::vector<Pick> pick(n, Pick{0, 0});
+        pick[0] = Pick{2, 1};
+        pick[1] = Pick{1, next[1]};
+        CHECK(mc.call(pick, rcs, used) == H263MI_OK);
+        CHECK(rcs[0] == H263MI_ERR_PICTURE_FORMAT_INVALID && used[0] == 0);
+        CHECK(rcs[1] == H263MI_OK && used[1] > 0);
+        next[1]++;
+        size_is(0, g_w, g_h);
+    }
+    // seven streams move to the second size at a key frame: a class of 8 slots for them; the first class keeps 1 member in 8 slots
+    for (uint32_t s = 0; s < n; s++)
+        if (s != 1) next[s] = 0;
+    step({0, 2, 3, 4, 5, 6, 7}, 2);
+    const uint64_t before_shrink = h263mi_mixed_frame_store_bytes(mc.m);
+    CHECK(h263mi_mixed_size_classes(mc.m) == 2);
+    CHECK(before_shrink > 4 * two);
+    size_is(0, g_w2, g_h2);
+    size_is(1, g_w, g_h);
+    // the sync finds the first class at most a quarter full and shrinks it to 1 slot
+    CHECK(h263mi_mixed_sync(mc.m, nullptr) == H263MI_OK);
+    CHECK(h263mi_mixed_size_classes(mc.m) == 2);
+    CHECK(h263mi_mixed_frame_store_bytes(mc.m) == before_shrink - 4 * two + two / 2);
+    for (uint32_t s = 0; s < n; s++) size_is(s, s == 1 ? g_w : g_w2, s == 1 ? g_h : g_h2);
+    // P pictures on both classes after the moves, then one stream back to the first size (its class grows to 2 slots)
+    step({1}, 1);
+    step({0, 2, 3, 4, 5, 6, 7}, 2);
+    const uint64_t before_grow = h263mi_mixed_frame_store_bytes(mc.m);
+    next[2] = 0;
+    step({2}, 1);
+    CHECK(h263mi_mixed_frame_store_bytes(mc.m) == before_grow + two / 2);
+    size_is(2, g_w, g_h);
+    step({1, 2}, 1);
+    step({0, 3, 4, 5, 6, 7}, 2);
+    CHECK(h263mi_mixed_sync(mc.m, nullptr) == H263MI_OK);
 }
 
 // one H263State fed coded pictures (h263mi_decode_next_picture: parse into the state's own staging slot), with the accessors
@@ -436,6 +571,63 @@ static void fault_sweep(const char *name, bool may_absorb, const std::function<S
     CHECK(!"the call never went through");
 }
 
+// h263mi_debug_fail_nth_hip_call at every HIP call of a mixed-size set's call, each time on a set made afresh: 3 streams, two of
+// the first size and one of the second; in the swept call stream 1 moves to the second size (that class grows).  A failed class
+// launch is reported in stream_rc and the call itself may return OK; a failed rendering is the call's error after the pictures
+// were decoded.  So what holds at every point is what tests/test_gpu_round5.py checks on the device: a stream reports OK exactly
+// when it consumed its picture, a stream with an error keeps its size and picture, a failure is reported somewhere, and a clean
+// call afterwards goes through and leaves the classes as large as a run without the failure does.
+static void mixed_fault_sweep(bool pipeline)
+{
+    typedef MixedCall::Pick Pick;
+    const std::vector<Pick> keys = {{1, 0}, {1, 0}, {2, 0}}, swept = {{1, 1}, {2, 0}, {2, 1}};
+    uint64_t clean_bytes = 0;                    // the frame stores after the two calls without a failure
+    {
+        MixedCall mc(3, pipeline);
+        std::vector<int> rcs;
+        std::vector<size_t> used;
+        CHECK(mc.call(keys, rcs, used) == H263MI_OK && mc.call(swept, rcs, used) == H263MI_OK);
+        CHECK(h263mi_mixed_sync(mc.m, nullptr) == H263MI_OK);
+        clean_bytes = h263mi_mixed_frame_store_bytes(mc.m);
+    }
+    int failures = 0;
+    for (int nth = 1; nth < 500; nth++) {
+        MixedCall mc(3, pipeline);
+        if (!mc.m) return;
+        std::vector<int> rcs;
+        std::vector<size_t> used;
+        CHECK(mc.call(keys, rcs, used) == H263MI_OK && rcs == std::vector<int>(3, H263MI_OK));
+        CHECK(h263mi_mixed_sync(mc.m, nullptr) == H263MI_OK);
+        const std::vector<uint64_t> before = mc.sizes();
+        h263mi_debug_fail_nth_hip_call(nth);
+        const int rc = mc.call(swept, rcs, used);
+        const bool fired = h263mi_debug_fail_nth_hip_call(0) <= 0;
+        const std::vector<uint64_t> after = mc.sizes();
+        bool any_rc = false;
+        for (size_t s = 0; s < 3; s++) {
+            CHECK((rcs[s] == H263MI_OK) == (used[s] > 0));
+            if (rcs[s] != H263MI_OK) {
+                any_rc = true;
+                CHECK(std::equal(after.begin() + 3 * s, after.begin() + 3 * s + 3, before.begin() + 3 * s));
+            }
+        }
+        if (!fired) {
+            CHECK(rc == H263MI_OK && !any_rc);
+            fprintf(stderr, "  fault sweep h263mi_mixed_decode_next_pictures_ps (pipeline %d): %d failures\n", (int)pipeline, failures);
+            CHECK(failures >= 8);
+            return;
+        }
+        failures++;
+        CHECK(rc != H263MI_OK || any_rc);
+        // the same pictures once more, without a failure: every stream decodes (the ones that advanced predict from them again),
+        // and the classes hold what they would have without the failure (a joiner whose launch failed gave its new slot back)
+        CHECK(mc.call(swept, rcs, used) == H263MI_OK && rcs == std::vector<int>(3, H263MI_OK));
+        CHECK(h263mi_mixed_sync(mc.m, nullptr) == H263MI_OK);
+        CHECK(h263mi_mixed_frame_store_bytes(mc.m) == clean_bytes);
+    }
+    CHECK(!"the mixed-size call never went through");
+}
+
 static void drive_fault_sweeps()
 {
     const long live0 = stub_live_allocations();
@@ -495,6 +687,41 @@ static void drive_fault_sweeps()
         }
     };
     fault_sweep("h263mi_batch_submit_host (2 streams)", false, [] { return new Batch(); });
+    // the bitstream entry of a batch: 2 streams, P pictures behind their key frames, rendered with the headers' strengths
+    struct BatchBitstream : SweepSubject {
+        h263mi_batch *b = nullptr;
+        void *d_rgba = nullptr;
+        BatchBitstream()
+        {
+            h263mi_backend_cfg cfg{0, 0, nullptr};
+            CHECK(h263mi_batch_create(2, g_w, g_h, &cfg, &b) == H263MI_OK);
+            CHECK(h263mi_device_malloc(0, (size_t)2 * g_w * g_h * 4, &d_rgba) == H263MI_OK);
+            CHECK(decode(0) == H263MI_OK);
+            CHECK(h263mi_batch_sync(b) == H263MI_OK);
+        }
+        ~BatchBitstream()
+        {
+            h263mi_batch_destroy(b);
+            CHECK(h263mi_device_free(0, d_rgba) == H263MI_OK);
+        }
+        int decode(uint32_t frame)
+        {
+            const uint8_t *data[2] = {g_corpus[0][frame].data(), g_corpus[1][frame].data()};
+            const size_t len[2] = {g_corpus[0][frame].size(), g_corpus[1][frame].size()};
+            size_t used[2] = {0, 0};
+            int rcs[2] = {-1, -1};
+            return h263mi_batch_decode_next_pictures_ps(b, H263MI_SORENSON_SPARK_BITSTREAM, data, len, used, 2, rcs,
+                                                        H263MI_STRENGTH_FROM_HEADER, nullptr, (uint8_t *)d_rgba, nullptr);
+        }
+        int call() override { return decode(1); }
+        std::vector<uint64_t> view() override
+        {
+            return {(uint64_t)h263mi_batch_stream_has_picture(b, 0), (uint64_t)h263mi_batch_stream_has_picture(b, 1)};
+        }
+    };
+    fault_sweep("h263mi_batch_decode_next_pictures_ps (2 streams)", false, [] { return new BatchBitstream(); });
+    if (!g_corpus2.empty())
+        for (bool pipeline : {false, true}) mixed_fault_sweep(pipeline);
     // every pinned and device block and every event of the objects above went with them
     CHECK(stub_live_allocations() == live0);
     CHECK(live0 == 0);
@@ -625,8 +852,8 @@ static void drive_state_precedence()
 
 int main(int argc, char **argv)
 {
-    if (argc < 2 || !load_corpus(argv[1])) {
-        fprintf(stderr, "usage: tsan_driver <corpus.bin> [rounds]\n");
+    if (argc < 2 || !load_corpus(argv[1], g_corpus, g_w, g_h) || (argc > 4 && !load_corpus(argv[4], g_corpus2, g_w2, g_h2))) {
+        fprintf(stderr, "usage: tsan_driver <corpus.bin> [rounds [max threads [corpus of another size.bin]]]\n");
         return 2;
     }
     const int rounds = argc > 2 ? atoi(argv[2]) : 2;
@@ -636,6 +863,8 @@ int main(int argc, char **argv)
     drive_state_precedence();
     drive_device_arrays();
     drive_host_garbage(900, 400);
+    if (!g_corpus2.empty())
+        for (bool pipeline : {false, true}) drive_mixed_sizes(pipeline);
     for (int r = 0; r < rounds; r++) {
         // one batch after the other: spinning and parking plans, teardown parked and mid-spin
         drive_batch(100 + r, n, 40, /*pipeline=*/true, /*destroy_mid_spin=*/false);
