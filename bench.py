@@ -11,13 +11,18 @@ starts.  With --gpus N every rank decodes its own 64 streams (weak scaling, no d
 carries the barrier and the max-over-ranks reduction.  `python bench.py --gpus N` launches the N ranks itself
 (torch.distributed.run); under an external launcher (WORLD_SIZE set) it is one of the ranks.
 
-After the timed region, and outside it, a PARITY GATE downloads the last picture (Y, Cb, Cr and RGBA) of streams
-0, 31 and 63 of the 64-stream batch and compares it with the CPU oracle run from the GOP's I picture; a mismatch
-makes the run fail.
+A plain run sets up, warms up, times the steps, writes --dump-outputs if asked and prints the line: nothing else.
+Everything else the benchmark measures or checks runs with --full (each part can be left out there with its --no-*
+option):
+  * a PARITY GATE after the timed region, and outside it: the last picture (Y, Cb, Cr and RGBA) of streams 0, 31 and
+    63 of the 64-stream batch is compared with the CPU oracle run from the GOP's I picture; a mismatch makes the run fail;
+  * the box's copy / read / write ceilings (roofline.peak_measured*, bound_observed) and roofline.trusted_mode;
+  * the `extra` legs (dense transport, dense I pictures, sustained, end to end from bitstreams, latencies);
+  * `cpu_baseline`: the C oracle (a port of the reference CPU path, not the Rust binary) built natively on this box
+    (-O3 -march=native -ffp-contract=off) and timed on its host cores with one stream per thread.
 
-One JSON line is printed by rank 0.  `roofline` is for the kernel with the larger share of the timed region;
-`cpu_baseline` is the C oracle (a port of the reference CPU path, not the Rust binary) built natively on this box
-(-O3 -march=native -ffp-contract=off) and timed on its host cores with one stream per thread.
+One JSON line is printed by rank 0.  `roofline` is for the kernel with the larger share of the timed region; its launch
+times are the HIP events of the timed steps themselves, so a plain run reports them too.
 """
 import argparse
 import hashlib
@@ -58,12 +63,17 @@ def parse_args(argv=None):
                          "the GPUs; 0 = off (weak scaling, --streams per GPU)")
     ap.add_argument("--gop", type=int, default=GOP)
     ap.add_argument("--gops-per-step", type=int, default=GOPS_PER_STEP)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the parity gate, the measured ceilings, the extra legs and the CPU "
+                         "baseline (the --no-* options below leave parts of that out)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline object")
     ap.add_argument("--cpu-baseline-only", action="store_true", help="print the cpu_baseline object and exit (no GPU needed)")
-    ap.add_argument("--no-extra", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the extra.e2e_bitstream* legs")
-    ap.add_argument("--sustained-seconds", type=float, default=10.0, help="length of extra.sustained (the headline loop, >= 10 s)")
-    ap.add_argument("--no-parity-gate", action="store_true", help="profiling runs only: the line then says so")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the extra legs and roofline.trusted_mode")
+    ap.add_argument("--no-e2e", action="store_true", help="--full without the extra.e2e_bitstream* legs")
+    ap.add_argument("--sustained-seconds", type=float, default=10.0,
+                    help="--full: length of extra.sustained (the headline loop, >= 10 s)")
+    ap.add_argument("--no-parity-gate", action="store_true", help="--full without the parity gate (profiling runs only: "
+                                                                   "the line then says so)")
     ap.add_argument("--dense-coeffs", action="store_true",
                     help="coefficients as dense 128-byte blocks in HBM (h263mi_batch_decode) instead of the sparse events the "
                          "host parser emits (h263mi_batch_decode_events)")
@@ -859,6 +869,7 @@ def main(argv=None):
     assert len(my_streams) == n and all(my_streams[k] == my_streams[0] + k * stride for k in range(n))
     pipeline = not args.no_pipeline and not args.overlap
     use_events = pipeline and not args.dense_coeffs
+    extras = args.full and not args.no_extra        # the legs after the headline (a plain run stops at the line)
     wl = Workload(h263mi, n, args.gop, my_streams[0], local_rank, stream, events=use_events, stream_stride=stride)
     batch = h263mi.Batch(n, W, H, local_rank, stream, overlap_post=args.overlap, pipeline_post=pipeline)
     d_rgba = h263mi.DeviceBuffer(n * RGBA_BYTES, local_rank)
@@ -881,17 +892,19 @@ def main(argv=None):
     pictures = shard.aggregate_pictures(dist, n * frames_per_step * args.steps)
     value = pictures * MP_PER_PICTURE / elapsed
 
-    # ---- parity gate (outside the timed region): every rank checks its own streams; any failure fails the job
-    gate, gate_streams = ("skipped", [])
-    if not args.no_parity_gate:
-        gate, gate_streams = parity_gate(h263mi, batch, d_rgba, my_streams[0], n, args.gop, stream_stride=stride)
-    gate_bad = 0 if gate in ("ok", "skipped") else 1
-    if dist is not None:
-        t = torch.tensor([gate_bad], dtype=torch.int32, device="cuda")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        gate_bad = int(t.item())
-    if gate_bad and gate == "ok":
-        gate = "failed on another rank"
+    # ---- parity gate (--full, outside the timed region): every rank checks its own streams; any failure fails the job
+    gate, gate_streams, gate_bad = ("not run (--full runs it)", [], 0)
+    if args.full:
+        gate = "skipped"
+        if not args.no_parity_gate:
+            gate, gate_streams = parity_gate(h263mi, batch, d_rgba, my_streams[0], n, args.gop, stream_stride=stride)
+        gate_bad = 0 if gate in ("ok", "skipped") else 1
+        if dist is not None:
+            t = torch.tensor([gate_bad], dtype=torch.int32, device="cuda")
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            gate_bad = int(t.item())
+        if gate_bad and gate == "ok":
+            gate = "failed on another rank"
 
     # ---- what the last timed step computed, before any later leg reuses the batch
     dumped = None
@@ -918,12 +931,6 @@ def main(argv=None):
     spent = {"k_recon": kt.recon_ms, "k_post": kt.post_ms, "k_frame": kt.frame_ms}
     dom = max(spent, key=spent.get)
 
-    # on-box ceilings, measured in this run: plain copy / read / write kernels over 1 GiB
-    cfg_stream = stream
-    peak_copy, copy_shape = h263mi.probe_bandwidth(h263mi.PROBE_COPY, 1 << 30, 10, local_rank, cfg_stream, True)
-    peak_read, read_shape = h263mi.probe_bandwidth(h263mi.PROBE_READ, 1 << 30, 10, local_rank, cfg_stream, True)
-    peak_write, write_shape = h263mi.probe_bandwidth(h263mi.PROBE_WRITE, 1 << 30, 10, local_rank, cfg_stream, True)
-
     # HBM traffic of that kernel: FETCH_SIZE + WRITE_SIZE from the separate rocprofv3 --pmc passes of
     # tools/prof_final.sh, committed under profiles/.  It cannot be measured from inside this process, so it is
     # reported only when the committed figure was taken on exactly this kernel source.
@@ -940,26 +947,12 @@ def main(argv=None):
     except Exception:
         traffic_source = "profiles/traffic_latest.json missing"
     ach = kernels[dom]["achieved_gbs"]
-    # A ceiling that knows the kernel's mix of reads and writes: on this part a stream of reads and a stream of writes
-    # take as long together as one after the other (copy of 1 GiB = read of 1 GiB + write of 1 GiB, in time, within
-    # 3 %), and writes are the slower of the two.  The time the ALGORITHMIC bytes of the dominant kernel need at the
-    # read-only and write-only rates measured in this run, and the rate that corresponds to.
-    alg_w = {"k_recon": wl.recon_write_bytes(), "k_post": post_alg, "k_frame": wl.recon_write_bytes() + post_alg}[dom]
-    alg_r = kernels[dom]["alg_bytes_per_launch"] - alg_w
-    mix_ms = (alg_r / (peak_read * 1e9) + alg_w / (peak_write * 1e9)) * 1e3 if peak_read and peak_write else 0.0
-    peak_mix = kernels[dom]["alg_bytes_per_launch"] / (mix_ms * 1e-3) / 1e9 if mix_ms else 0.0
     roofline = {"bound": "hbm", "kernel": dom, "achieved": round(ach, 1),
                 "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 4),
                 "traffic": traffic, "traffic_source": traffic_source,
-                "peak_measured": round(peak_copy, 1), "frac_measured": round(ach / peak_copy, 4) if peak_copy else None,
-                "peak_measured_what": "copy kernel (read + write counted) over 1 GiB on this device, in this run: the fastest of "
-                                      "the tuned launch shapes (%s) -- the MI355X guide's 6.29 TB/s float4 copy is what this "
-                                      "probe is held against; read-only %.0f GB/s (%s), write-only %.0f GB/s (%s)"
-                                      % (copy_shape, peak_read, read_shape, peak_write, write_shape),
-                "peak_measured_mix": round(peak_mix, 1), "frac_measured_mix": round(ach / peak_mix, 4) if peak_mix else None,
-                "peak_measured_mix_what": "algorithmic bytes / (bytes read / measured read-only rate + bytes written / "
-                                          "measured write-only rate): %.0f MB read, %.0f MB written per launch, %.3f ms"
-                                          % (alg_r / 1e6, alg_w / 1e6, mix_ms),
+                # the box's own ceilings take runs of their own: --full only (filled in below)
+                "peak_measured": None, "frac_measured": None, "peak_measured_what": None,
+                "peak_measured_mix": None, "frac_measured_mix": None, "peak_measured_mix_what": None,
                 "avg_launch_ms": round(kernels[dom]["avg_ms"], 4),
                 "alg_bytes_per_launch": int(kernels[dom]["alg_bytes_per_launch"]),
                 "alg_bytes_what": "bytes the coefficient transport that ran really moves (events: 4 B per coded block of index + 4 B "
@@ -979,6 +972,30 @@ def main(argv=None):
                                 "alg_bytes_per_launch": int(v["alg_bytes_per_launch"]),
                                 "achieved_gbs": round(v["achieved_gbs"], 1)} for k, v in kernels.items()},
                 "k_recon_p_alg_bytes_per_launch": int(recon_alg_p)}
+    peak_copy = None
+    if args.full:
+        # on-box ceilings, measured in this run: plain copy / read / write kernels over 1 GiB
+        peak_copy, copy_shape = h263mi.probe_bandwidth(h263mi.PROBE_COPY, 1 << 30, 10, local_rank, stream, True)
+        peak_read, read_shape = h263mi.probe_bandwidth(h263mi.PROBE_READ, 1 << 30, 10, local_rank, stream, True)
+        peak_write, write_shape = h263mi.probe_bandwidth(h263mi.PROBE_WRITE, 1 << 30, 10, local_rank, stream, True)
+        # A ceiling that knows the kernel's mix of reads and writes: on this part a stream of reads and a stream of writes
+        # take as long together as one after the other (copy of 1 GiB = read of 1 GiB + write of 1 GiB, in time, within
+        # 3 %), and writes are the slower of the two.  The time the ALGORITHMIC bytes of the dominant kernel need at the
+        # read-only and write-only rates measured in this run, and the rate that corresponds to.
+        alg_w = {"k_recon": wl.recon_write_bytes(), "k_post": post_alg, "k_frame": wl.recon_write_bytes() + post_alg}[dom]
+        alg_r = kernels[dom]["alg_bytes_per_launch"] - alg_w
+        mix_ms = (alg_r / (peak_read * 1e9) + alg_w / (peak_write * 1e9)) * 1e3 if peak_read and peak_write else 0.0
+        peak_mix = kernels[dom]["alg_bytes_per_launch"] / (mix_ms * 1e-3) / 1e9 if mix_ms else 0.0
+        roofline.update({
+            "peak_measured": round(peak_copy, 1), "frac_measured": round(ach / peak_copy, 4) if peak_copy else None,
+            "peak_measured_what": "copy kernel (read + write counted) over 1 GiB on this device, in this run: the fastest of "
+                                  "the tuned launch shapes (%s) -- the MI355X guide's 6.29 TB/s float4 copy is what this "
+                                  "probe is held against; read-only %.0f GB/s (%s), write-only %.0f GB/s (%s)"
+                                  % (copy_shape, peak_read, read_shape, peak_write, write_shape),
+            "peak_measured_mix": round(peak_mix, 1), "frac_measured_mix": round(ach / peak_mix, 4) if peak_mix else None,
+            "peak_measured_mix_what": "algorithmic bytes / (bytes read / measured read-only rate + bytes written / "
+                                      "measured write-only rate): %.0f MB read, %.0f MB written per launch, %.3f ms"
+                                      % (alg_r / 1e6, alg_w / 1e6, mix_ms)})
     # What bounds the launch in fact: the vector ALUs' issue slots, not HBM.  From the committed PMC passes of
     # tools/prof_final.sh over exactly these kernel sources (hash-tied like `traffic`): vector instructions per launch, the
     # lane operations that is per output pixel, the share of the launch's cycles the vector ALUs were busy -- and the time
@@ -996,7 +1013,8 @@ def main(argv=None):
                                       "tools/prof_final.sh, %s, kernel sources %s): mean over the launches of the profiled GOPs; "
                                       "alu_time_ms = busy_frac x this run's avg_launch_ms; hbm_busy_frac = achieved / this box's copy "
                                       "ceiling" % (tr.get("tag", "?"), tr["kernel_source_hash"])}
-        roofline["bound_observed"] = "valu" if (peak_copy and busy > ach / peak_copy) else "hbm"
+        # (without --full there is no copy ceiling to hold `achieved` against)
+        roofline["bound_observed"] = ("valu" if busy > ach / peak_copy else "hbm") if peak_copy else None
     else:
         roofline["valu"] = None
         roofline["bound_observed"] = None
@@ -1011,7 +1029,7 @@ def main(argv=None):
         torch.cuda.synchronize()
         return (time.perf_counter() - t1) / n_frames * 1e3
 
-    if not args.no_extra and pipeline:
+    if extras and pipeline:
         # The timed region runs CHECKED (ABI 7: the default): every call says how large its arrays are and the waves
         # bounds-check every coded block and event list they read -- the path real streams take.  What the opt-out would buy
         # (H263MI_CFG_TRUSTED_ARRAYS: the caller vouches, the waves check nothing): the same frames on a second batch made that
@@ -1035,7 +1053,7 @@ def main(argv=None):
     extra = {}
     # (the extra legs run on EVERY rank -- each on its own GPU and its own share of the host -- so that no rank sits in a
     # collective while another measures; rank 0 reports its own figures, the end-to-end leg the sum over the ranks)
-    if not args.no_extra and use_events:
+    if extras and use_events:
         # the same workload with the coefficients as dense 128-byte blocks in HBM (round 1-2's transport)
         wld = Workload(h263mi, n, args.gop, my_streams[0], local_rank, stream, events=False, stream_stride=stride)
         run_frames(batch, wld, d_rgba, args.gop, pipeline)
@@ -1056,7 +1074,7 @@ def main(argv=None):
             for k in ("mbs", "co", "base"):
                 fr[k].free()
         del wld
-    if not args.no_extra:
+    if extras:
         # BASELINE configs[1]: dense 1080p I pictures (every block Full): dequant + IDCT + YUV->RGBA, no deblock
         del wl
         dense = Workload(h263mi, n, 1, 0, local_rank, stream, i_kind=h263mi.SYNTH_I_DENSE, p_frames=False)
@@ -1109,7 +1127,7 @@ def main(argv=None):
                         "128 B per coded block + planes + RGBA written" % (n, reps)}
     roofline.setdefault("config2_dense_i", None)
 
-    if not args.no_extra and rank == 0 and world == 1 and pipeline:
+    if extras and rank == 0 and world == 1 and pipeline:
         # (needs the workload `wl`, which the dense-I leg above has freed: made again here, 2 GB)
         wl2 = Workload(h263mi, n, args.gop, my_streams[0], local_rank, stream, events=use_events, stream_stride=stride)
         try:
@@ -1125,7 +1143,7 @@ def main(argv=None):
         del wl2
 
     e2e_bad = 0
-    if not args.no_extra and not args.no_e2e:
+    if extras and not args.no_e2e:
         # every rank runs its own 64 streams end to end, on ITS share of the container's CPUs, all at the same time
         # ... as many parser threads as the LIBRARY chooses for that share (h263mi_default_parser_threads: under a CPU-time
         # quota more threads than the quota has CPUs, parked the moment they run out of work -- include/h263mi.h)
@@ -1191,18 +1209,19 @@ def main(argv=None):
         "ms_per_frame_index": round(elapsed / max(args.steps * frames_per_step, 1) * 1e3, 4),
         "realtime_1080p30_streams": round(value / (MP_PER_PICTURE * 30), 1),
         "parity_gate": gate, "parity_gate_streams": gate_streams,
-        "e2e_parity": None if (args.no_extra or args.no_e2e) else ("MISMATCH" if e2e_bad else "ok"),
+        "e2e_parity": None if (not extras or args.no_e2e) else ("MISMATCH" if e2e_bad else "ok"),
         "roofline": roofline,
     }
     if extra:
         out["extra"] = extra
     if dumped is not None:
         out["dumped_outputs"] = dumped
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(h263mi)
     elif rank == 0:
-        # N > 1: the CPU baseline is a property of the box, not of the job; it is timed at N = 1 only (there the host is
-        # idle beside it -- with N ranks their threads would compete with its `cores` threads)
+        # a plain run times the GPU only.  N > 1: the CPU baseline is a property of the box, not of the job; it is timed
+        # at N = 1 only (there the host is idle beside it -- with N ranks their threads would compete with its `cores`
+        # threads)
         out["cpu_baseline"] = None
     if rank == 0:
         print(json.dumps(out), flush=True)

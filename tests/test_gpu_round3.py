@@ -291,14 +291,17 @@ def test_every_reachable_inter_dc_value_over_prediction(pred):
 # the RCCL leg of bench.py in a driver-run record: one rank, process group "nccl" (= RCCL) forced on, the barrier, the
 # max-over-ranks reduction of the elapsed time, the sum of the pictures and the parity-gate verdict all go through it
 # ---------------------------------------------------------------------------------------------
-def _bench_child(extra_args, extra_env):
+def _bench_child(extra_args, extra_env, full=True):
+    """full: --full without the extra legs and the CPU baseline (the parity gate and the measured ceilings run)"""
     env = dict(os.environ)
     env.update(extra_env)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     env["MASTER_ADDR"] = "127.0.0.1"
     env["MASTER_PORT"] = "29533"
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-extra",
-           "--no-cpu-baseline"] + extra_args
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1"]
+    if full:
+        cmd += ["--full", "--no-extra", "--no-cpu-baseline"]
+    cmd += extra_args
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     return json.loads(r.stdout.strip().splitlines()[-1])
@@ -315,6 +318,18 @@ def test_bench_rccl_leg_strong_scaling_form():
     out = _bench_child(["--total-streams", "64"], {"H263MI_FORCE_DIST": "1"})
     assert out["parity_gate"] == "ok" and out["n_gpus"] == 1 and out["scaling"] == "strong"
     assert out["config"]["streams_per_gpu"] == 64 and out["config"]["pictures_per_step"] == 64 * 124
+
+
+def test_plain_bench_run_is_the_headline_alone():
+    """without --full the line carries the headline and the launch times of its own timed steps, and nothing that takes a
+    run of its own: no parity gate, no measured ceilings, no extra legs, no CPU baseline"""
+    out = _bench_child([], {}, full=False)
+    assert out["value"] > 1000.0 and out["unit"] == "MP/s" and out["higher_is_better"] is True
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["ms_per_step"] > 0
+    assert out["parity_gate"] == "not run (--full runs it)" and out["e2e_parity"] is None
+    assert "extra" not in out and out["cpu_baseline"] is None
+    assert out["roofline"]["kernel"] == "k_frame" and out["roofline"]["achieved"] > 0
+    assert out["roofline"]["peak_measured"] is None and out["roofline"]["trusted_mode"] is None
 
 
 # ---------------------------------------------------------------------------------------------

@@ -2,7 +2,7 @@
 # Evidence for profiles/ from ONE lease of one GPU box (profiles and bench lines from different
 # boxes cannot be compared; every file is stamped with this box's measured copy ceiling):
 #   box.txt                      the box's copy / read / write ceilings (tools/probes/ceiling.hip, the tuned shapes)
-#   bench.json                   the default `python bench.py` line (unprofiled), which reads traffic.json
+#   bench.json                   the `python bench.py --full` line (unprofiled), which reads traffic.json
 #   bench_under_rocprof.json + trace/   rocprofv3 --kernel-trace --stats of the same command
 #   traffic.json                 FETCH_SIZE / WRITE_SIZE PMC passes (counters only, separate runs)
 #   pmc_summary.txt              SQ / TCC / TCP counters of k_frame (tools/prof_pmc.sh groups)
@@ -20,8 +20,8 @@ cd /tmp && export TMPDIR=/tmp
 STAMP="box: $(grep 'BEST copy' $OUT/box.txt | awk '{print $3" GB/s copy ceiling"}'), $(hostname), $(date -u +%Y-%m-%dT%H:%MZ)"
 echo "$STAMP" >> $OUT/box.txt
 echo "== $STAMP"
-# ---- kernel trace of the default bench command
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py --no-cpu-baseline --no-extra > $OUT/bench_under_rocprof.json 2> $OUT/trace.log
+# ---- kernel trace of the bench command with its parity gate and measured ceilings (no extra legs)
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py --full --no-cpu-baseline --no-extra > $OUT/bench_under_rocprof.json 2> $OUT/trace.log
 # ---- HBM traffic: two counter-only passes
 for C in FETCH_SIZE WRITE_SIZE; do
   timeout 600 rocprofv3 --pmc $C --output-format csv -d $OUT/pmc_$C -- python3 $R/bench.py $PROF_ARGS > /dev/null 2> $OUT/pmc_$C.log
@@ -99,8 +99,8 @@ print(json.dumps(traffic))
 PY
 # the bench line below reports this traffic: same kernel sources, same box
 cp $OUT/traffic.json profiles/traffic_latest.json
-# ---- the default bench line, unprofiled (what the driver runs)
-timeout 1200 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err
+# ---- the full bench line, unprofiled
+timeout 1200 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 # ---- SQ / TCC / TCP counters of the launch
 bash tools/prof_pmc.sh final_${TAG}_pmc > /dev/null 2>&1
 cp gpurun_out/final_${TAG}_pmc/summary_table.txt $OUT/pmc_summary.txt 2>/dev/null

@@ -1,4 +1,4 @@
-"""One-screen summary of a bench.py line: python tools/sum_bench.py <file with the JSON line>"""
+"""One-screen summary of a `bench.py --full` line: python tools/sum_bench.py <file with the JSON line>"""
 import json,sys
 d=json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][0])
 print(d["value"], d["roofline"]["frac"], d["roofline"]["peak_measured"])
