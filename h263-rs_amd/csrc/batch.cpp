@@ -53,6 +53,46 @@ bool h263mi_batch::layout_ptrs(uint8_t *d_rgba, std::vector<uint8_t *> &ptrs) co
     return true;
 }
 
+h263mi_resize_scratch::~h263mi_resize_scratch()
+{
+    DeviceGuard g(device);
+    if (rgba) (void)hipFree(rgba);
+    if (spans) (void)hipFree(spans);
+}
+
+int h263mi_batch::resize_dst(const std::vector<int8_t> &sets, uint8_t *d_rgba, uint8_t *const *host_ptrs, hipStream_t on,
+                             uint8_t *const **d_out)
+{
+    std::vector<uint8_t *> p(n, nullptr);
+    for (uint32_t i = 0; i < n; i++)
+        if (sets[i] >= 0) p[i] = host_ptrs ? host_ptrs[i] : d_rgba + layout.offsets[i];
+    return upload(ptr_ring, p.data(), d_out, on);
+}
+
+int h263mi_batch::launch_resize(const RgbaLayout::Resize &rz, const std::vector<int8_t> &sets, uint8_t *const *d_dst, hipStream_t on)
+{
+    bool any = false;
+    for (int8_t v : sets) any = any || v >= 0;
+    if (!any) return H263MI_OK;
+    ResizeArgs a{};
+    a.src = rz.scratch->rgba;
+    a.dst = d_dst;
+    a.cols = rz.scratch->spans;
+    a.rows = rz.scratch->spans + rz.ow;
+    a.w = L.width;
+    a.h = L.height;
+    a.ow = rz.ow;
+    a.oh = rz.oh;
+    a.pitch = rz.pitch;
+    a.d = L.width * L.height;
+    a.inv_d = 1.0f / (float)a.d;
+    a.n_pictures = n;
+    if (!launch_rgba_resize) return H263MI_ERR_HIP;        // (kernels.h: only a stub runtime lacks it)
+    RC_TRY(time_begin(3, on));
+    HIP_TRY(launch_rgba_resize(a, on));
+    return H263MI_OK;
+}
+
 bool h263mi_batch::any_picture() const
 {
     for (const StreamState &t : ss)
@@ -136,16 +176,17 @@ int h263mi_batch::time_close()
     if (chain_kernel < 0) return H263MI_OK;
     const int k = chain_kernel;
     chain_kernel = -1;
-    HIP_TRY(hipEventRecord(ev_pool[ev_used + 1], stream_of(k)));
+    HIP_TRY(hipEventRecord(ev_pool[ev_used + 1], chain_on));
     ev_ranges.push_back(TimedChain{ev_used, k, chain_launches});
     ev_used += 2;
     return H263MI_OK;
 }
 
-int h263mi_batch::time_begin(int kernel_id)
+int h263mi_batch::time_begin(int kernel_id, hipStream_t on)
 {
     if (!timing) return H263MI_OK;
-    if (chain_kernel == kernel_id) {
+    if (!on) on = stream_of(kernel_id);
+    if (chain_kernel == kernel_id && chain_on == on) {
         chain_launches++;
         return H263MI_OK;
     }
@@ -157,8 +198,9 @@ int h263mi_batch::time_begin(int kernel_id)
             ev_pool.push_back(e);
         }
     }
-    HIP_TRY(hipEventRecord(ev_pool[ev_used], stream_of(kernel_id)));
+    HIP_TRY(hipEventRecord(ev_pool[ev_used], on));
     chain_kernel = kernel_id;
+    chain_on = on;
     chain_launches = 1;
     return H263MI_OK;
 }
@@ -243,6 +285,11 @@ int h263mi_batch::submit(uint8_t picture_type, const MbRecord *d_mbs, const h263
             return map_hip_error(e);
         }
         pending.valid = false;
+        if (pending.resize.on()) {           // the full-size pictures k_frame has just written into the scratch, resized
+            const RgbaLayout::Resize rz = std::move(pending.resize);
+            pending.resize = RgbaLayout::Resize();
+            RC_TRY(launch_resize(rz, pending.set, pending.resize_dst, stream));
+        }
     } else {
         RC_TRY(time_begin(0));
         HIP_TRY(launch_recon(a, stream, !words.empty() && words_inline ? words.data() : nullptr));
@@ -310,6 +357,21 @@ int h263mi_batch::note_pending(const Strengths &strength, uint8_t *d_rgba, uint8
 {
     pending.valid = false;
     pending.rgba_ptrs = nullptr;
+    pending.resize = RgbaLayout::Resize();
+    if (layout.resize.on() && (d_rgba || host_ptrs)) {
+        // a resize: the deferred rendering writes the full-size pictures into the scratch, k_rgba_resize follows it (the
+        // resize -- scratch, size, destinations -- is captured here, at the request)
+        for (uint32_t i = 0; i < n; i++)
+            pending.set[i] = (ss[i].active && (!host_ptrs || host_ptrs[i])) ? ss[i].cur : (int8_t)-1;
+        RC_TRY(resize_dst(pending.set, d_rgba, host_ptrs, stream, &pending.resize_dst));
+        pending.resize = layout.resize;
+        pending.out = OutLayout();
+        pending.valid = true;
+        pending.strength = strength;
+        pending.rgba = layout.resize.scratch->rgba;
+        pending.planes = d_planes;
+        return H263MI_OK;
+    }
     // (an output layout places each stream's picture through a per-stream pointer; the layout is captured here, at the request)
     std::vector<uint8_t *> placed;
     if (!host_ptrs && layout_ptrs(d_rgba, placed)) host_ptrs = placed.data();
@@ -328,15 +390,20 @@ int h263mi_batch::flush_pending()
 {
     if (!pending.valid) return H263MI_OK;
     pending.valid = false;
-    return launch_post_sets(pending.set, pending.strength, pending.rgba, pending.planes, stream, pending.rgba_ptrs, pending.out);
+    const RgbaLayout::Resize rz = std::move(pending.resize);
+    pending.resize = RgbaLayout::Resize();
+    RC_TRY(launch_post_sets(pending.set, pending.strength, pending.rgba, pending.planes, stream, pending.rgba_ptrs, pending.out));
+    return rz.on() ? launch_resize(rz, pending.set, pending.resize_dst, stream) : H263MI_OK;
 }
 
 int h263mi_batch::render(const Strengths &strength, uint8_t *d_rgba, uint8_t *d_planes, bool only_active, uint8_t *const *host_ptrs)
 {
     if (!any_picture()) return H263MI_ERR_NO_PICTURE;
     RC_TRY(flush_pending());
+    const RgbaLayout::Resize &rz = layout.resize;
+    const bool resized = rz.on() && (d_rgba || host_ptrs);
     std::vector<uint8_t *> placed;
-    if (!host_ptrs && layout_ptrs(d_rgba, placed)) host_ptrs = placed.data();
+    if (!resized && !host_ptrs && layout_ptrs(d_rgba, placed)) host_ptrs = placed.data();
     std::vector<int8_t> sets(n);
     bool reads[2] = {false, false};
     for (uint32_t i = 0; i < n; i++) {
@@ -345,8 +412,15 @@ int h263mi_batch::render(const Strengths &strength, uint8_t *d_rgba, uint8_t *d_
     }
     if (overlap_post) HIP_TRY(hipStreamWaitEvent(post_stream, ev_recon_done, 0));
     uint8_t *const *d_out_ptrs = nullptr;
-    if (host_ptrs) RC_TRY(upload(ptr_ring, host_ptrs, &d_out_ptrs, stream_of(1)));
-    RC_TRY(launch_post_sets(sets, strength, d_rgba, d_planes, stream_of(1), d_out_ptrs, layout.kernel));
+    if (resized) {
+        // full size into the scratch (the default kernels), then k_rgba_resize right behind it on the same stream
+        RC_TRY(resize_dst(sets, d_rgba, host_ptrs, stream_of(1), &d_out_ptrs));
+        RC_TRY(launch_post_sets(sets, strength, rz.scratch->rgba, d_planes, stream_of(1)));
+        RC_TRY(launch_resize(rz, sets, d_out_ptrs, stream_of(1)));
+    } else {
+        if (host_ptrs) RC_TRY(upload(ptr_ring, host_ptrs, &d_out_ptrs, stream_of(1)));
+        RC_TRY(launch_post_sets(sets, strength, d_rgba, d_planes, stream_of(1), d_out_ptrs, layout.kernel));
+    }
     // a later reconstruction may overwrite a frame set only when every post-processing that reads it is done: streams
     // that have drifted apart read both sets
     if (overlap_post)
@@ -620,6 +694,95 @@ int rgba_layout_extent(uint32_t n_streams, uint32_t w, uint32_t h, const h263mi_
     return H263MI_OK;
 }
 
+int rgba_resize_extent(uint32_t n_streams, const h263mi_rgba_resize *r, uint64_t *bytes)
+{
+    if (!r || !r->out_width || !r->out_height) return H263MI_ERR_INVALID_ARGUMENT;
+    for (uint8_t v : r->reserved)
+        if (v) return H263MI_ERR_INVALID_ARGUMENT;
+    // the rules of a layout: a full-size layout of a W' x H' picture has exactly the resize's shape
+    h263mi_rgba_layout lay{};
+    lay.row_pitch = r->row_pitch;
+    lay.offsets = r->offsets;
+    return rgba_layout_extent(n_streams, r->out_width, r->out_height, &lay, nullptr, nullptr, bytes);
+}
+
+bool resize_as_layout(uint32_t w, uint32_t h, const h263mi_rgba_resize &r, h263mi_rgba_layout *lay)
+{
+    int scale = -1;
+    for (int f = 0; f <= 2 && scale < 0; f++) {
+        const uint32_t m = (1u << f) - 1;
+        if (!(w & m) && !(h & m) && r.out_width == (w >> f) && r.out_height == (h >> f)) scale = f;
+    }
+    if (scale < 0) return false;
+    *lay = h263mi_rgba_layout{};
+    lay->scale_log2 = (uint8_t)scale;
+    lay->row_pitch = r.row_pitch;
+    lay->offsets = r.offsets;
+    return true;
+}
+
+// h263mi_batch_set_rgba_layout's shape for n streams of w x h
+static int layout_shape(uint32_t n, uint32_t w, uint32_t h, const h263mi_rgba_layout *layout, h263mi_batch::RgbaLayout &lay)
+{
+    uint32_t ow = 0, oh = 0;
+    RC_TRY(rgba_layout_extent(n, w, h, layout, &ow, &oh, &lay.bytes, &lay.kernel));
+    if (lay.placed()) {
+        lay.offsets.resize(n);
+        const uint64_t pitch = (layout->row_pitch ? layout->row_pitch : 4ull * ow);
+        for (uint32_t i = 0; i < n; i++) lay.offsets[i] = layout->offsets ? layout->offsets[i] : (uint64_t)i * oh * pitch;
+    }
+    return H263MI_OK;
+}
+
+uint64_t resize_scratch_bytes(uint32_t w, uint32_t h, uint32_t slots, const h263mi_rgba_resize &r)
+{
+    h263mi_rgba_layout lay;
+    if (resize_as_layout(w, h, r, &lay)) return 0;
+    return (uint64_t)slots * w * h * 4 + ((uint64_t)r.out_width + r.out_height) * sizeof(ResizeSpan);
+}
+
+int make_output_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_rgba_resize *r, h263mi_batch::RgbaLayout &out)
+{
+    h263mi_batch::RgbaLayout shape;
+    if (!r) {
+        RC_TRY(layout_shape(n, w, h, nullptr, shape));
+        out = std::move(shape);
+        return H263MI_OK;
+    }
+    uint64_t bytes = 0;
+    RC_TRY(rgba_resize_extent(n, r, &bytes));
+    h263mi_rgba_layout lay;
+    if (resize_as_layout(w, h, *r, &lay)) {     // identical by definition: the fused layout kernels, no scratch, no extra pass
+        RC_TRY(layout_shape(n, w, h, &lay, shape));
+        out = std::move(shape);
+        return H263MI_OK;
+    }
+    const uint32_t ow = r->out_width, oh = r->out_height;
+    const uint64_t pitch = r->row_pitch ? r->row_pitch : 4ull * ow;
+    std::vector<ResizeSpan> spans((size_t)ow + oh);
+    resize_spans(w, ow, spans.data());
+    resize_spans(h, oh, spans.data() + ow);
+    DeviceGuard g(device);
+    if (!g.ok) return H263MI_ERR_NO_DEVICE;
+    std::shared_ptr<h263mi_resize_scratch> sc(new (std::nothrow) h263mi_resize_scratch());
+    if (!sc) return H263MI_ERR_OUT_OF_MEMORY;
+    sc->device = device;
+    const size_t rgba_bytes = (size_t)n * w * h * 4, span_bytes = spans.size() * sizeof(ResizeSpan);
+    HIP_TRY(hipMalloc((void **)&sc->rgba, rgba_bytes));
+    HIP_TRY(hipMalloc((void **)&sc->spans, span_bytes));
+    HIP_TRY(hipMemcpy(sc->spans, spans.data(), span_bytes, hipMemcpyHostToDevice));
+    sc->bytes = rgba_bytes + span_bytes;
+    shape.bytes = bytes;
+    shape.offsets.resize(n);
+    for (uint32_t i = 0; i < n; i++) shape.offsets[i] = r->offsets ? r->offsets[i] : (uint64_t)i * oh * pitch;
+    shape.resize.scratch = std::move(sc);
+    shape.resize.ow = ow;
+    shape.resize.oh = oh;
+    shape.resize.pitch = (uint32_t)(oh > 1 ? pitch : 4ull * ow);     // (one row: the pitch is never used)
+    out = std::move(shape);
+    return H263MI_OK;
+}
+
 }  // namespace h263mi
 
 // =========================================================================================
@@ -740,13 +903,23 @@ int h263mi_batch_set_rgba_layout(h263mi_batch *b, const h263mi_rgba_layout *layo
 {
     if (!b) return H263MI_ERR_INVALID_ARGUMENT;
     h263mi_batch::RgbaLayout lay;
-    uint32_t ow = 0, oh = 0;
-    RC_TRY(rgba_layout_extent(b->n, b->L.width, b->L.height, layout, &ow, &oh, &lay.bytes, &lay.kernel));
-    if (lay.placed()) {
-        lay.offsets.resize(b->n);
-        const uint64_t pitch = (layout->row_pitch ? layout->row_pitch : 4ull * ow);
-        for (uint32_t i = 0; i < b->n; i++) lay.offsets[i] = layout->offsets ? layout->offsets[i] : (uint64_t)i * oh * pitch;
-    }
+    RC_TRY(layout_shape(b->n, b->L.width, b->L.height, layout, lay));
+    DeviceGuard g(b->device);                  // (a resize it replaces frees its scratch)
+    b->layout = std::move(lay);
+    return H263MI_OK;
+}
+
+int h263mi_rgba_resize_extent(uint32_t n_streams, const h263mi_rgba_resize *r, uint64_t *bytes)
+{
+    return rgba_resize_extent(n_streams, r, bytes);
+}
+
+int h263mi_batch_set_rgba_resize(h263mi_batch *b, const h263mi_rgba_resize *r)
+{
+    if (!b) return H263MI_ERR_INVALID_ARGUMENT;
+    h263mi_batch::RgbaLayout lay;
+    RC_TRY(make_output_shape(b->device, b->n, b->L.width, b->L.height, r, lay));
+    DeviceGuard g(b->device);
     b->layout = std::move(lay);
     return H263MI_OK;
 }
@@ -843,7 +1016,7 @@ int h263mi_batch_timing_end(h263mi_batch *b, h263mi_kernel_times *out)
         if (r.kernel == 0) {
             out->recon_ms += ms;
             out->recon_launches += r.launches;
-        } else if (r.kernel == 1) {
+        } else if (r.kernel == 1 || r.kernel == 3) {       // (3: k_rgba_resize, the second half of a resized rendering)
             out->post_ms += ms;
             out->post_launches += r.launches;
         } else {

@@ -37,6 +37,17 @@ struct h263mi_rgba_out {
     uint32_t scale = 0, pitch = 0;
 };
 
+// What k_rgba_resize reads (h263mi_batch_set_rgba_resize): the full-size pictures that the rendering kernels write for it, and
+// the spans of its geometry.  Shared between the batch's shape and the pending rendering that was requested under it, so that
+// switching the shape while a pipelined rendering waits frees nothing that rendering still needs.
+struct h263mi_resize_scratch {
+    int device = 0;
+    uint8_t *rgba = nullptr;                   // n * w*h*4 bytes
+    h263mi::ResizeSpan *spans = nullptr;       // W' column spans, then H' row spans
+    uint64_t bytes = 0;                        // device memory held (both allocations)
+    ~h263mi_resize_scratch();
+};
+
 struct h263mi_batch {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -77,11 +88,20 @@ struct h263mi_batch {
         std::vector<uint64_t> offsets;
         uint64_t bytes = 0;                    // what d_rgba must hold (h263mi_rgba_layout_extent)
         bool placed() const { return kernel.pitch != 0; }
+        // a resize that is not one of the layouts (scratch != nullptr): the rendering kernels write the full-size pictures into
+        // the scratch with the default `kernel`, then k_rgba_resize writes W' x H' at `offsets` (all of them filled in)
+        struct Resize {
+            std::shared_ptr<h263mi_resize_scratch> scratch;
+            uint32_t ow = 0, oh = 0, pitch = 0;
+            bool on() const { return scratch != nullptr; }
+        } resize;
     } layout;
     struct PendingPost {
         bool valid = false;
         Strengths strength;
         OutLayout out;                         // the layout in force when the rendering was requested
+        RgbaLayout::Resize resize;             // ... or the resize (then `rgba` is its scratch)
+        uint8_t *const *resize_dst = nullptr;  // DEVICE array: stream s's resized picture, nullptr = none
         uint8_t *rgba = nullptr, *planes = nullptr;
         uint8_t *const *rgba_ptrs = nullptr;   // DEVICE array of per-stream output pointers (a batch inside a mixed-size set)
         std::vector<int8_t> set;               // per stream: frame set it reads, -1 = nothing to post-process
@@ -158,6 +178,7 @@ struct h263mi_batch {
     struct TimedChain { size_t first; int kernel; uint32_t launches; };   // (index of the begin event, kernel id, launches)
     std::vector<TimedChain> ev_ranges;
     int chain_kernel = -1;
+    hipStream_t chain_on = nullptr;            // the stream the chain's launches are queued on
     uint32_t chain_launches = 0;
 
     ~h263mi_batch();
@@ -192,7 +213,8 @@ struct h263mi_batch {
     // ---- launch timing (h263mi_batch_timing_begin / _end); kernel ids: 0 k_recon, 1 k_post, 2 k_frame
     hipStream_t stream_of(int kernel_id) const { return (kernel_id == 1 && overlap_post) ? post_stream : stream; }
     int time_close();
-    int time_begin(int kernel_id);
+    // (kernel id 3: k_rgba_resize, queued on `on` behind the rendering it resizes; its time counts as post-processing)
+    int time_begin(int kernel_id, hipStream_t on = nullptr);
 
     // ---- the work
     // state.rs:432-483 for every stream of the batch that takes part.  types: one picture type per stream, or nullptr:
@@ -207,6 +229,11 @@ struct h263mi_batch {
     // the batch's layout applied to d_rgba: false = the default layout (d_rgba as it is); true = `ptrs` holds n DEVICE pointers,
     // stream s's picture at d_rgba + its offset
     bool layout_ptrs(uint8_t *d_rgba, std::vector<uint8_t *> &ptrs) const;
+    // a resize in force: the DEVICE array of k_rgba_resize's destinations -- stream s at host_ptrs[s] (if given) or d_rgba +
+    // its offset, nullptr where sets[s] < 0 -- uploaded on `on`
+    int resize_dst(const std::vector<int8_t> &sets, uint8_t *d_rgba, uint8_t *const *host_ptrs, hipStream_t on, uint8_t *const **d_out);
+    // k_rgba_resize of `rz` into `d_dst` (resize_dst), on `on`; nothing when no stream has a set (sets[s] < 0 for all)
+    int launch_resize(const RgbaLayout::Resize &rz, const std::vector<int8_t> &sets, uint8_t *const *d_dst, hipStream_t on);
     // pipeline mode: the post-processing of the pictures just submitted is deferred to the next launch.
     // host_ptrs (or nullptr): n DEVICE pointers, the RGBA buffer of each stream (nullptr = none for it) instead of d_rgba.
     int note_pending(const Strengths &strength, uint8_t *d_rgba, uint8_t *d_planes, uint8_t *const *host_ptrs = nullptr);
@@ -226,6 +253,15 @@ namespace h263mi {
 // h263mi_rgba_layout_extent; out_kernel (may be null): what the kernels are told (pitch 0 = today's layout)
 int rgba_layout_extent(uint32_t n_streams, uint32_t w, uint32_t h, const h263mi_rgba_layout *layout, uint32_t *out_w,
                        uint32_t *out_h, uint64_t *bytes, h263mi_batch::OutLayout *out_kernel = nullptr);
+// h263mi_rgba_resize_extent for n streams
+int rgba_resize_extent(uint32_t n_streams, const h263mi_rgba_resize *r, uint64_t *bytes);
+// the layout that a resize of a w x h picture is by definition (full size, or 1/2 or 1/4 of sizes that 2 or 4 divide), into
+// *lay (offsets and pitch copied); false: none, the resize needs k_rgba_resize
+bool resize_as_layout(uint32_t w, uint32_t h, const h263mi_rgba_resize &r, h263mi_rgba_layout *lay);
+// the shape `r` (NULL: the default) for a batch of n streams of w x h: the layout it routes to, or the resize with a new scratch
+int make_output_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_rgba_resize *r, h263mi_batch::RgbaLayout &out);
+// device memory a resize of `slots` pictures of w x h holds (0: it is a layout)
+uint64_t resize_scratch_bytes(uint32_t w, uint32_t h, uint32_t slots, const h263mi_rgba_resize &r);
 int batch_create(uint32_t n_streams, uint32_t w, uint32_t h, const h263mi_backend_cfg *cfg, h263mi_batch **out);
 // where the host side of device `dev`'s work belongs (worker_pool.h): the PCI addresses of the visible devices -> sysfs
 HostPlacement placement_of_device(int dev);

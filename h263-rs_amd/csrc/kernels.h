@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "dev_common.h"
+#include "resize_kernel.inl"
 
 namespace h263mi {
 
@@ -36,6 +37,10 @@ hipError_t launch_recon(const ReconArgs &args, hipStream_t stream, const uint32_
 // next reads the planes it wrote last -- the ones still in the infinity cache -- first (2 % on a 64-stream batch).
 hipError_t launch_frame(const ReconArgs &rargs, const PostArgs &pargs, hipStream_t stream, bool descending, const uint32_t *words = nullptr);
 hipError_t launch_post(const PostArgs &args, hipStream_t stream, const uint32_t *words = nullptr);
+// k_rgba_resize over args.n_pictures pictures (resize_kernel.inl; bands and chunk are set here).  Declared weak: the host
+// objects are also linked, in the CPU suite's ThreadSanitizer build (tests/tsan), against a stub runtime that has no resize
+// launcher.  The library always defines it (kernels.hip); h263mi_batch::launch_resize refuses to run without it.
+hipError_t launch_rgba_resize(const ResizeArgs &args, hipStream_t stream) __attribute__((weak));
 hipError_t launch_synth_headers(const SynthArgs &args, hipStream_t stream);
 hipError_t launch_synth_coeffs(const SynthArgs &args, hipStream_t stream);
 // streaming probes: mode 0 copy in -> out, 1 read in (out = 16-byte sink), 2 write out; bytes is a multiple of 16;

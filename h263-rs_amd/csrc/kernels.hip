@@ -4,6 +4,7 @@
 
 #include "post_kernel.inl"
 #include "recon_kernel.inl"
+#include "resize_kernel.inl"
 #include "synth.inl"
 
 namespace h263mi {
@@ -702,6 +703,33 @@ hipError_t launch_frame(const ReconArgs &rargs, const PostArgs &pargs, hipStream
     else if (pa.rgba_scale == 1) hipLaunchKernelGGL(k_frame_layout<1>, grid, dim3(64), 0, stream, sw, ra, pa, fg);
     else if (pa.rgba_scale == 2) hipLaunchKernelGGL(k_frame_layout<2>, grid, dim3(64), 0, stream, sw, ra, pa, fg);
     else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
+// k_rgba_resize: area-average resampling of full-size RGBA (resize_kernel.inl).  One wave per workgroup, no barrier;
+// blockIdx.y = picture, blockIdx.z = segment of 64 output columns, blockIdx.x = band of RESIZE_ROWS output rows in XCD
+// order: XCD k (blockIdx.x & 7, gridDim.x a multiple of 8) takes a contiguous run of bands, so the source rows that two
+// neighbouring bands share are fetched into one L2.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_rgba_resize(ResizeArgs a)
+{
+    __shared__ __attribute__((aligned(16))) ResizeLds lds;
+    const uint32_t band = (blockIdx.x & 7u) * a.chunk + (blockIdx.x >> 3);
+    if (band >= a.bands) return;
+    const int lane = threadIdx.x & 63;
+    ResizeLane t;
+    resize_item(a, lds, band, blockIdx.z, blockIdx.y, [&](auto f) { f(lane, t); });
+}
+
+hipError_t launch_rgba_resize(const ResizeArgs &args, hipStream_t stream)
+{
+    if (!args.n_pictures) return hipSuccess;
+    ResizeArgs a = args;
+    a.bands = (a.oh + RESIZE_ROWS - 1) / RESIZE_ROWS;
+    a.chunk = (a.bands + 7) / 8;
+    const dim3 grid(a.chunk * 8, a.n_pictures, (a.ow + 63) / 64);
+    hipLaunchKernelGGL(k_rgba_resize, grid, dim3(64), 0, stream, a);
     return hipGetLastError();
 }
 

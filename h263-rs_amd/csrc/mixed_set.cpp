@@ -59,18 +59,33 @@ struct h263mi_mixed {
     // What the frame stores of all classes together may take (0 = no limit).  The sizes come out of untrusted bitstreams:
     // without a limit one hostile key frame of 16 384 x 16 384 asks for 800 MB per stream that sends one.
     uint64_t limit_bytes = 0;
+    // h263mi_mixed_set_rgba_resize: every stream rendered as W' x H' (offsets NULL), or full size (resized false)
+    bool resized = false;
+    h263mi_rgba_resize resize{};
     ~h263mi_mixed()
     {
         pool.reset();                           // the host threads first
         for (SizeClass &c : classes) delete c.b;
     }
-    static uint64_t slots_bytes(uint32_t w, uint32_t h, uint32_t slots) { return 2ull * slots * make_layout(w, h).frame_bytes; }
+    // a class's frame store, and the scratch of its full-size pictures while a resize that is not a layout is in force
+    static uint64_t class_bytes(uint32_t w, uint32_t h, uint32_t slots, const h263mi_rgba_resize *rz)
+    {
+        return 2ull * slots * make_layout(w, h).frame_bytes + (rz ? resize_scratch_bytes(w, h, slots, *rz) : 0);
+    }
+    uint64_t slots_bytes(uint32_t w, uint32_t h, uint32_t slots) const { return class_bytes(w, h, slots, resized ? &resize : nullptr); }
     uint64_t store_bytes() const
     {
         uint64_t sum = 0;
         for (const SizeClass &c : classes)
             if (c.b) sum += slots_bytes(c.w, c.h, c.b->n);
         return sum;
+    }
+    // what stream s's buffer must hold for a picture of w x h
+    uint64_t rgba_need(uint32_t w, uint32_t h) const
+    {
+        if (!resized) return (uint64_t)w * h * 4;
+        const uint64_t row = 4ull * resize.out_width, pitch = resize.row_pitch ? resize.row_pitch : row;
+        return (uint64_t)(resize.out_height - 1) * pitch + row;
     }
     WorkerPool &workers(unsigned want)
     {
@@ -119,6 +134,13 @@ struct h263mi_mixed {
             return H263MI_ERR_OUT_OF_MEMORY;
         h263mi_batch *nb = nullptr;
         RC_TRY(batch_create(slots, c.w, c.h, &cfg, &nb));
+        {
+            const int rc = make_output_shape(cfg.device_id, slots, c.w, c.h, resized ? &resize : nullptr, nb->layout);
+            if (rc != H263MI_OK) {
+                delete nb;
+                return rc;
+            }
+        }
         std::vector<int> moved(slots, -1);
         if (ob) {
             std::vector<int> rcs(ob->n, H263MI_OK);
@@ -222,6 +244,27 @@ int h263mi_mixed_set_memory_limit(h263mi_mixed *m, uint64_t bytes)
 
 uint64_t h263mi_mixed_frame_store_bytes(const h263mi_mixed *m) { return m ? m->store_bytes() : 0; }
 
+int h263mi_mixed_set_rgba_resize(h263mi_mixed *m, const h263mi_rgba_resize *r)
+{
+    if (!m || (r && r->offsets)) return H263MI_ERR_INVALID_ARGUMENT;
+    if (r) RC_TRY(rgba_resize_extent(1, r, nullptr));
+    DeviceGuard g(m->cfg.device_id);
+    if (!g.ok) return H263MI_ERR_NO_DEVICE;
+    // every class's new shape first (the scratches they need count against the limit), then all of them at once
+    uint64_t total = 0;
+    for (const h263mi_mixed::SizeClass &c : m->classes)
+        if (c.b) total += h263mi_mixed::class_bytes(c.w, c.h, c.b->n, r);
+    if (m->limit_bytes && total > m->limit_bytes) return H263MI_ERR_OUT_OF_MEMORY;
+    std::vector<h263mi_batch::RgbaLayout> shapes(m->classes.size());
+    for (size_t k = 0; k < m->classes.size(); k++)
+        if (m->classes[k].b) RC_TRY(make_output_shape(m->cfg.device_id, m->classes[k].b->n, m->classes[k].w, m->classes[k].h, r, shapes[k]));
+    for (size_t k = 0; k < m->classes.size(); k++)
+        if (m->classes[k].b) m->classes[k].b->layout = std::move(shapes[k]);
+    m->resized = r != nullptr;
+    m->resize = r ? *r : h263mi_rgba_resize{};
+    return H263MI_OK;
+}
+
 int h263mi_mixed_decode_next_pictures(h263mi_mixed *m, uint32_t decoder_options, const uint8_t *const *data, const size_t *len,
                                       size_t *consumed, uint32_t n_threads, int *stream_rc, uint8_t strength,
                                       uint8_t *const *d_rgba, const size_t *rgba_capacity, h263mi_picture_desc *descs)
@@ -276,7 +319,7 @@ int h263mi_mixed_decode_next_pictures_ps(h263mi_mixed *m, uint32_t decoder_optio
         const bool has_ref = st_old && st_old->has_ref && st_old->cur >= 0;
         if (rc == H263MI_OK && any_inter && !has_ref) rc = H263MI_ERR_UNCODED_IFRAME_BLOCKS;          // gather.rs:149
         if (rc == H263MI_OK && any_inter && !same) rc = H263MI_ERR_PICTURE_FORMAT_INVALID;           // (see the head of this section)
-        if (rc == H263MI_OK && d_rgba && d_rgba[i] && rgba_capacity[i] < (size_t)w * h * 4) rc = H263MI_ERR_INVALID_ARGUMENT;
+        if (rc == H263MI_OK && d_rgba && d_rgba[i] && rgba_capacity[i] < m->rgba_need(w, h)) rc = H263MI_ERR_INVALID_ARGUMENT;
         if (rc == H263MI_OK) {
             want[i] = Want{w, h};
             target[i] = same ? c_old : -2;       // -2: joins a class of that size (existing or new), resolved below

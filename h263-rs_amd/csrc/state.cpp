@@ -307,6 +307,40 @@ int h263mi_render_rgba_layout(const h263mi_state *cs, uint8_t strength, const h2
     return H263MI_OK;
 }
 
+int h263mi_render_rgba_resize(const h263mi_state *cs, uint8_t strength, const h263mi_rgba_resize *r, uint8_t *rgba)
+{
+    h263mi_state *s = const_cast<h263mi_state *>(cs);
+    if (!s || !rgba || !r || r->offsets) return H263MI_ERR_INVALID_ARGUMENT;
+    if (!s->has_last || !s->b) return H263MI_ERR_NO_PICTURE;
+    h263mi_batch *b = s->b;
+    RC_TRY(rgba_resize_extent(1, r, nullptr));
+    h263mi_batch::Strengths st;
+    RC_TRY(state_strength(s, strength, st));
+    DeviceGuard g(s->cfg.device_id);
+    // rendered tightly (W' x H') into the device scratch, then copied out row by row when the caller's pitch is wider
+    const size_t row = (size_t)r->out_width * 4, bytes = row * r->out_height, pitch = r->row_pitch ? (size_t)r->row_pitch : row;
+    if (bytes > s->cap_rgba) {
+        if (s->d_rgba) (void)hipFree(s->d_rgba);
+        s->d_rgba = nullptr; s->cap_rgba = 0;
+        HIP_TRY(hipMalloc((void **)&s->d_rgba, bytes));
+        s->cap_rgba = bytes;
+    }
+    h263mi_rgba_resize tight = *r;
+    tight.row_pitch = 0;
+    h263mi_batch::RgbaLayout lay;
+    RC_TRY(make_output_shape(s->cfg.device_id, 1, b->L.width, b->L.height, &tight, lay));
+    h263mi_batch::RgbaLayout saved = std::move(b->layout);
+    b->layout = std::move(lay);
+    const int rc = b->render(st, s->d_rgba, nullptr);
+    lay = std::move(b->layout);                 // (its scratch, if any, goes at the end, once the copy below has waited for it)
+    b->layout = std::move(saved);
+    RC_TRY(rc);
+    if (pitch == row) HIP_TRY(hipMemcpyAsync(rgba, s->d_rgba, bytes, hipMemcpyDeviceToHost, b->stream));
+    else HIP_TRY(hipMemcpy2DAsync(rgba, pitch, s->d_rgba, row, row, r->out_height, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    return H263MI_OK;
+}
+
 int h263mi_render_rgba_pinned(const h263mi_state *cs, uint8_t strength, uint8_t *rgba_pinned)
 {
     h263mi_state *s = const_cast<h263mi_state *>(cs);

@@ -87,6 +87,8 @@ EXPORTS = [
     "h263mi_set_ranks_per_node", "h263mi_batch_host_placement", "h263mi_debug_host_placement",
     # ABI 7, additive: scaled RGBA with a row pitch and per-stream placement
     "h263mi_rgba_layout_extent", "h263mi_batch_set_rgba_layout", "h263mi_render_rgba_layout",
+    # ABI 7, additive: RGBA resized to any W' x H' by area averaging
+    "h263mi_rgba_resize_extent", "h263mi_batch_set_rgba_resize", "h263mi_render_rgba_resize", "h263mi_mixed_set_rgba_resize",
 ]
 STRENGTH_FROM_HEADER = 0xFF
 CFG_OVERLAP_POST, CFG_PIPELINE_POST, CFG_TRUSTED_ARRAYS = 1, 2, 4
@@ -147,6 +149,38 @@ def rgba_layout_extent(n_streams, width, height, scale_log2=0, row_pitch=0, offs
            "rgba_layout_extent")
     del keep
     return ow.value, oh.value, nb.value
+
+
+class RgbaResize(C.Structure):
+    """h263mi_rgba_resize: output picture out_width x out_height, the area average of the full-size RGBA, rows row_pitch bytes
+    apart (0 = tight), stream s's picture at byte offsets[s] (NULL = s * H' * pitch)."""
+    _fields_ = [("out_width", C.c_uint16), ("out_height", C.c_uint16), ("reserved", C.c_uint8 * 4), ("row_pitch", C.c_uint64),
+                ("offsets", C.POINTER(C.c_uint64))]
+
+
+def make_rgba_resize(out_width, out_height, row_pitch=0, offsets=None):
+    """-> (RgbaResize, the offsets array it points into: keep it alive with the struct)"""
+    r = RgbaResize()
+    r.out_width = out_width
+    r.out_height = out_height
+    r.row_pitch = row_pitch
+    keep = None
+    if offsets is not None:
+        keep = np.ascontiguousarray(offsets, dtype=np.uint64)
+        r.offsets = keep.ctypes.data_as(C.POINTER(C.c_uint64))
+    return r, keep
+
+
+def rgba_resize_extent(n_streams, out_width, out_height, row_pitch=0, offsets=None, resize=None):
+    """h263mi_rgba_resize_extent -> bytes the output buffer must hold; H263Error when the resize is refused.
+    resize: an RgbaResize to pass as it is (else one is made of the other arguments)."""
+    keep = None
+    if resize is None:
+        resize, keep = make_rgba_resize(out_width, out_height, row_pitch, offsets)
+    nb = C.c_uint64()
+    _check(lib().h263mi_rgba_resize_extent(n_streams, C.byref(resize), C.byref(nb)), "rgba_resize_extent")
+    del keep
+    return nb.value
 
 
 class KernelTimes(C.Structure):
@@ -281,6 +315,10 @@ def lib():
         L.h263mi_rgba_layout_extent.argtypes = [u32, u16, u16, vp, C.POINTER(u16), C.POINTER(u16), C.POINTER(C.c_uint64)]
         L.h263mi_batch_set_rgba_layout.argtypes = [vp, vp]
         L.h263mi_render_rgba_layout.argtypes = [vp, u8, vp, vp]
+        L.h263mi_rgba_resize_extent.argtypes = [u32, vp, C.POINTER(C.c_uint64)]
+        L.h263mi_batch_set_rgba_resize.argtypes = [vp, vp]
+        L.h263mi_render_rgba_resize.argtypes = [vp, u8, vp, vp]
+        L.h263mi_mixed_set_rgba_resize.argtypes = [vp, vp]
         L.h263mi_default_parser_threads.restype = u32
         L.h263mi_default_parser_threads.argtypes = [u32, C.POINTER(u32)]
         _lib = L
@@ -465,6 +503,17 @@ class H263State:
     def render_rgba_layout_into(self, strength, out, scale_log2=0, row_pitch=0):
         lay, _ = make_rgba_layout(scale_log2, row_pitch)
         _check(lib().h263mi_render_rgba_layout(self._h, strength, C.byref(lay), _p(out)), "render_rgba_layout")
+        return out
+
+    def render_rgba_resize(self, strength, out_width, out_height, row_pitch=0):
+        """h263mi_render_rgba_resize: H' * pitch bytes (rows of 4W' bytes; what lies between rows is zero here)"""
+        nb = rgba_resize_extent(1, out_width, out_height, row_pitch)
+        out = np.zeros(nb + (row_pitch - 4 * out_width if row_pitch else 0), np.uint8)
+        return self.render_rgba_resize_into(strength, out, out_width, out_height, row_pitch)
+
+    def render_rgba_resize_into(self, strength, out, out_width, out_height, row_pitch=0):
+        r, _ = make_rgba_resize(out_width, out_height, row_pitch)
+        _check(lib().h263mi_render_rgba_resize(self._h, strength, C.byref(r), _p(out)), "render_rgba_resize")
         return out
 
     def render_rgba_pinned(self, strength, pinned):
@@ -708,6 +757,15 @@ class Batch:
         _check(lib().h263mi_batch_set_rgba_layout(self._h, C.byref(lay)), "batch_set_rgba_layout")
         del keep
 
+    def set_rgba_resize(self, out_width=0, out_height=0, row_pitch=0, offsets=None, default=False):
+        """h263mi_batch_set_rgba_resize (default=True: back to today's output)"""
+        if default:
+            _check(lib().h263mi_batch_set_rgba_resize(self._h, None), "batch_set_rgba_resize")
+            return
+        r, keep = make_rgba_resize(out_width, out_height, row_pitch, offsets)
+        _check(lib().h263mi_batch_set_rgba_resize(self._h, C.byref(r)), "batch_set_rgba_resize")
+        del keep
+
     def render_rgba(self, strength, d_rgba, d_deblocked=None, strengths=None):
         keep, ps = self._strengths(strengths)
         _check(lib().h263mi_batch_render_rgba_ps(self._h, strength, ps, d_rgba, d_deblocked), "batch_render_rgba")
@@ -803,6 +861,14 @@ class MixedBatch:
 
     def size_classes(self):
         return lib().h263mi_mixed_size_classes(self._h)
+
+    def set_rgba_resize(self, out_width=0, out_height=0, row_pitch=0, default=False):
+        """h263mi_mixed_set_rgba_resize: every stream as out_width x out_height at its own buffer (default=True: full size)"""
+        if default:
+            _check(lib().h263mi_mixed_set_rgba_resize(self._h, None), "mixed_set_rgba_resize")
+            return
+        r, _ = make_rgba_resize(out_width, out_height, row_pitch)
+        _check(lib().h263mi_mixed_set_rgba_resize(self._h, C.byref(r)), "mixed_set_rgba_resize")
 
     def set_memory_limit(self, n_bytes):
         """what the frame stores of all size classes together may take (0 = no limit; default: half of the device's memory)"""

@@ -150,6 +150,16 @@ public:
         check(h263mi_render_rgba_layout(s_, strength, &layout, rgba.data()));
         return rgba;
     }
+    // the same resized to W' x H' (h263mi_rgba_resize, offsets NULL): H' * pitch bytes, the ones between rows zero
+    std::vector<uint8_t> render_rgba(uint8_t strength, const h263mi_rgba_resize &r) const
+    {
+        uint64_t bytes = 0;
+        check(h263mi_rgba_resize_extent(1, &r, &bytes));
+        const uint64_t pitch = r.row_pitch ? r.row_pitch : 4ull * r.out_width;
+        std::vector<uint8_t> rgba((size_t)(pitch * r.out_height));
+        check(h263mi_render_rgba_resize(s_, strength, &r, rgba.data()));
+        return rgba;
+    }
 
     // the same straight into page-locked memory of the caller (h263mi_host_alloc / h263mi_host_register): the buffer a
     // renderer reuses for every picture instead of the fresh Vec<u8> of bt601.rs:128; `rgba` holds width * height * 4 bytes
@@ -318,6 +328,8 @@ public:
     // device memory the frame stores of all sizes together may take (0 = no limit; default: half of the device's memory): a
     // picture of a new size that would go beyond it is that stream's Error (H263MI_ERR_OUT_OF_MEMORY)
     void set_memory_limit(uint64_t bytes) { check(h263mi_mixed_set_memory_limit(m_, bytes)); }
+    // every stream rendered as W' x H' (offsets NULL); nullptr = full size again
+    void set_rgba_resize(const h263mi_rgba_resize *r) { check(h263mi_mixed_set_rgba_resize(m_, r)); }
     uint64_t frame_store_bytes() const { return h263mi_mixed_frame_store_bytes(m_); }
     h263mi_mixed *raw() { return m_; }
 

@@ -395,6 +395,37 @@ int h263mi_batch_set_rgba_layout(h263mi_batch *b, const h263mi_rgba_layout *layo
  * be NULL. */
 int h263mi_render_rgba_layout(const h263mi_state *s, uint8_t strength, const h263mi_rgba_layout *layout, uint8_t *rgba);
 
+/*
+ * RGBA OUTPUT RESIZED TO ANY W' x H' (additive, ABI 7): an area average of the full-size RGBA (the picture's strength, deblock,
+ * BT.601).  With P the w x h source: output column X covers [X*w, (X+1)*w) and source column i covers [i*W', (i+1)*W');
+ * ox(X, i) is the length of their intersection, oy(Y, j) the same for rows with h and H', and
+ *     out[Y][X][c] = (sum_j sum_i oy(Y,j) * ox(X,i) * P[j][i][c] + floor(w*h/2)) div (w*h)   for R, G, B;  alpha 255.
+ * Exact integer arithmetic, one rounding (half up).  W' = w, H' = h is the full-size picture bit for bit; W' = w/f, H' = h/f
+ * with f = 2 or 4 dividing both sizes is the scale_log2 box average of h263mi_rgba_layout (and goes through the same kernels).
+ * Placement as h263mi_rgba_layout: rows row_pitch bytes apart, stream s's picture at byte offsets[s].  The deblocked planes
+ * (d_deblocked) stay full size.
+ */
+typedef struct h263mi_rgba_resize {
+    uint16_t out_width, out_height;   /* W', H' >= 1 */
+    uint8_t  reserved[4];             /* zero */
+    uint64_t row_pitch;               /* bytes from one output row to the next; 0 = 4 W' */
+    const uint64_t *offsets;          /* HOST, n_streams entries; NULL = s * H' * pitch; must be NULL for one state or a mixed set */
+} h263mi_rgba_resize;
+
+/* Pure host function, no HIP call: validates and returns the bytes the output buffer must hold.  H263MI_ERR_INVALID_ARGUMENT:
+ * r NULL, n_streams 0, W' or H' 0, a reserved byte set, and the rules of h263mi_rgba_layout_extent (pitch and offsets multiples
+ * of 4, pitch >= 4W', rows inside the pitch, (H'-1) * pitch + 4W' < 2^32, no two pictures sharing a byte). */
+int h263mi_rgba_resize_extent(uint32_t n_streams, const h263mi_rgba_resize *r, uint64_t *bytes);
+/* A batch has ONE output shape in force: a layout or a resize; each setter replaces the other, NULL restores the default.
+ * Every later call that writes d_rgba follows it, as with h263mi_batch_set_rgba_layout (a deferred rendering of
+ * H263MI_CFG_PIPELINE_POST keeps the shape of its request; a checked batch holds d_rgba to the resize extent).  Streams with
+ * nothing to render are not written, nor is anything outside the pictures' rectangles.  Unless the sizes make it one of the
+ * layouts above, the batch keeps a device scratch of n_streams * w*h*4 bytes (the full-size pictures) while a resize is in
+ * force. */
+int h263mi_batch_set_rgba_resize(h263mi_batch *b, const h263mi_rgba_resize *r);
+/* One state, into HOST memory: H' rows of 4*W' bytes at rgba + r * pitch; offsets must be NULL. */
+int h263mi_render_rgba_resize(const h263mi_state *s, uint8_t strength, const h263mi_rgba_resize *r, uint8_t *rgba);
+
 /* deblock (strength 0 = off) + BT.601 of every stream's last picture into d_rgba
  * (DEVICE, n_streams * w*h*4 bytes, stream-major); d_deblocked (DEVICE, may be NULL)
  * additionally receives the filtered planes, n_streams * (w*h + 2*cw*ch) bytes as
@@ -597,6 +628,12 @@ uint32_t h263mi_mixed_size_classes(const h263mi_mixed *m);
  * half of the device's memory; 0 = no limit. */
 int h263mi_mixed_set_memory_limit(h263mi_mixed *m, uint64_t bytes);
 uint64_t h263mi_mixed_frame_store_bytes(const h263mi_mixed *m);
+/* Every stream of the set, whatever its size, rendered as W' x H' (h263mi_rgba_resize; offsets must be NULL) at its own
+ * d_rgba[s], rows row_pitch bytes apart; NULL = full size again (the default).  rgba_capacity[s] must then be at least
+ * (H'-1) * pitch + 4W' (else that stream's H263MI_ERR_INVALID_ARGUMENT).  A class whose size is not one of the layouts of
+ * h263mi_rgba_resize keeps a device scratch of its full-size pictures, slots * w*h*4 bytes: it counts against
+ * h263mi_mixed_set_memory_limit and in h263mi_mixed_frame_store_bytes as its frame store does. */
+int h263mi_mixed_set_rgba_resize(h263mi_mixed *m, const h263mi_rgba_resize *r);
 /* DecodedPicture::as_yuv of stream `stream`'s last picture: tightly packed planes to HOST memory */
 int h263mi_mixed_copy_yuv(h263mi_mixed *m, uint32_t stream, uint8_t *y, uint8_t *cb, uint8_t *cr);
 /* H263State::new for one stream: it forgets its pictures and its size */
