@@ -53,6 +53,12 @@ bool h263mi_batch::layout_ptrs(uint8_t *d_rgba, std::vector<uint8_t *> &ptrs) co
     return true;
 }
 
+h263mi_yuv_offsets::~h263mi_yuv_offsets()
+{
+    DeviceGuard g(device);
+    if (d) (void)hipFree(d);
+}
+
 h263mi_resize_scratch::~h263mi_resize_scratch()
 {
     DeviceGuard g(device);
@@ -232,7 +238,11 @@ int h263mi_batch::submit(uint8_t picture_type, const MbRecord *d_mbs, const h263
     a.frame_set[0] = frames[0];
     a.frame_set[1] = frames[1];
     PostArgs pa{};
-    if (with_post) pa = post_args(0, pending.strength.of(0), pending.rgba, pending.planes);
+    // A pending rendering of planes in a YUV layout: k_frame's post-processing half is the YUV instantiation -- or, when RGBA
+    // is pending too, the RGBA goes with k_frame as ever and the planes follow in a k_post_yuv launch of their own
+    const bool yuv_post = with_post && pending.yuv.on() && pending.planes;
+    const bool yuv_split = yuv_post && (pending.rgba || pending.rgba_ptrs);
+    if (with_post) pa = post_args(0, pending.strength.of(0), pending.rgba, yuv_split ? nullptr : pending.planes);
     if (with_post) pa.rgba_ptrs = pending.rgba_ptrs;       // (read in the per-stream branch of the kernel only)
     if (with_post) pa.rgba_scale = pending.out.scale, pa.rgba_pitch = pending.out.pitch;
     // one strength for every picture of the launch, or one per stream (then it travels in the streams' words)
@@ -279,12 +289,19 @@ int h263mi_batch::submit(uint8_t picture_type, const MbRecord *d_mbs, const h263
     }
     if (with_post) {
         RC_TRY(time_begin(2));
-        const hipError_t e = launch_frame(a, pa, stream, (frame_launches++ & 1u) != 0, !words.empty() && words_inline ? words.data() : nullptr);
+        const uint32_t *launch_words = !words.empty() && words_inline ? words.data() : nullptr;
+        const bool descending = (frame_launches++ & 1u) != 0;
+        hipError_t e;
+        if (yuv_post && !yuv_split)
+            e = launch_frame_yuv ? launch_frame_yuv(a, pa, pending.yuv.out(pending.planes), stream, descending, launch_words)
+                                 : hipErrorUnknown;        // (kernels.h: only a stub runtime lacks it)
+        else e = launch_frame(a, pa, stream, descending, launch_words);
         if (e != hipSuccess) {               // the deferred post-processing must not get lost with the failed launch
             (void)flush_pending();
             return map_hip_error(e);
         }
         pending.valid = false;
+        if (yuv_split) RC_TRY(launch_post_sets(pending.set, pending.strength, nullptr, pending.planes, stream, nullptr, OutLayout(), &pending.yuv));
         if (pending.resize.on()) {           // the full-size pictures k_frame has just written into the scratch, resized
             const RgbaLayout::Resize rz = std::move(pending.resize);
             pending.resize = RgbaLayout::Resize();
@@ -323,8 +340,17 @@ PostArgs h263mi_batch::post_args(int set, uint8_t strength, uint8_t *d_rgba, uin
 }
 
 int h263mi_batch::launch_post_sets(const std::vector<int8_t> &sets, const Strengths &strength, uint8_t *d_rgba, uint8_t *d_planes,
-                                   hipStream_t on, uint8_t *const *rgba_ptrs, OutLayout out)
+                                   hipStream_t on, uint8_t *const *rgba_ptrs, OutLayout out, const YuvLayout *yuv)
 {
+    if (yuv && yuv->on() && d_planes) {
+        // planes in a YUV layout: the RGBA of the call first, by the kernels it always takes, then the planes alone
+        if (d_rgba || rgba_ptrs) RC_TRY(launch_post_sets(sets, strength, d_rgba, nullptr, on, rgba_ptrs, out));
+        d_rgba = nullptr;
+        rgba_ptrs = nullptr;
+        out = OutLayout();
+    } else {
+        yuv = nullptr;
+    }
     bool same = rgba_ptrs == nullptr && strength.same_for_all(), any = false;
     for (int8_t v : sets) {
         same = same && v == sets[0];
@@ -349,7 +375,13 @@ int h263mi_batch::launch_post_sets(const std::vector<int8_t> &sets, const Streng
         a.frame_set[1] = frames[1];
     }
     RC_TRY(time_begin(1));
-    HIP_TRY(launch_post(a, on, !words.empty() && words_inline ? words.data() : nullptr));
+    const uint32_t *launch_words = !words.empty() && words_inline ? words.data() : nullptr;
+    if (yuv) {
+        if (!launch_post_yuv) return H263MI_ERR_HIP;           // (kernels.h: only a stub runtime lacks it)
+        HIP_TRY(launch_post_yuv(a, yuv->out(d_planes), on, launch_words));
+    } else {
+        HIP_TRY(launch_post(a, on, launch_words));
+    }
     return H263MI_OK;
 }
 
@@ -358,6 +390,7 @@ int h263mi_batch::note_pending(const Strengths &strength, uint8_t *d_rgba, uint8
     pending.valid = false;
     pending.rgba_ptrs = nullptr;
     pending.resize = RgbaLayout::Resize();
+    pending.yuv = d_planes ? yuv : YuvLayout();      // (captured here, at the request, like the RGBA shape)
     if (layout.resize.on() && (d_rgba || host_ptrs)) {
         // a resize: the deferred rendering writes the full-size pictures into the scratch, k_rgba_resize follows it (the
         // resize -- scratch, size, destinations -- is captured here, at the request)
@@ -392,7 +425,7 @@ int h263mi_batch::flush_pending()
     pending.valid = false;
     const RgbaLayout::Resize rz = std::move(pending.resize);
     pending.resize = RgbaLayout::Resize();
-    RC_TRY(launch_post_sets(pending.set, pending.strength, pending.rgba, pending.planes, stream, pending.rgba_ptrs, pending.out));
+    RC_TRY(launch_post_sets(pending.set, pending.strength, pending.rgba, pending.planes, stream, pending.rgba_ptrs, pending.out, &pending.yuv));
     return rz.on() ? launch_resize(rz, pending.set, pending.resize_dst, stream) : H263MI_OK;
 }
 
@@ -415,11 +448,11 @@ int h263mi_batch::render(const Strengths &strength, uint8_t *d_rgba, uint8_t *d_
     if (resized) {
         // full size into the scratch (the default kernels), then k_rgba_resize right behind it on the same stream
         RC_TRY(resize_dst(sets, d_rgba, host_ptrs, stream_of(1), &d_out_ptrs));
-        RC_TRY(launch_post_sets(sets, strength, rz.scratch->rgba, d_planes, stream_of(1)));
+        RC_TRY(launch_post_sets(sets, strength, rz.scratch->rgba, d_planes, stream_of(1), nullptr, OutLayout(), &yuv));
         RC_TRY(launch_resize(rz, sets, d_out_ptrs, stream_of(1)));
     } else {
         if (host_ptrs) RC_TRY(upload(ptr_ring, host_ptrs, &d_out_ptrs, stream_of(1)));
-        RC_TRY(launch_post_sets(sets, strength, d_rgba, d_planes, stream_of(1), d_out_ptrs, layout.kernel));
+        RC_TRY(launch_post_sets(sets, strength, d_rgba, d_planes, stream_of(1), d_out_ptrs, layout.kernel, &yuv));
     }
     // a later reconstruction may overwrite a frame set only when every post-processing that reads it is done: streams
     // that have drifted apart read both sets
@@ -633,7 +666,9 @@ static int bound_output_buffers(const h263mi_batch *b, const uint8_t *d_rgba, co
 {
     if (b->trusted_arrays) return H263MI_OK;
     const size_t rgba_bytes = b->layout.bytes;      // (n * w*h*4 unless the batch has an output layout)
-    const size_t plane_bytes = (size_t)b->n * ((size_t)b->L.width * b->L.height + 2 * (size_t)b->L.cwidth * b->L.cheight);
+    // (n tightly packed I420 pictures unless the batch has a YUV layout)
+    const size_t plane_bytes = b->yuv.on() ? (size_t)b->yuv.bytes
+                                           : (size_t)b->n * ((size_t)b->L.width * b->L.height + 2 * (size_t)b->L.cwidth * b->L.cheight);
     size_t left = 0;
     if (d_rgba) {
         const int rc = bytes_behind(d_rgba, &left);
@@ -691,6 +726,118 @@ int rgba_layout_extent(uint32_t n_streams, uint32_t w, uint32_t h, const h263mi_
         out_kernel->scale = dflt ? 0u : scale;
         out_kernel->pitch = dflt ? 0u : (uint32_t)(oh > 1 ? pitch : row);     // (one row: the pitch is never used)
     }
+    return H263MI_OK;
+}
+
+// h263mi_yuv_layout_extent (include/h263mi.h has the rules)
+int yuv_layout_extent(uint32_t n_streams, uint32_t w, uint32_t h, const h263mi_yuv_layout *lay, uint64_t *bytes,
+                      h263mi_batch::YuvLayout *shape, std::vector<uint64_t> *offsets_out)
+{
+    if (!n_streams || !w || !h || w > 65535 || h > 65535) return H263MI_ERR_INVALID_ARGUMENT;
+    const uint32_t fmt = lay ? lay->format : (uint32_t)H263MI_YUV_I420;
+    if (fmt != H263MI_YUV_I420 && fmt != H263MI_YUV_NV12) return H263MI_ERR_INVALID_ARGUMENT;
+    if (lay)
+        for (uint8_t r : lay->reserved)
+            if (r) return H263MI_ERR_INVALID_ARGUMENT;
+    const bool nv12 = fmt == H263MI_YUV_NV12;
+    const uint64_t cw = (w + 1) / 2, ch = (h + 1) / 2;
+    const uint64_t row_y = w, row_c = nv12 ? 2 * cw : cw;
+    const uint64_t pitch_y = (lay && lay->pitch_y) ? lay->pitch_y : row_y, pitch_c = (lay && lay->pitch_c) ? lay->pitch_c : row_c;
+    if (pitch_y < row_y || pitch_c < row_c) return H263MI_ERR_INVALID_ARGUMENT;
+    // bytes from a plane's first byte to behind its last: lane offsets are 32-bit
+    if ((h > 1 && pitch_y >= (1ull << 32)) || (ch > 1 && pitch_c >= (1ull << 32))) return H263MI_ERR_INVALID_ARGUMENT;
+    const uint64_t span_y = (uint64_t)(h - 1) * pitch_y + row_y, span_c = (ch - 1) * pitch_c + row_c;
+    if (span_y >= (1ull << 32) || span_c >= (1ull << 32)) return H263MI_ERR_INVALID_ARGUMENT;
+    const uint64_t *oy = lay ? lay->offsets_y : nullptr, *ocb = lay ? lay->offsets_cb : nullptr, *ocr = lay ? lay->offsets_cr : nullptr;
+    if (nv12 && ocr) return H263MI_ERR_INVALID_ARGUMENT;
+    const int given = (oy ? 1 : 0) + (ocb ? 1 : 0) + (ocr ? 1 : 0), all = nv12 ? 2 : 3;
+    if (given != 0 && given != all) return H263MI_ERR_INVALID_ARGUMENT;
+    const uint32_t chroma_planes = nv12 ? 1u : 2u;
+    std::vector<uint64_t> offs((size_t)3 * n_streams);
+    uint64_t total = 0;
+    if (!given) {
+        // planes back to back, pictures back to back: P bytes each
+        const unsigned __int128 P = (unsigned __int128)h * pitch_y + (unsigned __int128)chroma_planes * ch * pitch_c;
+        if (P * n_streams > UINT64_MAX) return H263MI_ERR_INVALID_ARGUMENT;
+        for (uint32_t i = 0; i < n_streams; i++) {
+            const uint64_t base = (uint64_t)P * i;
+            offs[3 * i + 0] = base;
+            offs[3 * i + 1] = base + h * pitch_y;
+            offs[3 * i + 2] = nv12 ? offs[3 * i + 1] : base + h * pitch_y + ch * pitch_c;
+        }
+        total = (uint64_t)(P * n_streams);
+    } else {
+        // every plane a rectangle on the grid of its pitch: rows [o / pitch, + rows), byte columns [o % pitch, + row)
+        struct Rect { uint64_t r0, c0, rows, cols; };
+        struct Span { uint64_t lo, hi; bool chroma; };
+        std::vector<Rect> ry, rc;
+        std::vector<Span> spans;
+        for (uint32_t i = 0; i < n_streams; i++) {
+            const uint64_t o[3] = {oy[i], ocb[i], nv12 ? ocb[i] : ocr[i]};
+            for (uint32_t k = 0; k < 1 + chroma_planes; k++) {
+                const uint64_t pitch = k ? pitch_c : pitch_y, row = k ? row_c : row_y, rows = k ? ch : h, span = k ? span_c : span_y;
+                if (o[k] % pitch + row > pitch || o[k] > UINT64_MAX - span) return H263MI_ERR_INVALID_ARGUMENT;
+                total = std::max(total, o[k] + span);
+                (k ? rc : ry).push_back(Rect{o[k] / pitch, o[k] % pitch, rows, row});
+                spans.push_back(Span{o[k], o[k] + span, k != 0});
+            }
+            for (int k = 0; k < 3; k++) offs[3 * i + k] = o[k];
+        }
+        auto intersect = [](std::vector<Rect> &rs) {
+            std::sort(rs.begin(), rs.end(), [](const Rect &x, const Rect &y) { return x.r0 < y.r0 || (x.r0 == y.r0 && x.c0 < y.c0); });
+            for (size_t i = 0; i < rs.size(); i++)
+                for (size_t j = i + 1; j < rs.size() && rs[j].r0 < rs[i].r0 + rs[i].rows; j++)      // (sorted by first row: later ones start lower)
+                    if (rs[j].c0 < rs[i].c0 + rs[i].cols && rs[i].c0 < rs[j].c0 + rs[j].cols) return true;
+            return false;
+        };
+        if (pitch_y == pitch_c) {
+            // one grid for all planes: the rectangle test decides between luma and chroma too
+            ry.insert(ry.end(), rc.begin(), rc.end());
+            if (intersect(ry)) return H263MI_ERR_INVALID_ARGUMENT;
+        } else {
+            if (intersect(ry) || intersect(rc)) return H263MI_ERR_INVALID_ARGUMENT;
+            // across the two grids: no luma plane's byte span may meet a chroma plane's
+            std::sort(spans.begin(), spans.end(), [](const Span &x, const Span &y) { return x.lo < y.lo; });
+            uint64_t end_luma = 0, end_chroma = 0;
+            for (const Span &sp : spans) {
+                if (sp.lo < (sp.chroma ? end_luma : end_chroma)) return H263MI_ERR_INVALID_ARGUMENT;
+                uint64_t &e = sp.chroma ? end_chroma : end_luma;
+                e = std::max(e, sp.hi);
+            }
+        }
+    }
+    if (bytes) *bytes = total;
+    if (shape) {
+        shape->format = nv12 ? YUV_OUT_NV12 : YUV_OUT_I420;
+        shape->pitch_y = (uint32_t)(h > 1 ? pitch_y : row_y);      // (one row: the pitch is never used)
+        shape->pitch_c = (uint32_t)(ch > 1 ? pitch_c : row_c);
+        shape->bytes = total;
+        bool wide = shape->pitch_y % 4 == 0 && shape->pitch_c % 4 == 0;
+        for (uint64_t o : offs) wide = wide && o % 4 == 0;
+        shape->wide = wide;
+    }
+    if (offsets_out) *offsets_out = std::move(offs);
+    return H263MI_OK;
+}
+
+int make_yuv_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_yuv_layout *lay, h263mi_batch::YuvLayout &out)
+{
+    h263mi_batch::YuvLayout shape;
+    if (!lay) {
+        out = std::move(shape);
+        return H263MI_OK;
+    }
+    std::vector<uint64_t> offs;
+    RC_TRY(yuv_layout_extent(n, w, h, lay, nullptr, &shape, &offs));
+    DeviceGuard g(device);
+    if (!g.ok) return H263MI_ERR_NO_DEVICE;
+    std::shared_ptr<h263mi_yuv_offsets> d(new (std::nothrow) h263mi_yuv_offsets());
+    if (!d) return H263MI_ERR_OUT_OF_MEMORY;
+    d->device = device;
+    HIP_TRY(hipMalloc((void **)&d->d, offs.size() * sizeof(uint64_t)));
+    HIP_TRY(hipMemcpy(d->d, offs.data(), offs.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+    shape.offsets = std::move(d);
+    out = std::move(shape);
     return H263MI_OK;
 }
 
@@ -906,6 +1053,21 @@ int h263mi_batch_set_rgba_layout(h263mi_batch *b, const h263mi_rgba_layout *layo
     RC_TRY(layout_shape(b->n, b->L.width, b->L.height, layout, lay));
     DeviceGuard g(b->device);                  // (a resize it replaces frees its scratch)
     b->layout = std::move(lay);
+    return H263MI_OK;
+}
+
+int h263mi_yuv_layout_extent(uint32_t n_streams, uint16_t width, uint16_t height, const h263mi_yuv_layout *layout, uint64_t *bytes)
+{
+    return yuv_layout_extent(n_streams, width, height, layout, bytes);
+}
+
+int h263mi_batch_set_yuv_layout(h263mi_batch *b, const h263mi_yuv_layout *layout)
+{
+    if (!b) return H263MI_ERR_INVALID_ARGUMENT;
+    h263mi_batch::YuvLayout lay;
+    RC_TRY(make_yuv_shape(b->device, b->n, b->L.width, b->L.height, layout, lay));
+    DeviceGuard g(b->device);                  // (the layout it replaces frees its offsets, unless a pending rendering holds them)
+    b->yuv = std::move(lay);
     return H263MI_OK;
 }
 

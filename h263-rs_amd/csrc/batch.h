@@ -48,6 +48,14 @@ struct h263mi_resize_scratch {
     ~h263mi_resize_scratch();
 };
 
+// The per-stream plane offsets of a YUV layout in device memory (3 per stream: Y, Cb or CbCr, Cr), uploaded once when the layout
+// is set.  Shared between the batch's layout and a pending rendering requested under it, like the resize scratch.
+struct h263mi_yuv_offsets {
+    int device = 0;
+    uint64_t *d = nullptr;
+    ~h263mi_yuv_offsets();
+};
+
 struct h263mi_batch {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -96,8 +104,31 @@ struct h263mi_batch {
             bool on() const { return scratch != nullptr; }
         } resize;
     } layout;
+    // The layout of the deblocked planes in d_deblocked (h263mi_batch_set_yuv_layout).  format 0: none -- tightly packed I420
+    // written by the default kernels, as ever.  Else the YUV instantiations write the planes (kernels.h: launch_post_yuv,
+    // launch_frame_yuv), and RGBA asked for in the same call is rendered by a launch of its own.
+    struct YuvLayout {
+        uint32_t format = 0;                   // 0, YUV_OUT_I420, YUV_OUT_NV12
+        uint32_t pitch_y = 0, pitch_c = 0;
+        bool wide = false;                     // pitches and offsets are all multiples of 4: the wide-store path
+        std::shared_ptr<h263mi_yuv_offsets> offsets;
+        uint64_t bytes = 0;                    // what d_deblocked must hold (h263mi_yuv_layout_extent)
+        bool on() const { return format != 0; }
+        // what the kernels are told for planes at d_planes
+        h263mi::YuvOut out(const uint8_t *d_planes) const
+        {
+            h263mi::YuvOut o{};
+            o.format = format;
+            o.wide = (wide && ((uintptr_t)d_planes & 3u) == 0) ? 1u : 0u;
+            o.pitch_y = pitch_y;
+            o.pitch_c = pitch_c;
+            o.offsets = offsets ? offsets->d : nullptr;
+            return o;
+        }
+    } yuv;
     struct PendingPost {
         bool valid = false;
+        YuvLayout yuv;                         // the plane layout in force when the rendering was requested
         Strengths strength;
         OutLayout out;                         // the layout in force when the rendering was requested
         RgbaLayout::Resize resize;             // ... or the resize (then `rgba` is its scratch)
@@ -224,8 +255,10 @@ struct h263mi_batch {
     h263mi::PostArgs post_args(int set, uint8_t strength, uint8_t *d_rgba, uint8_t *d_planes) const;
     // k_post over `sets` (per stream: the frame set to read, -1 = skip the stream); rgba_ptrs: DEVICE array of per-stream
     // output pointers instead of d_rgba (or nullptr)
+    // yuv (may be null; used when it is on and d_planes given): the planes go out in that layout through k_post_yuv, behind a
+    // launch of their own for the RGBA if that is asked for too
     int launch_post_sets(const std::vector<int8_t> &sets, const Strengths &strength, uint8_t *d_rgba, uint8_t *d_planes, hipStream_t on,
-                         uint8_t *const *rgba_ptrs = nullptr, OutLayout out = OutLayout());
+                         uint8_t *const *rgba_ptrs = nullptr, OutLayout out = OutLayout(), const YuvLayout *yuv = nullptr);
     // the batch's layout applied to d_rgba: false = the default layout (d_rgba as it is); true = `ptrs` holds n DEVICE pointers,
     // stream s's picture at d_rgba + its offset
     bool layout_ptrs(uint8_t *d_rgba, std::vector<uint8_t *> &ptrs) const;
@@ -253,6 +286,12 @@ namespace h263mi {
 // h263mi_rgba_layout_extent; out_kernel (may be null): what the kernels are told (pitch 0 = today's layout)
 int rgba_layout_extent(uint32_t n_streams, uint32_t w, uint32_t h, const h263mi_rgba_layout *layout, uint32_t *out_w,
                        uint32_t *out_h, uint64_t *bytes, h263mi_batch::OutLayout *out_kernel = nullptr);
+// h263mi_yuv_layout_extent.  shape (may be null): format / pitches / wide / bytes filled in (no device memory);
+// offsets (may be null): the 3 * n_streams plane offsets the kernels take (default placement spelled out)
+int yuv_layout_extent(uint32_t n_streams, uint32_t w, uint32_t h, const h263mi_yuv_layout *layout, uint64_t *bytes,
+                      h263mi_batch::YuvLayout *shape = nullptr, std::vector<uint64_t> *offsets = nullptr);
+// the layout (NULL: none, format 0) for n streams of w x h on `device`, its offsets uploaded
+int make_yuv_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_yuv_layout *layout, h263mi_batch::YuvLayout &out);
 // h263mi_rgba_resize_extent for n streams
 int rgba_resize_extent(uint32_t n_streams, const h263mi_rgba_resize *r, uint64_t *bytes);
 // the layout that a resize of a w x h picture is by definition (full size, or 1/2 or 1/4 of sizes that 2 or 4 divide), into

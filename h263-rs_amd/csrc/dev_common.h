@@ -187,6 +187,17 @@ struct PostArgs {
     uint32_t rgba_pitch;         // bytes from one output row to the next (a multiple of 4; (H'-1) * pitch + 4W' < 2^32)
 };
 
+// Plane layout of the YUV instantiations (h263mi_yuv_layout), a kernel argument of their own so that the default kernels'
+// arguments stay as they are: the filtered planes go to PostArgs::planes_out in this shape and no RGBA is written.  Luma rows
+// pitch_y bytes apart, chroma rows pitch_c; picture p's planes at planes_out + offsets[3 p + 0 / 1 / 2] (Y, Cb or CbCr, Cr).
+enum : uint32_t { YUV_OUT_I420 = 1u, YUV_OUT_NV12 = 2u };
+struct YuvOut {
+    uint32_t format;             // YUV_OUT_I420 or YUV_OUT_NV12 (0: none; the launchers refuse it)
+    uint32_t wide;               // 1: both pitches, every offset and planes_out are multiples of 4: interior tiles, 16-byte stores
+    uint32_t pitch_y, pitch_c;
+    const uint64_t *offsets;     // DEVICE array, 3 per picture
+};
+
 // ---------------------------------------------------------------------------
 // small integer helpers
 // ---------------------------------------------------------------------------

@@ -37,6 +37,12 @@ hipError_t launch_recon(const ReconArgs &args, hipStream_t stream, const uint32_
 // next reads the planes it wrote last -- the ones still in the infinity cache -- first (2 % on a 64-stream batch).
 hipError_t launch_frame(const ReconArgs &rargs, const PostArgs &pargs, hipStream_t stream, bool descending, const uint32_t *words = nullptr);
 hipError_t launch_post(const PostArgs &args, hipStream_t stream, const uint32_t *words = nullptr);
+// The YUV instantiations (k_post_yuv, k_frame_yuv): the post-processing writes the filtered planes to args.planes_out in the
+// shape `yuv` (h263mi_yuv_layout) and no RGBA.  Declared weak for the same reason as launch_rgba_resize below; the batch
+// refuses to render planes in a layout without them.
+hipError_t launch_post_yuv(const PostArgs &args, const YuvOut &yuv, hipStream_t stream, const uint32_t *words = nullptr) __attribute__((weak));
+hipError_t launch_frame_yuv(const ReconArgs &rargs, const PostArgs &pargs, const YuvOut &yuv, hipStream_t stream, bool descending,
+                            const uint32_t *words = nullptr) __attribute__((weak));
 // k_rgba_resize over args.n_pictures pictures (resize_kernel.inl; bands and chunk are set here).  Declared weak: the host
 // objects are also linked, in the CPU suite's ThreadSanitizer build (tests/tsan), against a stub runtime that has no resize
 // launcher.  The library always defines it (kernels.hip); h263mi_batch::launch_resize refuses to run without it.

@@ -457,8 +457,8 @@ hipError_t launch_recon(const ReconArgs &args, hipStream_t stream, const uint32_
 // neighbouring tiles at any moment: the cache lines that the 4-pixel tile offset makes two tiles
 // share are then fetched once per L2 instead of once per XCD.
 // ---------------------------------------------------------------------------------------
-template <bool FETCH_AHEAD, bool STREAM_RGBA, bool INTERIOR, int SCALE>
-__device__ __forceinline__ void post_strip(const PostArgs &a, PostStrip &s, PostFetch &pf, int lane, int sx, int sy, int pic)
+template <bool FETCH_AHEAD, bool STREAM_RGBA, bool INTERIOR, int SCALE, int YUV>
+__device__ __forceinline__ void post_strip(const PostArgs &a, PostStrip &s, PostFetch &pf, int lane, int sx, int sy, int pic, const YuvOut &yo)
 {
     // `ln`: the lane index behind an opaque asm, re-derived per strip so that lane-only expressions (LDS
     // offsets, column indices, ...) are recomputed where used instead of being kept in registers across
@@ -489,18 +489,18 @@ __device__ __forceinline__ void post_strip(const PostArgs &a, PostStrip &s, Post
 #if H263MI_STOP_POST == 3
     return;
 #endif
-    post_phase_store<STREAM_RGBA, INTERIOR, SCALE>(a, s, ln, sx, sy, pic);
+    post_phase_store<STREAM_RGBA, INTERIOR, SCALE, YUV>(a, s, ln, sx, sy, pic, yo);
     ISA_MARK2(INTERIOR, "interior_", "edge_", "store_end");
 }
 
 // Two strips of a tile.  FETCH_AHEAD: queue the loads of the strips two further down right after each
 // commit, so that they are in flight while this pair is filtered and stored.
-template <bool FETCH_AHEAD, bool STREAM_RGBA, bool INTERIOR, int SCALE>
+template <bool FETCH_AHEAD, bool STREAM_RGBA, bool INTERIOR, int SCALE, int YUV>
 __device__ __forceinline__ void post_strip_pair(const PostArgs &a, PostStrip &s, PostFetch &pf0, PostFetch &pf1, int lane,
-                                                int sx, int sy, int pic)
+                                                int sx, int sy, int pic, const YuvOut &yo)
 {
-    post_strip<FETCH_AHEAD, STREAM_RGBA, INTERIOR, SCALE>(a, s, pf0, lane, sx, sy, pic);
-    post_strip<FETCH_AHEAD, STREAM_RGBA, INTERIOR, SCALE>(a, s, pf1, lane, sx, sy + 1, pic);
+    post_strip<FETCH_AHEAD, STREAM_RGBA, INTERIOR, SCALE, YUV>(a, s, pf0, lane, sx, sy, pic, yo);
+    post_strip<FETCH_AHEAD, STREAM_RGBA, INTERIOR, SCALE, YUV>(a, s, pf1, lane, sx, sy + 1, pic, yo);
 }
 
 // One wave's share of the post-processing: the 128x32 tile (sx, ty) of picture `pic` = 4 strips.
@@ -509,8 +509,8 @@ __device__ __forceinline__ void post_strip_pair(const PostArgs &a, PostStrip &s,
 // rows to store), which keeps the code straight-line.  INTERIOR (post_tile_is_interior, 82 % of the tiles of a 1080p
 // picture): no bounds handling at all and a fixed number of vector memory operations per strip, so that every wait is
 // an exact s_waitcnt vmcnt(N) that leaves the younger loads and stores in flight.
-template <bool STREAM_RGBA, bool INTERIOR, int SCALE>
-__device__ __forceinline__ void post_tile(const PostArgs &a, PostStrip &s, int lane, int sx, int ty, int pic)
+template <bool STREAM_RGBA, bool INTERIOR, int SCALE, int YUV>
+__device__ __forceinline__ void post_tile(const PostArgs &a, PostStrip &s, int lane, int sx, int ty, int pic, const YuvOut &yo)
 {
     const int sy0 = ty * POST_STRIPS;
     ISA_MARK2(INTERIOR, "interior_", "edge_", "tile_begin");
@@ -520,13 +520,16 @@ __device__ __forceinline__ void post_tile(const PostArgs &a, PostStrip &s, int l
     PostFetch pf0, pf1;
     post_phase_fetch<INTERIOR>(a, pf0, lane, sx, sy0, pic);
     post_phase_fetch<INTERIOR>(a, pf1, lane, sx, sy0 + 1, pic);
-    post_strip_pair<true, STREAM_RGBA, INTERIOR, SCALE>(a, s, pf0, pf1, lane, sx, sy0, pic);          // strips 0,1; queues the loads of 2,3
-    post_strip_pair<false, STREAM_RGBA, INTERIOR, SCALE>(a, s, pf0, pf1, lane, sx, sy0 + 2, pic);     // strips 2,3
+    post_strip_pair<true, STREAM_RGBA, INTERIOR, SCALE, YUV>(a, s, pf0, pf1, lane, sx, sy0, pic, yo);          // strips 0,1; queues the loads of 2,3
+    post_strip_pair<false, STREAM_RGBA, INTERIOR, SCALE, YUV>(a, s, pf0, pf1, lane, sx, sy0 + 2, pic, yo);     // strips 2,3
 }
 
 // SCALE: -1 = the default kernels (today's output), 0..2 = the LAYOUT instantiations (post_phase_store)
-template <bool STREAM_RGBA, int SCALE = -1>
-__device__ __forceinline__ void post_wave(const PostArgs &a0, PostStrip &s, int lane, int sx, int ty, int pic, ScalarPtr32 kernarg_words)
+// YUV: 0, or YUV_OUT_I420 / YUV_OUT_NV12 = the YUV instantiations: the filtered planes in the shape of h263mi_yuv_layout and no
+// RGBA; their tiles are interior by where they lie alone (post_tile_is_interior_yuv)
+template <bool STREAM_RGBA, int SCALE = -1, int YUV = 0>
+__device__ __forceinline__ void post_wave(const PostArgs &a0, PostStrip &s, int lane, int sx, int ty, int pic, ScalarPtr32 kernarg_words,
+                                          const YuvOut &yo = YuvOut())
 {
     if (ty >= (int)a0.tiles_y) return;
 #if H263MI_STOP_POST == 9
@@ -540,14 +543,15 @@ __device__ __forceinline__ void post_wave(const PostArgs &a0, PostStrip &s, int 
         a.strength = (st >> STREAM_STRENGTH_SHIFT) & STREAM_STRENGTH_MASK;      // this picture's own (deblock.rs:5-8)
         // per-stream output buffers: the phases address picture `pic` at a.rgba + pic * w*h*4 -- hand them the base that
         // puts it at its own pointer (uniform: two scalar loads)
-        if (a0.rgba_ptrs) a.rgba = a0.rgba_ptrs[pic] - (SCALE < 0 ? (size_t)pic * a0.L.width * a0.L.height * 4u : (size_t)pic * post_out_picture_bytes<SCALE>(a0));
+        if (!YUV && a0.rgba_ptrs) a.rgba = a0.rgba_ptrs[pic] - (SCALE < 0 ? (size_t)pic * a0.L.width * a0.L.height * 4u : (size_t)pic * post_out_picture_bytes<SCALE>(a0));
     }
-    if (post_tile_is_interior(a, sx, ty)) post_tile<STREAM_RGBA, true, SCALE>(a, s, lane, sx, ty, pic);       // wave-uniform
-    else post_tile<STREAM_RGBA, false, SCALE>(a, s, lane, sx, ty, pic);
+    if (YUV ? post_tile_is_interior_yuv(a, yo, sx, ty) : post_tile_is_interior(a, sx, ty))                         // wave-uniform
+        post_tile<STREAM_RGBA, true, SCALE, YUV>(a, s, lane, sx, ty, pic, yo);
+    else post_tile<STREAM_RGBA, false, SCALE, YUV>(a, s, lane, sx, ty, pic, yo);
 }
 
-template <int SCALE>
-__device__ __forceinline__ void post_kernel(const PostArgs &a, PostStrip *strips)      // k_post, k_post_layout
+template <int SCALE, int YUV = 0>
+__device__ __forceinline__ void post_kernel(const PostArgs &a, PostStrip *strips, const YuvOut &yo = YuvOut())      // k_post, k_post_layout, k_post_yuv
 {
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));    // wave index: scalar
     // one wave = one 128x32 tile = 4 strips; a workgroup = 4 vertically adjacent tiles (a 128x128 block), and
@@ -568,7 +572,7 @@ __device__ __forceinline__ void post_kernel(const PostArgs &a, PostStrip *strips
     const int pic = (int)blockIdx.y;
     const uint32_t gy = div_tiles_x(wg, a.tiles_x, a.inv_tiles_x);
     const int sx = (int)(wg - gy * a.tiles_x + a.wrap), ty = (int)gy * POST_GROUP + gw;      // (wrap: the first tile column is 1)
-    post_wave<false, SCALE>(a, strips[wave], lane, sx, ty, pic, kernarg_stream_words());
+    post_wave<false, SCALE, YUV>(a, strips[wave], lane, sx, ty, pic, kernarg_stream_words(), yo);
 }
 
 __global__ __launch_bounds__(POST_THREADS) void k_post(StreamWords, PostArgs a)
@@ -583,6 +587,14 @@ __global__ __launch_bounds__(POST_THREADS) void k_post_layout(StreamWords, PostA
 {
     __shared__ __attribute__((aligned(16))) PostStrip strips[POST_WAVES];
     post_kernel<SCALE>(a, strips);
+}
+
+// the planes alone, in the shape of h263mi_yuv_layout (yo.format = FMT): no conversion, no RGBA store
+template <int FMT>
+__global__ __launch_bounds__(POST_THREADS) void k_post_yuv(StreamWords, PostArgs a, YuvOut yo)
+{
+    __shared__ __attribute__((aligned(16))) PostStrip strips[POST_WAVES];
+    post_kernel<-1, FMT>(a, strips, yo);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -604,8 +616,9 @@ union FrameLds {
 #endif
 };
 
-template <int SCALE>
-__device__ __forceinline__ void frame_kernel(const ReconArgs &ra, const PostArgs &pa, const FrameGeom &fg, FrameLds &lds)   // k_frame, k_frame_layout
+template <int SCALE, int YUV = 0>
+__device__ __forceinline__ void frame_kernel(const ReconArgs &ra, const PostArgs &pa, const FrameGeom &fg, FrameLds &lds,   // k_frame, k_frame_layout,
+                                             const YuvOut &yo = YuvOut())                                                  // k_frame_yuv
 {
     const int lane = threadIdx.x & 63;
     const uint32_t per_group = fg.recon_per_group + fg.post_per_group;
@@ -654,9 +667,9 @@ __device__ __forceinline__ void frame_kernel(const ReconArgs &ra, const PostArgs
     } else {
         if (H263MI_PRIO_POST) __builtin_amdgcn_s_setprio(H263MI_PRIO_POST);
 #if defined(H263MI_EXP_PLAIN_RGBA)
-        post_wave<false, SCALE>(pa, lds.p, lane, (int)(r - fg.recon_per_group + pa.wrap), (int)group, pic, kernarg_stream_words());
+        post_wave<false, SCALE, YUV>(pa, lds.p, lane, (int)(r - fg.recon_per_group + pa.wrap), (int)group, pic, kernarg_stream_words(), yo);
 #else
-        post_wave<true, SCALE>(pa, lds.p, lane, (int)(r - fg.recon_per_group + pa.wrap), (int)group, pic, kernarg_stream_words());
+        post_wave<true, SCALE, YUV>(pa, lds.p, lane, (int)(r - fg.recon_per_group + pa.wrap), (int)group, pic, kernarg_stream_words(), yo);
 #endif
     }
 }
@@ -675,7 +688,17 @@ __global__ __launch_bounds__(64) void k_frame_layout(StreamWords, ReconArgs ra, 
     frame_kernel<SCALE>(ra, pa, fg, lds);
 }
 
-hipError_t launch_frame(const ReconArgs &rargs, const PostArgs &pargs, hipStream_t stream, bool descending, const uint32_t *words)
+// the same with the YUV instantiation of the post-processing half (yo.format = FMT), as k_post_yuv
+template <int FMT>
+__global__ __launch_bounds__(64) void k_frame_yuv(StreamWords, ReconArgs ra, PostArgs pa, FrameGeom fg, YuvOut yo)
+{
+    __shared__ __attribute__((aligned(16))) FrameLds lds;
+    frame_kernel<-1, FMT>(ra, pa, fg, lds, yo);
+}
+
+// yuv != nullptr: the YUV instantiation (launch_frame_yuv)
+static hipError_t launch_frame_any(const ReconArgs &rargs, const PostArgs &pargs, hipStream_t stream, bool descending, const uint32_t *words,
+                                   const YuvOut *yuv)
 {
     if (!rargs.n_pictures) return hipSuccess;
     if (rargs.n_pictures != pargs.n_pictures || rargs.n_pictures > 65535) return hipErrorInvalidValue;
@@ -698,12 +721,27 @@ hipError_t launch_frame(const ReconArgs &rargs, const PostArgs &pargs, hipStream
     ra.words_inline = pa.words_inline = inline_words(words, rargs.n_pictures, sw) ? 1u : 0u;
     const uint32_t chunk = (fg.groups * per_group + fg.bands - 1) / fg.bands, side_by_side = 8 / fg.bands;
     const dim3 grid(chunk * 8, (rargs.n_pictures + side_by_side - 1) / side_by_side);
-    if (!pa.rgba_pitch) hipLaunchKernelGGL(k_frame, grid, dim3(64), 0, stream, sw, ra, pa, fg);
+    // (a YUV layout: planes only -- the caller renders RGBA it wants beside them in a launch of its own)
+    if (yuv && yuv->format == YUV_OUT_I420) hipLaunchKernelGGL(k_frame_yuv<(int)YUV_OUT_I420>, grid, dim3(64), 0, stream, sw, ra, pa, fg, *yuv);
+    else if (yuv && yuv->format == YUV_OUT_NV12) hipLaunchKernelGGL(k_frame_yuv<(int)YUV_OUT_NV12>, grid, dim3(64), 0, stream, sw, ra, pa, fg, *yuv);
+    else if (yuv) return hipErrorInvalidValue;
+    else if (!pa.rgba_pitch) hipLaunchKernelGGL(k_frame, grid, dim3(64), 0, stream, sw, ra, pa, fg);
     else if (pa.rgba_scale == 0) hipLaunchKernelGGL(k_frame_layout<0>, grid, dim3(64), 0, stream, sw, ra, pa, fg);
     else if (pa.rgba_scale == 1) hipLaunchKernelGGL(k_frame_layout<1>, grid, dim3(64), 0, stream, sw, ra, pa, fg);
     else if (pa.rgba_scale == 2) hipLaunchKernelGGL(k_frame_layout<2>, grid, dim3(64), 0, stream, sw, ra, pa, fg);
     else return hipErrorInvalidValue;
     return hipGetLastError();
+}
+
+hipError_t launch_frame(const ReconArgs &rargs, const PostArgs &pargs, hipStream_t stream, bool descending, const uint32_t *words)
+{
+    return launch_frame_any(rargs, pargs, stream, descending, words, nullptr);
+}
+
+hipError_t launch_frame_yuv(const ReconArgs &rargs, const PostArgs &pargs, const YuvOut &yuv, hipStream_t stream, bool descending,
+                            const uint32_t *words)
+{
+    return launch_frame_any(rargs, pargs, stream, descending, words, &yuv);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -733,7 +771,7 @@ hipError_t launch_rgba_resize(const ResizeArgs &args, hipStream_t stream)
     return hipGetLastError();
 }
 
-hipError_t launch_post(const PostArgs &args, hipStream_t stream, const uint32_t *words)
+static hipError_t launch_post_any(const PostArgs &args, hipStream_t stream, const uint32_t *words, const YuvOut *yuv)
 {
     if (!args.n_pictures) return hipSuccess;
     if (args.n_pictures > 65535 || args.tiles_x * args.tiles_y >= (1u << 20)) return hipErrorInvalidValue;
@@ -745,12 +783,22 @@ hipError_t launch_post(const PostArgs &args, hipStream_t stream, const uint32_t 
     const uint32_t groups_y = (args.tiles_y + POST_GROUP - 1) / POST_GROUP;
     const uint32_t upp = args.tiles_x * groups_y * (POST_GROUP / POST_WAVES), chunk = (upp + 7) / 8;
     const dim3 grid(chunk * 8, args.n_pictures);
-    if (!a.rgba_pitch) hipLaunchKernelGGL(k_post, grid, dim3(POST_THREADS), 0, stream, sw, a);
+    if (yuv && yuv->format == YUV_OUT_I420) hipLaunchKernelGGL(k_post_yuv<(int)YUV_OUT_I420>, grid, dim3(POST_THREADS), 0, stream, sw, a, *yuv);
+    else if (yuv && yuv->format == YUV_OUT_NV12) hipLaunchKernelGGL(k_post_yuv<(int)YUV_OUT_NV12>, grid, dim3(POST_THREADS), 0, stream, sw, a, *yuv);
+    else if (yuv) return hipErrorInvalidValue;
+    else if (!a.rgba_pitch) hipLaunchKernelGGL(k_post, grid, dim3(POST_THREADS), 0, stream, sw, a);
     else if (a.rgba_scale == 0) hipLaunchKernelGGL(k_post_layout<0>, grid, dim3(POST_THREADS), 0, stream, sw, a);
     else if (a.rgba_scale == 1) hipLaunchKernelGGL(k_post_layout<1>, grid, dim3(POST_THREADS), 0, stream, sw, a);
     else if (a.rgba_scale == 2) hipLaunchKernelGGL(k_post_layout<2>, grid, dim3(POST_THREADS), 0, stream, sw, a);
     else return hipErrorInvalidValue;
     return hipGetLastError();
+}
+
+hipError_t launch_post(const PostArgs &args, hipStream_t stream, const uint32_t *words) { return launch_post_any(args, stream, words, nullptr); }
+
+hipError_t launch_post_yuv(const PostArgs &args, const YuvOut &yuv, hipStream_t stream, const uint32_t *words)
+{
+    return launch_post_any(args, stream, words, &yuv);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -237,6 +237,16 @@ H263_DEV uint32_t pack2_u8(int lo, int hi)                     // (lo & 0xff) | 
 // and, the point of the exercise, become STRAIGHT-LINE code with a fixed number of vector memory operations per strip
 // (2 loads, 4 stores), so that the compiler can leave exactly the younger loads and stores in flight at each wait
 // (s_waitcnt vmcnt(N)) instead of draining the queue.  Wave-uniform, decided once per wave.
+// The geometric conditions alone: where the tile lies (kept beside post_tile_is_interior, which the default kernels compile
+// exactly as before).
+H263_HD bool post_tile_is_interior_geom(const PostArgs &a, int sx, int ty)
+{
+    const int xl = sx * POST_TW - POST_OX, yl = ty * POST_STRIPS * POST_SH - 4;
+    const int w8 = (int)(a.L.width / 8) * 8, h8 = (int)(a.L.height / 8) * 8;
+    const int cw8 = (int)(a.L.cwidth / 8) * 8, ch8 = (int)(a.L.cheight / 8) * 8;
+    return xl >= 0 && yl >= 0 && xl + POST_TW <= w8 && xl / 2 + POST_CW <= cw8 && yl + POST_STRIPS * POST_SH <= h8 &&
+           yl / 2 + POST_STRIPS * POST_CSH <= ch8;
+}
 H263_HD bool post_tile_is_interior(const PostArgs &a, int sx, int ty)
 {
     const int xl = sx * POST_TW - POST_OX, yl = ty * POST_STRIPS * POST_SH - 4;
@@ -244,6 +254,12 @@ H263_HD bool post_tile_is_interior(const PostArgs &a, int sx, int ty)
     const int cw8 = (int)(a.L.cwidth / 8) * 8, ch8 = (int)(a.L.cheight / 8) * 8;
     return xl >= 0 && yl >= 0 && xl + POST_TW <= w8 && xl / 2 + POST_CW <= cw8 && yl + POST_STRIPS * POST_SH <= h8 &&
            yl / 2 + POST_STRIPS * POST_CSH <= ch8 && a.rgba != nullptr && a.planes_out == nullptr && !a.luma_only;
+}
+// The YUV instantiations (planes only, in the shape of h263mi_yuv_layout) ask for the geometry alone, and for a layout whose
+// rows their wide stores can address: pitches, offsets and the buffer itself multiples of 4.
+H263_HD bool post_tile_is_interior_yuv(const PostArgs &a, const YuvOut &yo, int sx, int ty)
+{
+    return yo.wide && post_tile_is_interior_geom(a, sx, ty);
 }
 
 // ---- phase 0: strip -> registers -> LDS -----------------------------------------------------
@@ -672,15 +688,122 @@ H263_DEV void post_store_scaled(const PostArgs &a, const PostStrip &s, uint8_t *
     }
 }
 
+// ---- phase 3 of the YUV instantiations: the filtered planes in the shape of h263mi_yuv_layout, no conversion ---------------
+// Cb and Cr bytes of four chroma columns -> the eight bytes Cb0 Cr0 Cb1 Cr1 | Cb2 Cr2 Cb3 Cr3 of an NV12 row
+H263_DEV uint32_t interleave_lo(uint32_t cb, uint32_t cr)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_perm(cr, cb, 0x05010400u);
+#else
+    return (cb & 0xffu) | ((cr & 0xffu) << 8) | ((cb & 0xff00u) << 8) | ((cr & 0xff00u) << 16);
+#endif
+}
+H263_DEV uint32_t interleave_hi(uint32_t cb, uint32_t cr)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_perm(cr, cb, 0x07030602u);
+#else
+    return ((cb >> 16) & 0xffu) | (((cr >> 16) & 0xffu) << 8) | ((cb >> 24) << 16) | ((cr >> 24) << 24);
+#endif
+}
+// 4 bytes to an address that is a multiple of 2 (an I420 chroma row at the strip's origin, 2 mod 4)
+template <bool STREAM>
+H263_DEV void store4_align2(uint8_t *dst, uint32_t a)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef uint32_t __attribute__((aligned(2))) u32_a2;
+    if (STREAM) __builtin_nontemporal_store(a, reinterpret_cast<u32_a2 *>(dst));
+    else *reinterpret_cast<u32_a2 *>(dst) = a;
+#else
+    memcpy(dst, &a, 4);
+#endif
+}
+
+// where picture `pic`'s planes start: wave-uniform 64-bit bases (three scalar loads), every lane offset below is 32-bit
+// (a plane's span is < 2^32: h263mi_yuv_layout_extent)
+struct YuvPlanes {
+    uint8_t *y, *c0, *c1;       // Y; Cb or the CbCr plane; Cr (NV12: unused)
+};
+H263_HD YuvPlanes post_yuv_planes(const PostArgs &a, const YuvOut &yo, int pic)
+{
+    const uint64_t *o = yo.offsets + 3 * (size_t)pic;
+    YuvPlanes p;
+    p.y = a.planes_out + o[0];
+    p.c0 = a.planes_out + o[1];
+    p.c1 = a.planes_out + o[2];
+    return p;
+}
+
+// FMT: YUV_OUT_I420 or YUV_OUT_NV12.  INTERIOR (post_tile_is_interior_yuv): straight-line, the strip's 1 024 luma bytes as
+// one 16-byte store per lane (8 lanes = the 128 bytes of a row), its 2 x 256 chroma bytes as one 8-byte store of interleaved
+// pairs per lane (NV12: 16 lanes = the 128 bytes of a CbCr row, 4-byte aligned because the strip origin is 4 mod 8) or as two
+// 4-byte stores per lane, Cb then Cr (I420: 16 lanes = the 64 bytes of a row, 2-byte aligned: the chroma origin is 2 mod 4).
+// Edge tiles: every byte tested against the picture, dword stores for whole luma groups of a wide layout, bytes otherwise.
+template <bool STREAM, bool INTERIOR, int FMT>
+H263_DEV void post_store_yuv(const PostArgs &a, const YuvOut &yo, const PostStrip &s, int lane, int xl, int yl, int pic)
+{
+    const YuvPlanes P = post_yuv_planes(a, yo, pic);
+    const uint32_t pitch_y = yo.pitch_y, pitch_c = yo.pitch_c;
+    if (INTERIOR) {
+        {
+            const int row = lane >> 3, col = (lane & 7) * 16;
+            const uint4 v = *reinterpret_cast<const uint4 *>(&s.y[row * POST_TW + col]);
+            store16_align4<STREAM>(P.y + ((uint32_t)(yl + row) * pitch_y + (uint32_t)(xl + col)), v.x, v.y, v.z, v.w);
+        }
+        const int row = lane >> 4, g = lane & 15;              // chroma row of the strip, group of 4 chroma columns
+        const uint32_t cb = *reinterpret_cast<const uint32_t *>(&s.c[0][row * POST_CW + 4 * g]);
+        const uint32_t cr = *reinterpret_cast<const uint32_t *>(&s.c[1][row * POST_CW + 4 * g]);
+        const uint32_t rowoff = (uint32_t)(yl / 2 + row) * pitch_c;
+        if (FMT == (int)YUV_OUT_NV12) {
+            store8_align4<STREAM>(P.c0 + (rowoff + (uint32_t)(xl + 8 * g)), interleave_lo(cb, cr), interleave_hi(cb, cr));
+        } else {
+            store4_align2<STREAM>(P.c0 + (rowoff + (uint32_t)(xl / 2 + 4 * g)), cb);
+            store4_align2<STREAM>(P.c1 + (rowoff + (uint32_t)(xl / 2 + 4 * g)), cr);
+        }
+        return;
+    }
+    const int w = (int)a.L.width, h = (int)a.L.height, cw = (int)a.L.cwidth, ch = (int)a.L.cheight;
+    for (int it = 0; it < 4; it++) {
+        const int item = it * 64 + lane, row = item >> 5, g = item & 31;
+        const int gy = yl + row, gx = post_wrap_x(a, xl + 4 * g);
+        if (gy < 0 || gy >= h || gx < 0 || gx >= w) continue;
+        const uint32_t off = (uint32_t)gy * pitch_y + (uint32_t)gx;
+        // (gx is a multiple of 4: the strip origin is, and the wrap moves a group by the width, a multiple of 4 where it applies)
+        if (yo.wide && gx + 4 <= w) store4<STREAM>(P.y + off, *reinterpret_cast<const uint32_t *>(&s.y[row * POST_TW + 4 * g]));
+        else
+            for (int k = 0; k < 4 && gx + k < w; k++) P.y[off + (uint32_t)k] = s.y[row * POST_TW + 4 * g + k];
+    }
+    for (int plane = 0; plane < 2; plane++) {
+        const int row = lane >> 4, g = lane & 15;
+        const int gy = yl / 2 + row, gx = xl / 2 + 4 * g;
+        if (gy < 0 || gy >= ch) continue;
+        uint8_t *o = (FMT == (int)YUV_OUT_NV12 || plane == 0) ? P.c0 : P.c1;
+        const uint32_t rowoff = (uint32_t)gy * pitch_c;
+        // the chroma strip origin is 2 mod 4: a group of 4 may straddle column 0 (and the wrap)
+        for (int k = 0; k < 4; k++) {
+            const int cx = post_wrap_cx(a, gx + k);
+            if (cx < 0 || cx >= cw) continue;
+            const uint32_t off = FMT == (int)YUV_OUT_NV12 ? rowoff + 2u * (uint32_t)cx + (uint32_t)plane : rowoff + (uint32_t)cx;
+            o[off] = s.c[plane][row * POST_CW + 4 * g + k];
+        }
+    }
+}
+
 // STREAM_RGBA: the RGBA stores are non-temporal.  k_frame sets it: the 8.3 MB of RGBA per picture then no longer push
 // the planes that the reconstruction half of the same launch (and the next one) reads out of the L2 / infinity cache --
 // 10 % on a frame index (profiles/README.md).  k_post on its own keeps plain stores: alone, it is 10 % faster with them.
 // SCALE: -1 (the default kernels) = today's output, w x h tightly packed; 0, 1, 2 = the LAYOUT instantiations: rows
 // a.rgba_pitch bytes apart, boxes of 2^SCALE x 2^SCALE pixels averaged (post_store_scaled).
-template <bool STREAM_RGBA, bool INTERIOR = false, int SCALE = -1>
-H263_DEV void post_phase_store(const PostArgs &a, PostStrip &s, int lane, int sx, int sy, int pic)
+// YUV: 0, or the plane format of the YUV instantiations (YUV_OUT_*): planes in the shape of h263mi_yuv_layout and nothing else
+// (post_store_yuv; their stores are non-temporal where the RGBA stores would be).
+template <bool STREAM_RGBA, bool INTERIOR = false, int SCALE = -1, int YUV = 0>
+H263_DEV void post_phase_store(const PostArgs &a, PostStrip &s, int lane, int sx, int sy, int pic, const YuvOut &yo = YuvOut())
 {
     const int xl = sx * POST_TW - POST_OX, yl = sy * POST_SH - 4;
+    if (YUV) {
+        post_store_yuv<STREAM_RGBA, INTERIOR, YUV>(a, yo, s, lane, xl, yl, pic);
+        return;
+    }
     const int w = (int)a.L.width, h = (int)a.L.height, cw = (int)a.L.cwidth, ch = (int)a.L.cheight;
 
     if (SCALE > 0) {

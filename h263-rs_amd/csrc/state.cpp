@@ -18,11 +18,19 @@ struct h263mi_state {
     bits::ParserContext parser_ctx;   // header + format of the last picture decoded from a bitstream (state.rs:143-167)
     bits::ParsedPicture parsed;       // parse results of h263mi_decode_next_picture: kept, so that its buffers are reused
     uint8_t *d_rgba = nullptr;  size_t cap_rgba = 0;   // rendering scratch of h263mi_render_rgba[_layout]
+    // h263mi_render_yuv: the device-side shape it renders in (per format: 256-byte pitches, the wide-store path for every
+    // picture size), kept for as long as the picture size stays, and the scratch that holds the planes
+    struct YuvScratch {
+        h263mi_batch::YuvLayout shape;
+        uint32_t w = 0, h = 0;
+    } yuv[2];
+    uint8_t *d_yuv = nullptr;  size_t cap_yuv = 0;
     ~h263mi_state()
     {
         DeviceGuard g(cfg.device_id);
         if (b) (void)hipStreamSynchronize(b->stream);
         if (d_rgba) (void)hipFree(d_rgba);
+        if (d_yuv) (void)hipFree(d_yuv);
         delete b;
     }
 };
@@ -337,6 +345,58 @@ int h263mi_render_rgba_resize(const h263mi_state *cs, uint8_t strength, const h2
     RC_TRY(rc);
     if (pitch == row) HIP_TRY(hipMemcpyAsync(rgba, s->d_rgba, bytes, hipMemcpyDeviceToHost, b->stream));
     else HIP_TRY(hipMemcpy2DAsync(rgba, pitch, s->d_rgba, row, row, r->out_height, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    return H263MI_OK;
+}
+
+int h263mi_render_yuv(const h263mi_state *cs, uint8_t strength, const h263mi_yuv_layout *layout, uint8_t *out)
+{
+    h263mi_state *s = const_cast<h263mi_state *>(cs);
+    if (!s || !out) return H263MI_ERR_INVALID_ARGUMENT;
+    if (!s->has_last || !s->b) return H263MI_ERR_NO_PICTURE;
+    h263mi_batch *b = s->b;
+    const uint32_t w = b->L.width, h = b->L.height, cw = b->L.cwidth, ch = b->L.cheight;
+    // the caller's shape: where its planes lie in `out`
+    h263mi_batch::YuvLayout host;
+    std::vector<uint64_t> off;
+    RC_TRY(yuv_layout_extent(1, w, h, layout, nullptr, &host, &off));
+    h263mi_batch::Strengths st;
+    RC_TRY(state_strength(s, strength, st));
+    DeviceGuard g(s->cfg.device_id);
+    // rendered on the device at pitches of 256 bytes, planes back to back (every layout of that kind takes the wide stores),
+    // then each plane copied out row by row into the caller's rectangle: nothing else of `out` is touched
+    const bool nv12 = host.format == YUV_OUT_NV12;
+    const uint32_t row_c = nv12 ? 2 * cw : cw;
+    h263mi_state::YuvScratch &sc = s->yuv[nv12 ? 1 : 0];
+    if (!sc.shape.on() || sc.w != w || sc.h != h) {
+        h263mi_yuv_layout dev{};
+        dev.format = nv12 ? H263MI_YUV_NV12 : H263MI_YUV_I420;
+        dev.pitch_y = ((uint64_t)w + 255) / 256 * 256;
+        dev.pitch_c = ((uint64_t)row_c + 255) / 256 * 256;
+        sc.shape = h263mi_batch::YuvLayout();
+        RC_TRY(make_yuv_shape(s->cfg.device_id, 1, w, h, &dev, sc.shape));
+        sc.w = w;
+        sc.h = h;
+    }
+    const size_t bytes = (size_t)sc.shape.bytes;
+    if (bytes > s->cap_yuv) {
+        if (s->d_yuv) (void)hipFree(s->d_yuv);
+        s->d_yuv = nullptr; s->cap_yuv = 0;
+        HIP_TRY(hipMalloc((void **)&s->d_yuv, bytes));
+        s->cap_yuv = bytes;
+    }
+    h263mi_batch::YuvLayout saved = std::move(b->yuv);
+    b->yuv = sc.shape;
+    const int rc = b->render(st, nullptr, s->d_yuv);
+    b->yuv = std::move(saved);
+    RC_TRY(rc);
+    // (pitch_y, pitch_c of the device shape; default placement: Y at 0, the chroma planes behind it)
+    const size_t dpy = ((size_t)w + 255) / 256 * 256, dpc = ((size_t)row_c + 255) / 256 * 256;
+    const uint8_t *d_c0 = s->d_yuv + (size_t)h * dpy;
+    HIP_TRY(hipMemcpy2DAsync(out + off[0], h > 1 ? host.pitch_y : w, s->d_yuv, dpy, w, h, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipMemcpy2DAsync(out + off[1], ch > 1 ? host.pitch_c : row_c, d_c0, dpc, row_c, ch, hipMemcpyDeviceToHost, b->stream));
+    if (!nv12)
+        HIP_TRY(hipMemcpy2DAsync(out + off[2], ch > 1 ? host.pitch_c : row_c, d_c0 + (size_t)ch * dpc, dpc, row_c, ch, hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     return H263MI_OK;
 }

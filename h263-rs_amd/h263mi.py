@@ -89,7 +89,10 @@ EXPORTS = [
     "h263mi_rgba_layout_extent", "h263mi_batch_set_rgba_layout", "h263mi_render_rgba_layout",
     # ABI 7, additive: RGBA resized to any W' x H' by area averaging
     "h263mi_rgba_resize_extent", "h263mi_batch_set_rgba_resize", "h263mi_render_rgba_resize", "h263mi_mixed_set_rgba_resize",
+    # ABI 7, additive: deblocked YUV 4:2:0 planes as I420 or NV12 with pitches and per-stream placement
+    "h263mi_yuv_layout_extent", "h263mi_batch_set_yuv_layout", "h263mi_render_yuv",
 ]
+YUV_I420, YUV_NV12 = 0, 1
 STRENGTH_FROM_HEADER = 0xFF
 CFG_OVERLAP_POST, CFG_PIPELINE_POST, CFG_TRUSTED_ARRAYS = 1, 2, 4
 
@@ -179,6 +182,42 @@ def rgba_resize_extent(n_streams, out_width, out_height, row_pitch=0, offsets=No
         resize, keep = make_rgba_resize(out_width, out_height, row_pitch, offsets)
     nb = C.c_uint64()
     _check(lib().h263mi_rgba_resize_extent(n_streams, C.byref(resize), C.byref(nb)), "rgba_resize_extent")
+    del keep
+    return nb.value
+
+
+class YuvLayout(C.Structure):
+    """h263mi_yuv_layout: the deblocked planes as I420 (Y, Cb, Cr) or NV12 (Y, interleaved CbCr), luma rows pitch_y bytes apart,
+    chroma rows pitch_c (0 = tight), stream s's planes at byte offsets_y[s], offsets_cb[s], offsets_cr[s] (all NULL: back to back)."""
+    _fields_ = [("format", C.c_uint8), ("reserved", C.c_uint8 * 7), ("pitch_y", C.c_uint64), ("pitch_c", C.c_uint64),
+                ("offsets_y", C.POINTER(C.c_uint64)), ("offsets_cb", C.POINTER(C.c_uint64)), ("offsets_cr", C.POINTER(C.c_uint64))]
+
+
+def make_yuv_layout(format=YUV_I420, pitch_y=0, pitch_c=0, offsets_y=None, offsets_cb=None, offsets_cr=None):
+    """-> (YuvLayout, the offset arrays it points into: keep them alive with the struct)"""
+    lay = YuvLayout()
+    lay.format = format
+    lay.pitch_y = pitch_y
+    lay.pitch_c = pitch_c
+    keep = []
+    for name, offs in (("offsets_y", offsets_y), ("offsets_cb", offsets_cb), ("offsets_cr", offsets_cr)):
+        if offs is not None:
+            arr = np.ascontiguousarray(offs, dtype=np.uint64)
+            setattr(lay, name, arr.ctypes.data_as(C.POINTER(C.c_uint64)))
+            keep.append(arr)
+    return lay, keep
+
+
+def yuv_layout_extent(n_streams, width, height, format=YUV_I420, pitch_y=0, pitch_c=0, offsets_y=None, offsets_cb=None,
+                      offsets_cr=None, layout=None, default=False):
+    """h263mi_yuv_layout_extent -> bytes d_deblocked must hold; H263Error when the layout is refused.  Needs no device.
+    layout: a YuvLayout to pass as it is (else one is made of the other arguments); default=True: the NULL layout."""
+    keep = None
+    if layout is None and not default:
+        layout, keep = make_yuv_layout(format, pitch_y, pitch_c, offsets_y, offsets_cb, offsets_cr)
+    nb = C.c_uint64()
+    _check(lib().h263mi_yuv_layout_extent(n_streams, width, height, C.byref(layout) if layout is not None else None, C.byref(nb)),
+           "yuv_layout_extent")
     del keep
     return nb.value
 
@@ -319,6 +358,9 @@ def lib():
         L.h263mi_batch_set_rgba_resize.argtypes = [vp, vp]
         L.h263mi_render_rgba_resize.argtypes = [vp, u8, vp, vp]
         L.h263mi_mixed_set_rgba_resize.argtypes = [vp, vp]
+        L.h263mi_yuv_layout_extent.argtypes = [u32, u16, u16, vp, C.POINTER(C.c_uint64)]
+        L.h263mi_batch_set_yuv_layout.argtypes = [vp, vp]
+        L.h263mi_render_yuv.argtypes = [vp, u8, vp, vp]
         L.h263mi_default_parser_threads.restype = u32
         L.h263mi_default_parser_threads.argtypes = [u32, C.POINTER(u32)]
         _lib = L
@@ -514,6 +556,24 @@ class H263State:
     def render_rgba_resize_into(self, strength, out, out_width, out_height, row_pitch=0):
         r, _ = make_rgba_resize(out_width, out_height, row_pitch)
         _check(lib().h263mi_render_rgba_resize(self._h, strength, C.byref(r), _p(out)), "render_rgba_resize")
+        return out
+
+    def render_yuv(self, strength=0, format=YUV_I420, pitch_y=0, pitch_c=0):
+        """h263mi_render_yuv with default placement: the extent's bytes (what lies between rows is zero here)"""
+        v = self._view(lib().h263mi_get_last_picture, "get_last_picture")
+        if v is None:
+            raise H263Error(ERR_NO_PICTURE, "render_yuv")
+        out = np.zeros(yuv_layout_extent(1, v.width, v.height, format, pitch_y, pitch_c), np.uint8)
+        return self.render_yuv_into(strength, out, format, pitch_y, pitch_c)
+
+    def render_yuv_into(self, strength, out, format=YUV_I420, pitch_y=0, pitch_c=0, offsets_y=None, offsets_cb=None,
+                        offsets_cr=None, layout=None):
+        """h263mi_render_yuv into `out` (a uint8 array of at least the layout's extent); bytes outside the planes stay"""
+        keep = None
+        if layout is None:
+            layout, keep = make_yuv_layout(format, pitch_y, pitch_c, offsets_y, offsets_cb, offsets_cr)
+        _check(lib().h263mi_render_yuv(self._h, strength, C.byref(layout), _p(out)), "render_yuv")
+        del keep
         return out
 
     def render_rgba_pinned(self, strength, pinned):
@@ -755,6 +815,18 @@ class Batch:
             return
         lay, keep = make_rgba_layout(scale_log2, row_pitch, offsets)
         _check(lib().h263mi_batch_set_rgba_layout(self._h, C.byref(lay)), "batch_set_rgba_layout")
+        del keep
+
+    def set_yuv_layout(self, format=YUV_I420, pitch_y=0, pitch_c=0, offsets_y=None, offsets_cb=None, offsets_cr=None,
+                       default=False, layout=None):
+        """h263mi_batch_set_yuv_layout: the shape of d_deblocked from now on (default=True: back to tightly packed I420)"""
+        if default:
+            _check(lib().h263mi_batch_set_yuv_layout(self._h, None), "batch_set_yuv_layout")
+            return
+        keep = None
+        if layout is None:
+            layout, keep = make_yuv_layout(format, pitch_y, pitch_c, offsets_y, offsets_cb, offsets_cr)
+        _check(lib().h263mi_batch_set_yuv_layout(self._h, C.byref(layout)), "batch_set_yuv_layout")
         del keep
 
     def set_rgba_resize(self, out_width=0, out_height=0, row_pitch=0, offsets=None, default=False):

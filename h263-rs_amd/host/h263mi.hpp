@@ -160,6 +160,18 @@ public:
         check(h263mi_render_rgba_resize(s_, strength, &r, rgba.data()));
         return rgba;
     }
+    // the deblocked planes of the last picture as I420 or NV12 (h263mi_yuv_layout; nullptr: tightly packed I420), without
+    // going through RGBA: the layout's extent in bytes, the ones outside the planes zero
+    std::vector<uint8_t> render_yuv(uint8_t strength, const h263mi_yuv_layout *layout = nullptr) const
+    {
+        h263mi_frame_view v;
+        check(h263mi_get_last_picture(s_, &v));
+        uint64_t bytes = 0;
+        check(h263mi_yuv_layout_extent(1, v.width, v.height, layout, &bytes));
+        std::vector<uint8_t> out((size_t)bytes);
+        check(h263mi_render_yuv(s_, strength, layout, out.data()));
+        return out;
+    }
 
     // the same straight into page-locked memory of the caller (h263mi_host_alloc / h263mi_host_register): the buffer a
     // renderer reuses for every picture instead of the fresh Vec<u8> of bt601.rs:128; `rgba` holds width * height * 4 bytes

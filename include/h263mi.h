@@ -426,10 +426,52 @@ int h263mi_batch_set_rgba_resize(h263mi_batch *b, const h263mi_rgba_resize *r);
 /* One state, into HOST memory: H' rows of 4*W' bytes at rgba + r * pitch; offsets must be NULL. */
 int h263mi_render_rgba_resize(const h263mi_state *s, uint8_t strength, const h263mi_rgba_resize *r, uint8_t *rgba);
 
+/*
+ * DEBLOCKED YUV 4:2:0 OUTPUT LAYOUT (additive, ABI 7): where the filtered planes go inside d_deblocked.  The planes are always
+ * full size (w x h luma, cw x ch chroma, cw = ceil(w/2), ch = ceil(h/2)); the RGBA layouts and resizes above apply to d_rgba
+ * only and the two shapes are independent.  I420: three planes Y, Cb, Cr.  NV12: a Y plane and one plane of ch rows of cw
+ * interleaved Cb,Cr byte pairs.  Luma rows are pitch_y bytes apart, chroma rows pitch_c.
+ * Default placement (all offset arrays NULL): picture s starts at s * P with P = h*pitch_y + k*ch*pitch_c (k = 2 for I420, 1 for
+ * NV12); Y at 0, Cb (NV12: the CbCr plane) at h*pitch_y, Cr at h*pitch_y + ch*pitch_c.  I420 with both pitches 0 is the tightly
+ * packed Y,Cb,Cr per stream that a batch without a YUV layout writes, byte for byte.
+ * Offset arrays are given all together or not at all: Y and Cb for NV12, all three for I420.
+ */
+#define H263MI_YUV_I420 0   /* Y plane, Cb plane, Cr plane */
+#define H263MI_YUV_NV12 1   /* Y plane, one plane of interleaved Cb,Cr pairs */
+typedef struct h263mi_yuv_layout {
+    uint8_t  format;              /* H263MI_YUV_I420 or H263MI_YUV_NV12 */
+    uint8_t  reserved[7];         /* must be 0 */
+    uint64_t pitch_y;             /* bytes between luma rows, 0 = w */
+    uint64_t pitch_c;             /* bytes between chroma rows, 0 = cw (I420) or 2*cw (NV12) */
+    const uint64_t *offsets_y;    /* HOST arrays of n_streams byte offsets into d_deblocked; copied */
+    const uint64_t *offsets_cb;   /* NV12: the CbCr plane */
+    const uint64_t *offsets_cr;   /* NV12: must be NULL */
+} h263mi_yuv_layout;
+
+/* Pure host function, no HIP call: validates and returns the bytes d_deblocked must hold (layout NULL: n * (w*h + 2*cw*ch)).
+ * H263MI_ERR_INVALID_ARGUMENT: an unknown format; a reserved byte set; a pitch below its row length (w; cw or 2*cw); a plane
+ * span (rows-1) * pitch + row >= 2^32; a row that crosses its pitch boundary (offset mod pitch + row > pitch); offsets_cr given
+ * for NV12; offset arrays given only in part; two planes that share a byte.  The overlap rule: luma planes are rectangles on the
+ * grid of pitch_y, chroma planes on the grid of pitch_c, and no two rectangles of a grid may intersect; the byte span of a luma
+ * plane must not intersect the byte span of a chroma plane unless pitch_y == pitch_c, where all planes share one grid and the
+ * rectangle test decides. */
+int h263mi_yuv_layout_extent(uint32_t n_streams, uint16_t width, uint16_t height, const h263mi_yuv_layout *layout, uint64_t *bytes);
+/* Every later call on this batch that writes d_deblocked follows the layout (h263mi_batch_decode[_ps], _decode_events[_ps],
+ * _render_rgba[_ps], _decode_next_pictures_ex / _ps; a deferred rendering of H263MI_CFG_PIPELINE_POST keeps the shape its request
+ * was made under); NULL = the default (tightly packed I420, as before).  Offsets are copied.  A checked batch holds d_deblocked
+ * to the layout's extent.  d_rgba and d_deblocked may both be given.  Streams with nothing to render are not written, nor is any
+ * byte outside the planes' rectangles.  A layout whose pitches and offsets are all multiples of 4 is written with 16-byte
+ * stores; any other layout is written correctly with narrower ones. */
+int h263mi_batch_set_yuv_layout(h263mi_batch *b, const h263mi_yuv_layout *layout);
+/* One state, into HOST memory: the last picture's planes, deblocked with `strength` (0 = as decoded; H263MI_STRENGTH_FROM_HEADER
+ * as in h263mi_render_rgba), in the shape of `layout` for one stream (NULL: tightly packed I420).  No RGBA is made on the way.
+ * Bytes outside the planes' rectangles are untouched. */
+int h263mi_render_yuv(const h263mi_state *s, uint8_t strength, const h263mi_yuv_layout *layout, uint8_t *out);
+
 /* deblock (strength 0 = off) + BT.601 of every stream's last picture into d_rgba
  * (DEVICE, n_streams * w*h*4 bytes, stream-major); d_deblocked (DEVICE, may be NULL)
  * additionally receives the filtered planes, n_streams * (w*h + 2*cw*ch) bytes as
- * Y,Cb,Cr per stream, tightly packed. */
+ * Y,Cb,Cr per stream, tightly packed -- or in the shape of h263mi_batch_set_yuv_layout. */
 /*
  * The same from HOST records, one picture per stream: the batch counterpart of h263mi_submit_picture for a server
  * whose parser threads fill one record array per stream.  mbs[s] / coeffs[s] hold stream s' macroblocks
