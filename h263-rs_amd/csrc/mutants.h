@@ -8,6 +8,11 @@
 //   -DH263MI_MUTATE_DEQUANT_SATURATION   the dequantiser's saturated values keep their low bits: 2047.9375 instead of 2047
 //   -DH263MI_MUTATE_DEQUANT_WRAP         the dequantiser of wide LEVELs saturates where the reference's i16 product wraps
 //   (the fourth mutant, libh263mi_fma.so, is a compiler flag: -ffp-contract=fast fuses the IDCT's multiplies into its adds)
+// ... and two of the motion compensation (tests/test_gpu_mutation.py with tests/mc_mutation_probe.py):
+//   -DH263MI_MUTATE_BLEND_ROUNDING       blend_rows adds its extra one wherever both dropped bits are set, also where an odd
+//                                        Ha + Hb has absorbed it: +1 in some pixels of (1/2, 1/2) pieces, nowhere else
+//   -DH263MI_MUTATE_INTEGER_BORDER       border lanes of a wave whose vectors are all integer skip the clamped re-gather and
+//                                        use the bytes of their window as loaded
 // Included by recon_kernel.inl behind the definitions it uses (f32x2, splat2, BasisPtr, basis_pair).
 #pragma once
 
@@ -28,6 +33,16 @@ constexpr bool kDequantSaturation = false;
 constexpr bool kDequantWrap = true;
 #else
 constexpr bool kDequantWrap = false;
+#endif
+#if defined(H263MI_MUTATE_BLEND_ROUNDING)
+constexpr bool kBlendRounding = true;
+#else
+constexpr bool kBlendRounding = false;
+#endif
+#if defined(H263MI_MUTATE_INTEGER_BORDER)
+constexpr bool kIntegerBorder = true;
+#else
+constexpr bool kIntegerBorder = false;
 #endif
 
 // kPairwise: the eight rounded products summed as a balanced tree instead of in the order of the frequency index

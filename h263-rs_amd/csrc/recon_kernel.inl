@@ -1101,7 +1101,7 @@ H263_DEV uint32_t blend_rows(uint32_t ha, uint32_t xa, uint32_t hn, uint32_t xn,
     const uint32_t dm = (ha ^ hn) & my;            // Ha ^ Hb
     const uint32_t hb = ha ^ dm;
     const uint32_t both = xa & (xn | ~my) & 0x01010101u;
-    return lerp_u8x4(ha, hb, 0x01010101u) + (both ^ (both & dm));
+    return lerp_u8x4(ha, hb, 0x01010101u) + (mutants::kBlendRounding ? both : (both ^ (both & dm)));   // (mutants.h: false in the product)
 }
 
 template <int N_ROWS>
@@ -1112,7 +1112,7 @@ H263_DEV void predict_piece(ReconWave &s, uint32_t (*rows)[3], uint32_t mvw, uin
     const uint32_t ix = (uint32_t)mvx & 1u, my = 0u - ((mvw >> 16) & 1u);
     const int u = g.px + (mvx >> 1);
     uint32_t sh = (uint32_t)u & 3u;          // the rows were loaded from the dword at or below u
-    if (flags & SEG_BORDER) {
+    if ((flags & SEG_BORDER) && !(mutants::kIntegerBorder && all_integer)) {     // (mutants.h: compile-time false in the product)
         // some tap lies outside the picture: rebuild the rows tap by tap from the loaded window
         const int ub = border_window(u, g.pw);
 #pragma unroll
@@ -1141,8 +1141,12 @@ H263_DEV void predict_piece(ReconWave &s, uint32_t (*rows)[3], uint32_t mvw, uin
 }
 
 // MC = false: nothing is predicted anywhere in the wave: the strip starts from zeros (gather.rs:136-138).
+// host_luma_integer / host_chroma_integer: the CPU checker runs the lanes one by one, so it makes the two reductions over
+// its lanes' vectors that the device makes with the ballots below and hands them in (tests/sim/sim.cpp); the device never
+// passes nor reads them.
 template <bool MC = true>
-H263_DEV void recon_phase_predict(const ReconArgs &a, ReconWave &s, WaveFetch &f, int lane, const WavePos &p, const WaveMasks &km)
+H263_DEV void recon_phase_predict(const ReconArgs &a, ReconWave &s, WaveFetch &f, int lane, const WavePos &p, const WaveMasks &km,
+                                  bool host_luma_integer = false, bool host_chroma_integer = false)
 {
     const PieceGeo gl = piece_geometry(a, lane, 0, p), gc = piece_geometry(a, lane, 1, p);
     if (!MC) {
@@ -1157,7 +1161,7 @@ H263_DEV void recon_phase_predict(const ReconArgs &a, ReconWave &s, WaveFetch &f
     const bool luma_integer = __ballot(((f.mvw[0] | (f.mvw[0] >> 16)) & 1u) != 0) == 0;
     const bool chroma_integer = __ballot(((f.mvw[1] | (f.mvw[1] >> 16)) & 1u) != 0) == 0;
 #else
-    const bool luma_integer = false, chroma_integer = false;   // (the general form covers integer vectors: checked by the CPU suite)
+    const bool luma_integer = host_luma_integer, chroma_integer = host_chroma_integer;
 #endif
     predict_piece<LUMA_ROWS>(s, f.ly, f.mvw[0], f.flags, gl, luma_integer, all_inter);
     predict_piece<CHROMA_ROWS>(s, f.ch, f.mvw[1], f.flags >> 2, gc, chroma_integer, all_inter);

@@ -246,3 +246,62 @@ def decode_picture(width, height, mbs, coeffs, ref=None):
                 P[sl] = np.clip(P[sl] + res, 0, 255)
     return 0, (Y[:h, :w].astype(np.uint8).ravel(), CB[:ch, :cw].astype(np.uint8).ravel(),
                CR[:ch, :cw].astype(np.uint8).ravel())
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The same motion compensation for a whole plane at once (tests/test_sim_mc_sweep.py: the per-macroblock loop of
+# decode_picture is too slow for its tables).  Same rules as gather_block, lerp_params and chroma_mv above, restated
+# over arrays.
+# ---------------------------------------------------------------------------------------------------------------
+def gather_plane(plane, mvx, mvy):
+    """gather_block for every 8x8 block of a plane: plane uint8[h, w]; mvx, mvy int[bh, bw], one vector per block.
+    Returns int32[bh * 8, bw * 8] (the padded work plane)."""
+    h, w = plane.shape
+    mvx, mvy = np.asarray(mvx, np.int64), np.asarray(mvy, np.int64)
+    bh, bw = mvx.shape
+
+    def per_pixel(a):
+        return np.repeat(np.repeat(a, 8, axis=0), 8, axis=1)
+
+    dx, ix = per_pixel(mvx >> 1), per_pixel(mvx & 1).astype(bool)      # floor(mv / 2), odd (types.rs:721-729)
+    dy, iy = per_pixel(mvy >> 1), per_pixel(mvy & 1).astype(bool)
+    us = np.arange(bw * 8)[None, :] + dx
+    vs = np.arange(bh * 8)[:, None] + dy
+    p = plane.astype(np.int32)
+
+    def tap(du, dv):
+        return p[np.clip(vs + dv, 0, h - 1), np.clip(us + du, 0, w - 1)]
+
+    a, b, c, d = tap(0, 0), tap(1, 0), tap(0, 1), tap(1, 1)
+    return np.where(ix & iy, (a + b + c + d + 2) // 4, np.where(ix, (a + b + 1) // 2, np.where(iy, (a + c + 1) // 2, a)))
+
+
+def chroma_mv_array(s):
+    """chroma_mv for an array of component sums (the sums are i16: they wrap)"""
+    s = np.asarray(s, np.int64).astype(np.int16).astype(np.int64)
+    whole = (s >> 4) << 1
+    frac = s & 15
+    return whole + (frac > 2) + (frac >= 14)
+
+
+def predict_picture(width, height, mbs, ref):
+    """decode_picture for a P picture in which every macroblock is inter and nothing is coded (the prediction IS the
+    picture).  Raises ValueError for any other picture: those go through decode_picture."""
+    w, h = width, height
+    cw, ch = (w + 1) // 2, (h + 1) // 2
+    mbw, mbh = (w + 15) // 16, (h + 15) // 16
+    n = mbw * mbh
+    mb_type = np.zeros(n, np.int64)
+    cbp = np.zeros(n, np.int64)
+    mv = np.zeros((n, 4, 2), np.int64)
+    k = min(n, len(mbs))
+    mb_type[:k], cbp[:k], mv[:k] = mbs["mb_type"][:k], mbs["cbp"][:k], mbs["mv"][:k]
+    if not np.isin(mb_type, (0, 1, 2, 5)).all() or cbp.any():
+        raise ValueError("predict_picture: an intra macroblock or a coded block")
+    mv = mv.reshape(mbh, mbw, 2, 2, 2)                                   # [mby, mbx, block row, block column, component]
+    luma = mv.transpose(0, 2, 1, 3, 4).reshape(mbh * 2, mbw * 2, 2)
+    y = gather_plane(np.asarray(ref[0], np.uint8).reshape(h, w), luma[..., 0], luma[..., 1])
+    c = chroma_mv_array(mv.reshape(mbh, mbw, 4, 2).sum(axis=2))
+    cb = gather_plane(np.asarray(ref[1], np.uint8).reshape(ch, cw), c[..., 0], c[..., 1])
+    cr = gather_plane(np.asarray(ref[2], np.uint8).reshape(ch, cw), c[..., 0], c[..., 1])
+    return 0, (y[:h, :w].astype(np.uint8).ravel(), cb[:ch, :cw].astype(np.uint8).ravel(), cr[:ch, :cw].astype(np.uint8).ravel())

@@ -70,6 +70,14 @@ void sim_wide_bits_events(const uint32_t *events, uint32_t n, uint32_t *out)
 static int force_wide_rounds = 0;
 void sim_force_wide_rounds(int on) { force_wide_rounds = on; }
 
+// 1: the predict phase never takes the short cut of a wave whose vectors are all integer (recon_phase_predict: the general
+// form must give the same pixels -- tests/test_sim_mc_sweep.py runs its whole-wave-integer table both ways)
+static int no_integer_short_cut = 0;
+void sim_no_integer_short_cut(int on) { no_integer_short_cut = on; }
+// how many waves of the sim_recon calls so far took the short cut for (luma, chroma)
+static uint64_t integer_waves[2] = {0, 0};
+void sim_integer_waves(uint64_t out[2]) { out[0] = integer_waves[0]; out[1] = integer_waves[1]; }
+
 void sim_layout(uint32_t w, uint32_t h, FrameLayout *out) { *out = make_layout(w, h); }
 
 // block_first_event / events: sparse coefficient transport consumed by the reconstruction wave itself (nullptr: dense)
@@ -188,8 +196,16 @@ int sim_recon_ex(uint32_t w, uint32_t h, uint32_t n_pictures, const MbRecord *mb
                     for (int l = 0; l < 64; l++) any_special = any_special || recon_block_is_special(ri[l], l, rows_any, cols_any);
                 }
                 if (round == 0) {
+                    // the two reductions over the lanes' vectors that the device makes with ballots (recon_phase_predict)
+                    bool luma_integer = mc && !no_integer_short_cut, chroma_integer = luma_integer;
+                    for (int l = 0; l < 64 && mc; l++) {
+                        if ((f[l].mvw[0] | (f[l].mvw[0] >> 16)) & 1u) luma_integer = false;
+                        if ((f[l].mvw[1] | (f[l].mvw[1] >> 16)) & 1u) chroma_integer = false;
+                    }
+                    integer_waves[0] += luma_integer;
+                    integer_waves[1] += chroma_integer;
                     for (int l = 0; l < 64; l++) {
-                        if (mc) recon_phase_predict<true>(a, *s, f[l], l, p, km);
+                        if (mc) recon_phase_predict<true>(a, *s, f[l], l, p, km, luma_integer, chroma_integer);
                         else recon_phase_predict<false>(a, *s, f[l], l, p, km);
                     }
                 }

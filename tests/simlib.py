@@ -22,8 +22,9 @@ class FrameLayout(C.Structure):
 _libs = {}
 
 
-def lib(asan=False):
-    name = "libh263mi_sim_asan.so" if asan else "libh263mi_sim.so"
+def lib(asan=False, variant=None):
+    """variant: "blend" / "intborder" = the checker built with that motion-compensation mutation (csrc/mutants.h)"""
+    name = "libh263mi_sim_%s.so" % variant if variant else ("libh263mi_sim_asan.so" if asan else "libh263mi_sim.so")
     if name not in _libs:
         subprocess.check_call(["make", "-C", SIM_DIR, "-s", name])
         L = C.CDLL(os.path.join(SIM_DIR, name))
@@ -98,10 +99,12 @@ def to_sparse_records(mbs, w, h):
     return np.ascontiguousarray(mbs[keep]), index
 
 
-def recon(w, h, mbs, coeffs, ref=None, asan=False, events=False, sparse_records=False):
+def recon(w, h, mbs, coeffs, ref=None, asan=False, events=False, sparse_records=False, variant=None):
     """One picture through the kernel phases on the CPU.  Returns (status, (y, cb, cr)).  events: the coefficients reach
     the reconstruction wave as sparse events (block_first_event + events), not as dense blocks."""
     L = layout(w, h)
+    if variant:
+        return _recon_with(lib(variant=variant), L, w, h, mbs, coeffs, ref)
     mbs = pad_records(mbs, w, h)
     keep_alive = None
     if sparse_records:
@@ -143,6 +146,20 @@ def recon(w, h, mbs, coeffs, ref=None, asan=False, events=False, sparse_records=
     rc = lib(asan).sim_recon(w, h, 1, _p(mbs), _p(cpad), coeffs.shape[0], None, _p(reff), 1 if ref is not None else 0,
                              _p(cur), _p(status))
     assert rc == 0, "sim_recon: %d (-2: desc_pix_origin != task_pix_origin)" % rc
+    return int(status[0]), unpack_frame(L, cur)
+
+
+def _recon_with(Lib, L, w, h, mbs, coeffs, ref):
+    """dense records and coefficients through another build of the checker"""
+    mbs = pad_records(mbs, w, h)
+    coeffs = np.ascontiguousarray(coeffs, np.int16).reshape(-1, 64)
+    cpad = np.zeros((coeffs.shape[0] + 1, 64), np.int16)
+    cpad[:coeffs.shape[0]] = coeffs
+    reff = pack_frame(L, ref) if ref is not None else None
+    cur = np.full(L.frame_bytes, 0xC3, np.uint8)
+    status = np.zeros(1, np.uint32)
+    rc = Lib.sim_recon(w, h, 1, _p(mbs), _p(cpad), coeffs.shape[0], None, _p(reff), 1 if ref is not None else 0, _p(cur), _p(status))
+    assert rc == 0
     return int(status[0]), unpack_frame(L, cur)
 
 

@@ -4,7 +4,12 @@ Two mutants of the product library are built from the same sources (h263-rs_amd/
   libh263mi_fma.so       -ffp-contract=fast instead of off: the compiler fuses the IDCT's multiplies into its adds
   libh263mi_pairwise.so  -DH263MI_MUTATE_PAIRWISE: idct_1d sums its eight products as a balanced tree
 On the committed block set (found with the FPU-free soft-float model, tools/find_sensitive_blocks.py) the real
-library must reproduce the reference arithmetic (idct.rs:52-65, 171-196) pixel for pixel, and each mutant must NOT."""
+library must reproduce the reference arithmetic (idct.rs:52-65, 171-196) pixel for pixel, and each mutant must NOT.
+
+Two more mutants are of the MOTION COMPENSATION (csrc/mutants.h; probe and models: tests/mc_mutation_probe.py):
+  libh263mi_blend.so      blend_rows without its `^ (both & dm)` exclusion: +1 in some pixels of (1/2, 1/2) pieces
+  libh263mi_intborder.so  border lanes of an all-integer wave skip the clamped re-gather
+Their arithmetic is integer: each must differ from the oracle AND equal its numpy model on every byte."""
 import json
 import os
 import subprocess
@@ -118,3 +123,71 @@ def test_wrap_mutant_is_caught_by_the_11_bit_level_test():
         good = subprocess.run(cmd, env=dict(os.environ, H263MI_LIB=os.path.join(PKG, "libh263mi.so")), capture_output=True,
                               text=True, timeout=600)
         assert good.returncode == 0 and "%d passed" % n in good.stdout, good.stdout[-800:]
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the motion-compensation mutants
+# ---------------------------------------------------------------------------------------------------------------
+def _mc_probe(lib_path, tmp_path, name):
+    out = str(tmp_path / (name + ".npz"))
+    env = dict(os.environ, H263MI_LIB=lib_path)
+    subprocess.run([sys.executable, os.path.join(HERE, "mc_mutation_probe.py"), out], env=env, check=True, timeout=900)
+    return np.load(out)
+
+
+@pytest.fixture(scope="module")
+def mc_probe_expected():
+    """per probe picture: (name, picture, reference planes, the oracle's planes)"""
+    import mc_cases as mc
+    import mc_mutation_probe as probe
+    from oracle import oracle as orc
+    out = []
+    for k, pic in enumerate(probe.pictures_d()):
+        mbs, co = mc.reference_records(pic["w"], pic["h"])
+        rc, ref = orc.decode_picture(pic["w"], pic["h"], mbs, co, None)
+        rc, want = orc.decode_picture(pic["w"], pic["h"], pic["mbs"], pic["coeffs"], ref)
+        assert rc == 0
+        out.append(("d%03d" % k, pic, ref, want))
+    w, h, intra, push, co = mc.f_blocks_reference()
+    rc, ref = orc.decode_picture(w, h, intra, mc.NO_COEFFS, None)
+    rc, ref = orc.decode_picture(w, h, push, co, ref)
+    for k, pic in enumerate(probe.pictures_f()):
+        rc, want = orc.decode_picture(w, h, pic["mbs"], pic["coeffs"], ref)
+        assert rc == 0
+        out.append(("f%d" % k, pic, ref, want))
+    return out
+
+
+@pytest.mark.parametrize("mutant", ["blend", "intborder"])
+def test_mc_mutant_build_fails_exactly_as_its_model_predicts(mutant, tmp_path, mc_probe_expected):
+    """tables (d) and (f) of tests/mc_cases.py through a mutant build (child process): it must differ from the oracle, and
+    every byte must be the one the numpy model of the mutation predicts (the product build, run the same way, is clean:
+    the test below)"""
+    import mc_cases as mc
+    import mc_mutation_probe as probe
+    lib = os.path.join(PKG, "mutants", "libh263mi_%s.so" % mutant)
+    if not os.path.exists(lib):                                  # normally built by __graft_entry__.build()
+        subprocess.check_call(["make", "-C", PKG, "-s", "mutants"])
+    got = _mc_probe(lib, tmp_path, mutant)
+    model = probe.model_blend if mutant == "blend" else probe.model_intborder
+    differing = {"d": 0, "f": 0}
+    wrong_bytes = 0
+    for name, pic, ref, want in mc_probe_expected:
+        planes = tuple(got["%s_%d" % (name, i)] for i in range(3))
+        diff = mc.first_difference(pic, planes, model(pic, ref, want))
+        assert diff is None, "the %s mutant (got) against its model (expected), picture %s: %s" % (mutant, name, diff)
+        n = sum(int((g != e).sum()) for g, e in zip(planes, want))
+        differing[name[0]] += n > 0
+        wrong_bytes += n
+    print("%s mutant: %d bytes differ from the oracle, in %d pictures of table (d) and %d of table (f); all as its model predicts"
+          % (mutant, wrong_bytes, differing["d"], differing["f"]))
+    assert differing["f" if mutant == "blend" else "d"] > 0, "the %s mutant went unnoticed" % mutant
+
+
+def test_mc_probe_through_the_product_build_is_clean(tmp_path, mc_probe_expected):
+    """the same child-process path with the product library: every byte is the oracle's"""
+    import mc_cases as mc
+    clean = _mc_probe(os.path.join(PKG, "libh263mi.so"), tmp_path, "product")
+    for name, pic, ref, want in mc_probe_expected:
+        diff = mc.first_difference(pic, tuple(clean["%s_%d" % (name, i)] for i in range(3)), want)
+        assert diff is None, "the product build, picture %s: %s" % (name, diff)

@@ -8,32 +8,39 @@
 #   pmc_summary.txt              SQ / TCC / TCP counters of k_frame (tools/prof_pmc.sh groups)
 #   e2e_kernel_stats.csv         rocprofv3 kernel stats of the end-to-end path alone (tools/probes/e2e_trace.py)
 # usage (GPU box, repo root): bash tools/prof_final.sh r03_x      -> gpurun_out/final_r03_x/
+#   COUNTERS_ONLY=1 bash tools/prof_final.sh r12_x   only the counter passes and traffic.json (-> profiles/traffic_latest.json):
+#                   what a change needs that touches the hashed kernel sources without changing the kernels' code
 set -u
+COUNTERS_ONLY=${COUNTERS_ONLY:-0}
 TAG=${1:-rXX}
 R=$PWD; OUT=$R/gpurun_out/final_$TAG; mkdir -p $OUT
 PROF_ARGS="--gops-per-step 1 --steps 2 --warmup 1 --no-cpu-baseline --no-extra --no-parity-gate"
 cd /tmp && export TMPDIR=/tmp
 # ---- the box
 # (the probe is built here, on the box: build/ does not travel with the snapshot any more)
+if [ "$COUNTERS_ONLY" = 1 ]; then
+STAMP="box: one MI355X, $(date -u +%Y-%m-%dT%H:%MZ), counter passes of tools/prof_final.sh"
+else
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 $R/tools/probes/ceiling.hip -o /tmp/ceiling 2> /dev/null
 ( [ -x /tmp/ceiling ] && timeout 200 /tmp/ceiling 1024 | grep "BEST\|hipMemcpy" ) > $OUT/box.txt 2>&1
 STAMP="box: $(grep 'BEST copy' $OUT/box.txt | awk '{print $3" GB/s copy ceiling"}'), $(hostname), $(date -u +%Y-%m-%dT%H:%MZ)"
 echo "$STAMP" >> $OUT/box.txt
+fi
 echo "== $STAMP"
 # ---- kernel trace of the bench command with its parity gate and measured ceilings (no extra legs)
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py --full --no-cpu-baseline --no-extra > $OUT/bench_under_rocprof.json 2> $OUT/trace.log
+[ "$COUNTERS_ONLY" = 1 ] || timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py --full --no-cpu-baseline --no-extra > $OUT/bench_under_rocprof.json 2> $OUT/trace.log
 # ---- HBM traffic: two counter-only passes
 for C in FETCH_SIZE WRITE_SIZE; do
-  timeout 600 rocprofv3 --pmc $C --output-format csv -d $OUT/pmc_$C -- python3 $R/bench.py $PROF_ARGS > /dev/null 2> $OUT/pmc_$C.log
+  timeout 600 rocprofv3 --pmc $C --output-format csv -d $OUT/pmc_$C -- python3 $R/bench.py $PROF_ARGS > /dev/null 2> $OUT/pmc_$C.log || { echo "counter pass $C failed"; exit 1; }
 done
 # ... and the request counters behind them, by size (round 4: tools/fetch_calib.sh shows that EVERY read request of the L2s
 # is 128 bytes on gfx950, for k_frame's gathers and strip loads as for streaming reads -- FETCH_SIZE, which prices a request
 # at 64 bytes, times 2 is exact; TCC_EA0_RDREQ_DRAM_32B x 32 bytes agrees to 0.2 %)
-timeout 600 rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_128B_sum TCC_EA0_RDREQ_DRAM_32B_sum --output-format csv -d $OUT/pmc_RDREQ -- python3 $R/bench.py $PROF_ARGS > /dev/null 2> $OUT/pmc_RDREQ.log
-timeout 600 rocprofv3 --pmc TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum TCC_EA0_WRREQ_WRITE_DRAM_32B_sum --output-format csv -d $OUT/pmc_WRREQ -- python3 $R/bench.py $PROF_ARGS > /dev/null 2> $OUT/pmc_WRREQ.log
+timeout 600 rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_128B_sum TCC_EA0_RDREQ_DRAM_32B_sum --output-format csv -d $OUT/pmc_RDREQ -- python3 $R/bench.py $PROF_ARGS > /dev/null 2> $OUT/pmc_RDREQ.log || { echo "counter pass RDREQ failed"; exit 1; }
+timeout 600 rocprofv3 --pmc TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum TCC_EA0_WRREQ_WRITE_DRAM_32B_sum --output-format csv -d $OUT/pmc_WRREQ -- python3 $R/bench.py $PROF_ARGS > /dev/null 2> $OUT/pmc_WRREQ.log || { echo "counter pass WRREQ failed"; exit 1; }
 # ... and what the vector ALUs did (round 5: the launch is bound by their issue slots, bench.py reports it as roofline.valu)
-timeout 600 rocprofv3 --pmc SQ_INSTS_VALU GRBM_GUI_ACTIVE --output-format csv -d $OUT/pmc_VALU -- python3 $R/bench.py $PROF_ARGS > /dev/null 2> $OUT/pmc_VALU.log
-timeout 600 rocprofv3 --pmc VALUBusy --output-format csv -d $OUT/pmc_VALUBUSY -- python3 $R/bench.py $PROF_ARGS > /dev/null 2> $OUT/pmc_VALUBUSY.log
+timeout 600 rocprofv3 --pmc SQ_INSTS_VALU GRBM_GUI_ACTIVE --output-format csv -d $OUT/pmc_VALU -- python3 $R/bench.py $PROF_ARGS > /dev/null 2> $OUT/pmc_VALU.log || { echo "counter pass VALU failed"; exit 1; }
+timeout 600 rocprofv3 --pmc VALUBusy --output-format csv -d $OUT/pmc_VALUBUSY -- python3 $R/bench.py $PROF_ARGS > /dev/null 2> $OUT/pmc_VALUBUSY.log || { echo "counter pass VALUBUSY failed"; exit 1; }
 cd $R
 python3 - "$OUT" "$TAG" "$STAMP" <<'PY'
 import csv, glob, json, os, sys, collections
@@ -99,6 +106,7 @@ print(json.dumps(traffic))
 PY
 # the bench line below reports this traffic: same kernel sources, same box
 cp $OUT/traffic.json profiles/traffic_latest.json
+[ "$COUNTERS_ONLY" = 1 ] && exit 0
 # ---- the full bench line, unprofiled
 timeout 1200 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 # ---- SQ / TCC / TCP counters of the launch
