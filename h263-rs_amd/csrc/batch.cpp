@@ -66,6 +66,58 @@ h263mi_resize_scratch::~h263mi_resize_scratch()
     if (spans) (void)hipFree(spans);
 }
 
+h263mi_plane_scratch::~h263mi_plane_scratch()
+{
+    DeviceGuard g(device);
+    if (planes) (void)hipFree(planes);
+    if (spans) (void)hipFree(spans);
+}
+
+int h263mi_batch::plane_resize_dst(const YuvLayout::Resize &rz, const std::vector<int8_t> &sets, uint8_t *d_planes, hipStream_t on,
+                                   const PlaneDst **d_out, bool *wide)
+{
+    std::vector<PlaneDst> p(n, PlaneDst{{nullptr, nullptr, nullptr}});
+    const bool nv12 = rz.format == YUV_OUT_NV12;
+    for (uint32_t i = 0; i < n; i++)
+        if (sets[i] >= 0) {
+            p[i].p[0] = d_planes + rz.offsets[3 * i + 0];
+            p[i].p[1] = d_planes + rz.offsets[3 * i + 1];
+            p[i].p[2] = nv12 ? nullptr : d_planes + rz.offsets[3 * i + 2];
+        }
+    *wide = rz.wide && ((uintptr_t)d_planes & 3u) == 0;
+    return upload(plane_ring, p.data(), d_out, on);
+}
+
+int h263mi_batch::launch_plane_resize(const YuvLayout::Resize &rz, const std::vector<int8_t> &sets, const PlaneDst *d_dst, bool wide,
+                                      hipStream_t on)
+{
+    bool any = false;
+    for (int8_t v : sets) any = any || v >= 0;
+    if (!any) return H263MI_OK;
+    PlaneResizeArgs a{};
+    a.src = rz.scratch->planes;
+    a.dst = d_dst;
+    a.w = L.width, a.h = L.height, a.cw = L.cwidth, a.ch = L.cheight;
+    a.ow = rz.ow, a.oh = rz.oh, a.cow = (rz.ow + 1) / 2, a.coh = (rz.oh + 1) / 2;
+    a.cols_y = rz.scratch->spans;
+    a.rows_y = a.cols_y + a.ow;
+    a.cols_c = a.rows_y + a.oh;
+    a.rows_c = a.cols_c + a.cow;
+    a.pitch_y = rz.pitch_y;
+    a.pitch_c = rz.pitch_c;
+    a.nv12 = rz.format == YUV_OUT_NV12 ? 1u : 0u;
+    a.wide = wide ? 1u : 0u;
+    a.d_y = L.width * L.height;
+    a.d_c = L.cwidth * L.cheight;
+    a.inv_d_y = 1.0f / (float)a.d_y;
+    a.inv_d_c = 1.0f / (float)a.d_c;
+    a.n_pictures = n;
+    if (!::h263mi::launch_plane_resize) return H263MI_ERR_HIP;      // (kernels.h: only a stub runtime lacks it)
+    RC_TRY(time_begin(4, on));
+    HIP_TRY(::h263mi::launch_plane_resize(a, on));
+    return H263MI_OK;
+}
+
 int h263mi_batch::resize_dst(const std::vector<int8_t> &sets, uint8_t *d_rgba, uint8_t *const *host_ptrs, hipStream_t on,
                              uint8_t *const **d_out)
 {
@@ -307,6 +359,11 @@ int h263mi_batch::submit(uint8_t picture_type, const MbRecord *d_mbs, const h263
             pending.resize = RgbaLayout::Resize();
             RC_TRY(launch_resize(rz, pending.set, pending.resize_dst, stream));
         }
+        if (pending.yuv.resize.on() && pending.plane_dst) {     // ... and the full-size planes in theirs
+            const YuvLayout::Resize rz = std::move(pending.yuv.resize);
+            pending.yuv = YuvLayout();
+            RC_TRY(launch_plane_resize(rz, pending.set, pending.plane_dst, pending.plane_wide, stream));
+        }
     } else {
         RC_TRY(time_begin(0));
         HIP_TRY(launch_recon(a, stream, !words.empty() && words_inline ? words.data() : nullptr));
@@ -391,18 +448,27 @@ int h263mi_batch::note_pending(const Strengths &strength, uint8_t *d_rgba, uint8
     pending.rgba_ptrs = nullptr;
     pending.resize = RgbaLayout::Resize();
     pending.yuv = d_planes ? yuv : YuvLayout();      // (captured here, at the request, like the RGBA shape)
+    pending.plane_dst = nullptr;
+    // a YUV resize: the deferred rendering writes the full-size planes into its scratch, k_plane_resize follows it
+    auto note_planes = [&]() -> int {
+        if (!pending.yuv.resize.on()) return H263MI_OK;
+        RC_TRY(plane_resize_dst(pending.yuv.resize, pending.set, d_planes, stream, &pending.plane_dst, &pending.plane_wide));
+        pending.planes = pending.yuv.resize.scratch->planes;
+        return H263MI_OK;
+    };
     if (layout.resize.on() && (d_rgba || host_ptrs)) {
         // a resize: the deferred rendering writes the full-size pictures into the scratch, k_rgba_resize follows it (the
         // resize -- scratch, size, destinations -- is captured here, at the request)
         for (uint32_t i = 0; i < n; i++)
             pending.set[i] = (ss[i].active && (!host_ptrs || host_ptrs[i])) ? ss[i].cur : (int8_t)-1;
         RC_TRY(resize_dst(pending.set, d_rgba, host_ptrs, stream, &pending.resize_dst));
+        pending.planes = d_planes;
+        RC_TRY(note_planes());
         pending.resize = layout.resize;
         pending.out = OutLayout();
         pending.valid = true;
         pending.strength = strength;
         pending.rgba = layout.resize.scratch->rgba;
-        pending.planes = d_planes;
         return H263MI_OK;
     }
     // (an output layout places each stream's picture through a per-stream pointer; the layout is captured here, at the request)
@@ -410,12 +476,13 @@ int h263mi_batch::note_pending(const Strengths &strength, uint8_t *d_rgba, uint8
     if (!host_ptrs && layout_ptrs(d_rgba, placed)) host_ptrs = placed.data();
     pending.out = layout.kernel;
     if (host_ptrs) RC_TRY(upload(ptr_ring, host_ptrs, &pending.rgba_ptrs, stream));
+    for (uint32_t i = 0; i < n; i++)
+        pending.set[i] = (ss[i].active && (!host_ptrs || host_ptrs[i])) ? ss[i].cur : (int8_t)-1;
+    pending.planes = d_planes;
+    RC_TRY(note_planes());
     pending.valid = d_rgba || d_planes || host_ptrs;
     pending.strength = strength;
     pending.rgba = d_rgba;
-    pending.planes = d_planes;
-    for (uint32_t i = 0; i < n; i++)
-        pending.set[i] = (ss[i].active && (!host_ptrs || host_ptrs[i])) ? ss[i].cur : (int8_t)-1;
     return H263MI_OK;
 }
 
@@ -425,8 +492,11 @@ int h263mi_batch::flush_pending()
     pending.valid = false;
     const RgbaLayout::Resize rz = std::move(pending.resize);
     pending.resize = RgbaLayout::Resize();
+    const YuvLayout::Resize yrz = std::move(pending.yuv.resize);
+    pending.yuv.resize = YuvLayout::Resize();
     RC_TRY(launch_post_sets(pending.set, pending.strength, pending.rgba, pending.planes, stream, pending.rgba_ptrs, pending.out, &pending.yuv));
-    return rz.on() ? launch_resize(rz, pending.set, pending.resize_dst, stream) : H263MI_OK;
+    if (rz.on()) RC_TRY(launch_resize(rz, pending.set, pending.resize_dst, stream));
+    return yrz.on() && pending.plane_dst ? launch_plane_resize(yrz, pending.set, pending.plane_dst, pending.plane_wide, stream) : H263MI_OK;
 }
 
 int h263mi_batch::render(const Strengths &strength, uint8_t *d_rgba, uint8_t *d_planes, bool only_active, uint8_t *const *host_ptrs)
@@ -445,6 +515,14 @@ int h263mi_batch::render(const Strengths &strength, uint8_t *d_rgba, uint8_t *d_
     }
     if (overlap_post) HIP_TRY(hipStreamWaitEvent(post_stream, ev_recon_done, 0));
     uint8_t *const *d_out_ptrs = nullptr;
+    // a YUV resize: the full-size planes into its scratch (the default kernels), k_plane_resize behind the rendering
+    const bool planes_resized = yuv.resize.on() && d_planes;
+    const PlaneDst *d_plane_dst = nullptr;
+    bool plane_wide = false;
+    if (planes_resized) {
+        RC_TRY(plane_resize_dst(yuv.resize, sets, d_planes, stream_of(1), &d_plane_dst, &plane_wide));
+        d_planes = yuv.resize.scratch->planes;
+    }
     if (resized) {
         // full size into the scratch (the default kernels), then k_rgba_resize right behind it on the same stream
         RC_TRY(resize_dst(sets, d_rgba, host_ptrs, stream_of(1), &d_out_ptrs));
@@ -454,6 +532,7 @@ int h263mi_batch::render(const Strengths &strength, uint8_t *d_rgba, uint8_t *d_
         if (host_ptrs) RC_TRY(upload(ptr_ring, host_ptrs, &d_out_ptrs, stream_of(1)));
         RC_TRY(launch_post_sets(sets, strength, d_rgba, d_planes, stream_of(1), d_out_ptrs, layout.kernel, &yuv));
     }
+    if (planes_resized) RC_TRY(launch_plane_resize(yuv.resize, sets, d_plane_dst, plane_wide, stream_of(1)));
     // a later reconstruction may overwrite a frame set only when every post-processing that reads it is done: streams
     // that have drifted apart read both sets
     if (overlap_post)
@@ -666,8 +745,8 @@ static int bound_output_buffers(const h263mi_batch *b, const uint8_t *d_rgba, co
 {
     if (b->trusted_arrays) return H263MI_OK;
     const size_t rgba_bytes = b->layout.bytes;      // (n * w*h*4 unless the batch has an output layout)
-    // (n tightly packed I420 pictures unless the batch has a YUV layout)
-    const size_t plane_bytes = b->yuv.on() ? (size_t)b->yuv.bytes
+    // (n tightly packed I420 pictures unless the batch has a YUV layout or resize)
+    const size_t plane_bytes = b->yuv.shaped() ? (size_t)b->yuv.bytes
                                            : (size_t)b->n * ((size_t)b->L.width * b->L.height + 2 * (size_t)b->L.cwidth * b->L.cheight);
     size_t left = 0;
     if (d_rgba) {
@@ -837,6 +916,73 @@ int make_yuv_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_
     HIP_TRY(hipMalloc((void **)&d->d, offs.size() * sizeof(uint64_t)));
     HIP_TRY(hipMemcpy(d->d, offs.data(), offs.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
     shape.offsets = std::move(d);
+    out = std::move(shape);
+    return H263MI_OK;
+}
+
+int yuv_resize_extent(uint32_t n_streams, const h263mi_yuv_resize *r, uint64_t *bytes, h263mi_batch::YuvLayout *shape,
+                      std::vector<uint64_t> *offsets)
+{
+    if (!r || !r->out_width || !r->out_height) return H263MI_ERR_INVALID_ARGUMENT;
+    for (uint8_t v : r->reserved)
+        if (v) return H263MI_ERR_INVALID_ARGUMENT;
+    // the rules of a layout: a layout of a W' x H' picture has exactly the resize's shape
+    h263mi_yuv_layout lay{};
+    lay.format = r->format;
+    lay.pitch_y = r->pitch_y;
+    lay.pitch_c = r->pitch_c;
+    lay.offsets_y = r->offsets_y;
+    lay.offsets_cb = r->offsets_cb;
+    lay.offsets_cr = r->offsets_cr;
+    return yuv_layout_extent(n_streams, r->out_width, r->out_height, &lay, bytes, shape, offsets);
+}
+
+int make_yuv_resize_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_yuv_resize *r, h263mi_batch::YuvLayout &out)
+{
+    if (!r) {
+        out = h263mi_batch::YuvLayout();
+        return H263MI_OK;
+    }
+    h263mi_batch::YuvLayout placed;
+    std::vector<uint64_t> offs;
+    RC_TRY(yuv_resize_extent(n, r, nullptr, &placed, &offs));
+    const uint32_t ow = r->out_width, oh = r->out_height;
+    if (ow == w && oh == h) {                   // identical by definition: the YUV instantiations, no scratch, no extra pass
+        h263mi_yuv_layout lay{};
+        lay.format = r->format;
+        lay.pitch_y = r->pitch_y;
+        lay.pitch_c = r->pitch_c;
+        lay.offsets_y = r->offsets_y;
+        lay.offsets_cb = r->offsets_cb;
+        lay.offsets_cr = r->offsets_cr;
+        return make_yuv_shape(device, n, w, h, &lay, out);
+    }
+    const uint32_t cw = (w + 1) / 2, ch = (h + 1) / 2, cow = (ow + 1) / 2, coh = (oh + 1) / 2;
+    std::vector<ResizeSpan> spans((size_t)ow + oh + cow + coh);
+    resize_spans(w, ow, spans.data());
+    resize_spans(h, oh, spans.data() + ow);
+    resize_spans(cw, cow, spans.data() + ow + oh);
+    resize_spans(ch, coh, spans.data() + ow + oh + cow);
+    DeviceGuard g(device);
+    if (!g.ok) return H263MI_ERR_NO_DEVICE;
+    std::shared_ptr<h263mi_plane_scratch> sc(new (std::nothrow) h263mi_plane_scratch());
+    if (!sc) return H263MI_ERR_OUT_OF_MEMORY;
+    sc->device = device;
+    const size_t plane_bytes = (size_t)n * ((size_t)w * h + 2 * (size_t)cw * ch), span_bytes = spans.size() * sizeof(ResizeSpan);
+    HIP_TRY(hipMalloc((void **)&sc->planes, plane_bytes));
+    HIP_TRY(hipMalloc((void **)&sc->spans, span_bytes));
+    HIP_TRY(hipMemcpy(sc->spans, spans.data(), span_bytes, hipMemcpyHostToDevice));
+    sc->bytes = plane_bytes + span_bytes;
+    h263mi_batch::YuvLayout shape;              // (format 0: the rendering kernels write their default planes, into the scratch)
+    shape.bytes = placed.bytes;
+    shape.resize.scratch = std::move(sc);
+    shape.resize.format = placed.format;
+    shape.resize.ow = ow;
+    shape.resize.oh = oh;
+    shape.resize.pitch_y = placed.pitch_y;
+    shape.resize.pitch_c = placed.pitch_c;
+    shape.resize.wide = placed.wide;
+    shape.resize.offsets = std::move(offs);
     out = std::move(shape);
     return H263MI_OK;
 }
@@ -1071,6 +1217,21 @@ int h263mi_batch_set_yuv_layout(h263mi_batch *b, const h263mi_yuv_layout *layout
     return H263MI_OK;
 }
 
+int h263mi_yuv_resize_extent(uint32_t n_streams, const h263mi_yuv_resize *r, uint64_t *bytes)
+{
+    return yuv_resize_extent(n_streams, r, bytes);
+}
+
+int h263mi_batch_set_yuv_resize(h263mi_batch *b, const h263mi_yuv_resize *r)
+{
+    if (!b) return H263MI_ERR_INVALID_ARGUMENT;
+    h263mi_batch::YuvLayout shape;
+    RC_TRY(make_yuv_resize_shape(b->device, b->n, b->L.width, b->L.height, r, shape));
+    DeviceGuard g(b->device);                  // (the shape it replaces frees its memory, unless a pending rendering holds it)
+    b->yuv = std::move(shape);
+    return H263MI_OK;
+}
+
 int h263mi_rgba_resize_extent(uint32_t n_streams, const h263mi_rgba_resize *r, uint64_t *bytes)
 {
     return rgba_resize_extent(n_streams, r, bytes);
@@ -1181,6 +1342,8 @@ int h263mi_batch_timing_end(h263mi_batch *b, h263mi_kernel_times *out)
         } else if (r.kernel == 1 || r.kernel == 3) {       // (3: k_rgba_resize, the second half of a resized rendering)
             out->post_ms += ms;
             out->post_launches += r.launches;
+        } else if (r.kernel == 4) {                        // (k_plane_resize: post-processing time of the renderings counted above)
+            out->post_ms += ms;
         } else {
             out->frame_ms += ms;
             out->frame_launches += r.launches;

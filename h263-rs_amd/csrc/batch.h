@@ -56,6 +56,17 @@ struct h263mi_yuv_offsets {
     ~h263mi_yuv_offsets();
 };
 
+// What k_plane_resize reads (h263mi_batch_set_yuv_resize): the full-size planes, tightly packed I420 per stream, that the
+// rendering kernels write for it by default, and the spans of its two geometries.  Shared with a pending rendering like the
+// RGBA scratch above.
+struct h263mi_plane_scratch {
+    int device = 0;
+    uint8_t *planes = nullptr;                 // n * (w*h + 2*cw*ch) bytes
+    h263mi::ResizeSpan *spans = nullptr;       // W' luma column spans, H' luma row spans, cW' chroma column spans, cH' chroma row spans
+    uint64_t bytes = 0;                        // device memory held (both allocations)
+    ~h263mi_plane_scratch();
+};
+
 struct h263mi_batch {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -107,6 +118,8 @@ struct h263mi_batch {
     // The layout of the deblocked planes in d_deblocked (h263mi_batch_set_yuv_layout).  format 0: none -- tightly packed I420
     // written by the default kernels, as ever.  Else the YUV instantiations write the planes (kernels.h: launch_post_yuv,
     // launch_frame_yuv), and RGBA asked for in the same call is rendered by a launch of its own.
+    // Or the planes are RESIZED (h263mi_batch_set_yuv_resize; then format stays 0): the default kernels write the full-size
+    // planes into the resize's scratch and k_plane_resize follows them on the same stream.  A layout or a resize, never both.
     struct YuvLayout {
         uint32_t format = 0;                   // 0, YUV_OUT_I420, YUV_OUT_NV12
         uint32_t pitch_y = 0, pitch_c = 0;
@@ -125,6 +138,16 @@ struct h263mi_batch {
             o.offsets = offsets ? offsets->d : nullptr;
             return o;
         }
+        // a resize that is not the full-size layout (scratch != nullptr): W' x H' planes in `format` at `offsets` of d_deblocked
+        struct Resize {
+            std::shared_ptr<h263mi_plane_scratch> scratch;
+            uint32_t format = 0;               // YUV_OUT_I420, YUV_OUT_NV12
+            uint32_t ow = 0, oh = 0, pitch_y = 0, pitch_c = 0;
+            bool wide = false;                 // pitches and offsets are all multiples of 4
+            std::vector<uint64_t> offsets;     // 3 per stream: Y, Cb or CbCr, Cr
+            bool on() const { return scratch != nullptr; }
+        } resize;
+        bool shaped() const { return on() || resize.on(); }      // (then `bytes` is what d_deblocked must hold)
     } yuv;
     struct PendingPost {
         bool valid = false;
@@ -133,12 +156,15 @@ struct h263mi_batch {
         OutLayout out;                         // the layout in force when the rendering was requested
         RgbaLayout::Resize resize;             // ... or the resize (then `rgba` is its scratch)
         uint8_t *const *resize_dst = nullptr;  // DEVICE array: stream s's resized picture, nullptr = none
+        const h263mi::PlaneDst *plane_dst = nullptr;   // yuv.resize: DEVICE array of the streams' planes (then `planes` is its scratch)
+        bool plane_wide = false;               // ... which all allow word stores
         uint8_t *rgba = nullptr, *planes = nullptr;
         uint8_t *const *rgba_ptrs = nullptr;   // DEVICE array of per-stream output pointers (a batch inside a mixed-size set)
         std::vector<int8_t> set;               // per stream: frame set it reads, -1 = nothing to post-process
     } pending;
     // per-stream output pointers for the kernels (made on first use)
     h263mi::UploadRing<uint8_t *> ptr_ring;
+    h263mi::UploadRing<h263mi::PlaneDst> plane_ring;       // ... and the plane pointers of a YUV resize
     uint32_t n = 0;
     h263mi::FrameLayout L{};
     uint8_t *frames[2] = {nullptr, nullptr};   // ping-pong frame sets, n * frame_bytes each
@@ -244,7 +270,8 @@ struct h263mi_batch {
     // ---- launch timing (h263mi_batch_timing_begin / _end); kernel ids: 0 k_recon, 1 k_post, 2 k_frame
     hipStream_t stream_of(int kernel_id) const { return (kernel_id == 1 && overlap_post) ? post_stream : stream; }
     int time_close();
-    // (kernel id 3: k_rgba_resize, queued on `on` behind the rendering it resizes; its time counts as post-processing)
+    // (kernel id 3: k_rgba_resize, queued on `on` behind the rendering it resizes; its time counts as post-processing.
+    // id 4: k_plane_resize, likewise -- its time is post-processing time, and post_launches goes on counting renderings)
     int time_begin(int kernel_id, hipStream_t on = nullptr);
 
     // ---- the work
@@ -267,6 +294,13 @@ struct h263mi_batch {
     int resize_dst(const std::vector<int8_t> &sets, uint8_t *d_rgba, uint8_t *const *host_ptrs, hipStream_t on, uint8_t *const **d_out);
     // k_rgba_resize of `rz` into `d_dst` (resize_dst), on `on`; nothing when no stream has a set (sets[s] < 0 for all)
     int launch_resize(const RgbaLayout::Resize &rz, const std::vector<int8_t> &sets, uint8_t *const *d_dst, hipStream_t on);
+    // a YUV resize `rz` of planes that go to d_planes: the DEVICE array of k_plane_resize's destinations -- stream s's planes at
+    // d_planes + its offsets, null where sets[s] < 0 -- uploaded on `on`; *wide: word stores are possible
+    int plane_resize_dst(const YuvLayout::Resize &rz, const std::vector<int8_t> &sets, uint8_t *d_planes, hipStream_t on,
+                         const h263mi::PlaneDst **d_out, bool *wide);
+    // k_plane_resize of `rz` into `d_dst` (plane_resize_dst), on `on`; nothing when no stream has a set
+    int launch_plane_resize(const YuvLayout::Resize &rz, const std::vector<int8_t> &sets, const h263mi::PlaneDst *d_dst, bool wide,
+                            hipStream_t on);
     // pipeline mode: the post-processing of the pictures just submitted is deferred to the next launch.
     // host_ptrs (or nullptr): n DEVICE pointers, the RGBA buffer of each stream (nullptr = none for it) instead of d_rgba.
     int note_pending(const Strengths &strength, uint8_t *d_rgba, uint8_t *d_planes, uint8_t *const *host_ptrs = nullptr);
@@ -292,6 +326,12 @@ int yuv_layout_extent(uint32_t n_streams, uint32_t w, uint32_t h, const h263mi_y
                       h263mi_batch::YuvLayout *shape = nullptr, std::vector<uint64_t> *offsets = nullptr);
 // the layout (NULL: none, format 0) for n streams of w x h on `device`, its offsets uploaded
 int make_yuv_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_yuv_layout *layout, h263mi_batch::YuvLayout &out);
+// h263mi_yuv_resize_extent; shape / offsets as yuv_layout_extent (of the W' x H' picture)
+int yuv_resize_extent(uint32_t n_streams, const h263mi_yuv_resize *r, uint64_t *bytes, h263mi_batch::YuvLayout *shape = nullptr,
+                      std::vector<uint64_t> *offsets = nullptr);
+// the YUV shape `r` (NULL: none) for n streams of w x h on `device`: the full-size layout it is by definition when W' = w and
+// H' = h, else the resize with a new scratch
+int make_yuv_resize_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_yuv_resize *r, h263mi_batch::YuvLayout &out);
 // h263mi_rgba_resize_extent for n streams
 int rgba_resize_extent(uint32_t n_streams, const h263mi_rgba_resize *r, uint64_t *bytes);
 // the layout that a resize of a w x h picture is by definition (full size, or 1/2 or 1/4 of sizes that 2 or 4 divide), into

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "dev_common.h"
+#include "plane_resize_kernel.inl"
 #include "resize_kernel.inl"
 
 namespace h263mi {
@@ -47,6 +48,10 @@ hipError_t launch_frame_yuv(const ReconArgs &rargs, const PostArgs &pargs, const
 // objects are also linked, in the CPU suite's ThreadSanitizer build (tests/tsan), against a stub runtime that has no resize
 // launcher.  The library always defines it (kernels.hip); h263mi_batch::launch_resize refuses to run without it.
 hipError_t launch_rgba_resize(const ResizeArgs &args, hipStream_t stream) __attribute__((weak));
+// k_plane_resize over args.n_pictures pictures (plane_resize_kernel.inl; bands, chunk and segs_y are set here): the luma and
+// chroma planes of every picture in ONE launch.  Weak like launch_rgba_resize; h263mi_batch::launch_plane_resize refuses to run
+// without it.
+hipError_t launch_plane_resize(const PlaneResizeArgs &args, hipStream_t stream) __attribute__((weak));
 hipError_t launch_synth_headers(const SynthArgs &args, hipStream_t stream);
 hipError_t launch_synth_coeffs(const SynthArgs &args, hipStream_t stream);
 // streaming probes: mode 0 copy in -> out, 1 read in (out = 16-byte sink), 2 write out; bytes is a multiple of 16;

@@ -4,6 +4,7 @@
 
 #include "post_kernel.inl"
 #include "recon_kernel.inl"
+#include "plane_resize_kernel.inl"
 #include "resize_kernel.inl"
 #include "synth.inl"
 
@@ -768,6 +769,35 @@ hipError_t launch_rgba_resize(const ResizeArgs &args, hipStream_t stream)
     a.chunk = (a.bands + 7) / 8;
     const dim3 grid(a.chunk * 8, a.n_pictures, (a.ow + 63) / 64);
     hipLaunchKernelGGL(k_rgba_resize, grid, dim3(64), 0, stream, a);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
+// k_plane_resize: area-average resampling of the full-size deblocked planes into I420 or NV12 (plane_resize_kernel.inl).  One
+// wave per workgroup, no barrier; blockIdx.y = picture, blockIdx.z = segment of PLANE_OUT output columns (the luma segments,
+// then the chroma segments: one launch for all planes), blockIdx.x = band of PLANE_ROWS output rows in XCD order, as
+// k_rgba_resize.  A chroma wave whose band lies below its planes (they have half the rows) leaves at once.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_plane_resize(PlaneResizeArgs a)
+{
+    __shared__ __attribute__((aligned(16))) PlaneLds lds;
+    const uint32_t band = (blockIdx.x & 7u) * a.chunk + (blockIdx.x >> 3);
+    if (band >= a.bands) return;
+    const int lane = threadIdx.x & 63;
+    PlaneLane t;
+    plane_resize_item(a, lds, band, blockIdx.z, blockIdx.y, [&](auto f) { f(lane, t); });
+}
+
+hipError_t launch_plane_resize(const PlaneResizeArgs &args, hipStream_t stream)
+{
+    if (!args.n_pictures) return hipSuccess;
+    if (args.n_pictures > 65535) return hipErrorInvalidValue;
+    PlaneResizeArgs a = args;
+    a.bands = (a.oh + PLANE_ROWS - 1) / PLANE_ROWS;
+    a.chunk = (a.bands + 7) / 8;
+    a.segs_y = (a.ow + PLANE_OUT - 1) / PLANE_OUT;
+    const dim3 grid(a.chunk * 8, a.n_pictures, a.segs_y + (a.cow + PLANE_OUT - 1) / PLANE_OUT);
+    hipLaunchKernelGGL(k_plane_resize, grid, dim3(64), 0, stream, a);
     return hipGetLastError();
 }
 

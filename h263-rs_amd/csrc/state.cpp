@@ -401,6 +401,64 @@ int h263mi_render_yuv(const h263mi_state *cs, uint8_t strength, const h263mi_yuv
     return H263MI_OK;
 }
 
+int h263mi_render_yuv_resize(const h263mi_state *cs, uint8_t strength, const h263mi_yuv_resize *r, uint8_t *out)
+{
+    h263mi_state *s = const_cast<h263mi_state *>(cs);
+    if (!s || !out || !r) return H263MI_ERR_INVALID_ARGUMENT;
+    if (!s->has_last || !s->b) return H263MI_ERR_NO_PICTURE;
+    h263mi_batch *b = s->b;
+    // the caller's shape: where its planes lie in `out`
+    h263mi_batch::YuvLayout host;
+    std::vector<uint64_t> off;
+    RC_TRY(yuv_resize_extent(1, r, nullptr, &host, &off));
+    if (r->out_width == b->L.width && r->out_height == b->L.height) {      // the full-size layout, by definition
+        h263mi_yuv_layout lay{};
+        lay.format = r->format;
+        lay.pitch_y = r->pitch_y;
+        lay.pitch_c = r->pitch_c;
+        lay.offsets_y = r->offsets_y;
+        lay.offsets_cb = r->offsets_cb;
+        lay.offsets_cr = r->offsets_cr;
+        return h263mi_render_yuv(cs, strength, &lay, out);
+    }
+    h263mi_batch::Strengths st;
+    RC_TRY(state_strength(s, strength, st));
+    DeviceGuard g(s->cfg.device_id);
+    // resized on the device at pitches that are multiples of 4, planes back to back (the word stores), then each plane copied
+    // out row by row into the caller's rectangle: nothing else of `out` is touched
+    const bool nv12 = host.format == YUV_OUT_NV12;
+    const uint32_t ow = r->out_width, oh = r->out_height, cow = (ow + 1) / 2, coh = (oh + 1) / 2, row_c = nv12 ? 2 * cow : cow;
+    const size_t dpy = ((size_t)ow + 3) / 4 * 4, dpc = ((size_t)row_c + 3) / 4 * 4;
+    h263mi_yuv_resize dev{};
+    dev.out_width = r->out_width;
+    dev.out_height = r->out_height;
+    dev.format = r->format;
+    dev.pitch_y = dpy;
+    dev.pitch_c = dpc;
+    h263mi_batch::YuvLayout shape;
+    RC_TRY(make_yuv_resize_shape(s->cfg.device_id, 1, b->L.width, b->L.height, &dev, shape));
+    const size_t bytes = (size_t)shape.bytes;
+    if (bytes > s->cap_yuv) {
+        if (s->d_yuv) (void)hipFree(s->d_yuv);
+        s->d_yuv = nullptr; s->cap_yuv = 0;
+        HIP_TRY(hipMalloc((void **)&s->d_yuv, bytes));
+        s->cap_yuv = bytes;
+    }
+    h263mi_batch::YuvLayout saved = std::move(b->yuv);
+    b->yuv = std::move(shape);
+    const int rc = b->render(st, nullptr, s->d_yuv);
+    shape = std::move(b->yuv);                  // (its scratch goes at the end, once the copies below have waited for it)
+    b->yuv = std::move(saved);
+    RC_TRY(rc);
+    const uint8_t *d_c0 = s->d_yuv + (size_t)oh * dpy;
+    HIP_TRY(hipMemcpy2DAsync(out + off[0], oh > 1 ? host.pitch_y : ow, s->d_yuv, dpy, ow, oh, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipMemcpy2DAsync(out + off[1], coh > 1 ? host.pitch_c : row_c, d_c0, dpc, row_c, coh, hipMemcpyDeviceToHost, b->stream));
+    if (!nv12)
+        HIP_TRY(hipMemcpy2DAsync(out + off[2], coh > 1 ? host.pitch_c : row_c, d_c0 + (size_t)coh * dpc, dpc, row_c, coh, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    return H263MI_OK;
+}
+
 int h263mi_render_rgba_pinned(const h263mi_state *cs, uint8_t strength, uint8_t *rgba_pinned)
 {
     h263mi_state *s = const_cast<h263mi_state *>(cs);

@@ -91,6 +91,8 @@ EXPORTS = [
     "h263mi_rgba_resize_extent", "h263mi_batch_set_rgba_resize", "h263mi_render_rgba_resize", "h263mi_mixed_set_rgba_resize",
     # ABI 7, additive: deblocked YUV 4:2:0 planes as I420 or NV12 with pitches and per-stream placement
     "h263mi_yuv_layout_extent", "h263mi_batch_set_yuv_layout", "h263mi_render_yuv",
+    # ABI 7, additive: the same planes resized to any W' x H' by area averaging
+    "h263mi_yuv_resize_extent", "h263mi_batch_set_yuv_resize", "h263mi_render_yuv_resize",
 ]
 YUV_I420, YUV_NV12 = 0, 1
 STRENGTH_FROM_HEADER = 0xFF
@@ -218,6 +220,45 @@ def yuv_layout_extent(n_streams, width, height, format=YUV_I420, pitch_y=0, pitc
     nb = C.c_uint64()
     _check(lib().h263mi_yuv_layout_extent(n_streams, width, height, C.byref(layout) if layout is not None else None, C.byref(nb)),
            "yuv_layout_extent")
+    del keep
+    return nb.value
+
+
+class YuvResize(C.Structure):
+    """h263mi_yuv_resize: the deblocked planes resized to out_width x out_height (luma; chroma ceil(W'/2) x ceil(H'/2)), each
+    plane the area average of its full-size plane, placed like a YuvLayout of an out_width x out_height picture."""
+    _fields_ = [("out_width", C.c_uint16), ("out_height", C.c_uint16), ("format", C.c_uint8), ("reserved", C.c_uint8 * 3),
+                ("pitch_y", C.c_uint64), ("pitch_c", C.c_uint64),
+                ("offsets_y", C.POINTER(C.c_uint64)), ("offsets_cb", C.POINTER(C.c_uint64)), ("offsets_cr", C.POINTER(C.c_uint64))]
+
+
+def make_yuv_resize(out_width, out_height, format=YUV_I420, pitch_y=0, pitch_c=0, offsets_y=None, offsets_cb=None,
+                    offsets_cr=None):
+    """-> (YuvResize, the offset arrays it points into: keep them alive with the struct)"""
+    r = YuvResize()
+    r.out_width = out_width
+    r.out_height = out_height
+    r.format = format
+    r.pitch_y = pitch_y
+    r.pitch_c = pitch_c
+    keep = []
+    for name, offs in (("offsets_y", offsets_y), ("offsets_cb", offsets_cb), ("offsets_cr", offsets_cr)):
+        if offs is not None:
+            arr = np.ascontiguousarray(offs, dtype=np.uint64)
+            setattr(r, name, arr.ctypes.data_as(C.POINTER(C.c_uint64)))
+            keep.append(arr)
+    return r, keep
+
+
+def yuv_resize_extent(n_streams, out_width, out_height, format=YUV_I420, pitch_y=0, pitch_c=0, offsets_y=None, offsets_cb=None,
+                      offsets_cr=None, resize=None):
+    """h263mi_yuv_resize_extent -> bytes d_deblocked must hold; H263Error when the resize is refused.  Needs no device.
+    resize: a YuvResize to pass as it is (else one is made of the other arguments)."""
+    keep = None
+    if resize is None:
+        resize, keep = make_yuv_resize(out_width, out_height, format, pitch_y, pitch_c, offsets_y, offsets_cb, offsets_cr)
+    nb = C.c_uint64()
+    _check(lib().h263mi_yuv_resize_extent(n_streams, C.byref(resize), C.byref(nb)), "yuv_resize_extent")
     del keep
     return nb.value
 
@@ -361,6 +402,9 @@ def lib():
         L.h263mi_yuv_layout_extent.argtypes = [u32, u16, u16, vp, C.POINTER(C.c_uint64)]
         L.h263mi_batch_set_yuv_layout.argtypes = [vp, vp]
         L.h263mi_render_yuv.argtypes = [vp, u8, vp, vp]
+        L.h263mi_yuv_resize_extent.argtypes = [u32, vp, C.POINTER(C.c_uint64)]
+        L.h263mi_batch_set_yuv_resize.argtypes = [vp, vp]
+        L.h263mi_render_yuv_resize.argtypes = [vp, u8, vp, vp]
         L.h263mi_default_parser_threads.restype = u32
         L.h263mi_default_parser_threads.argtypes = [u32, C.POINTER(u32)]
         _lib = L
@@ -573,6 +617,21 @@ class H263State:
         if layout is None:
             layout, keep = make_yuv_layout(format, pitch_y, pitch_c, offsets_y, offsets_cb, offsets_cr)
         _check(lib().h263mi_render_yuv(self._h, strength, C.byref(layout), _p(out)), "render_yuv")
+        del keep
+        return out
+
+    def render_yuv_resize(self, strength, out_width, out_height, format=YUV_I420, pitch_y=0, pitch_c=0):
+        """h263mi_render_yuv_resize with default placement: the extent's bytes (what lies between rows is zero here)"""
+        out = np.zeros(yuv_resize_extent(1, out_width, out_height, format, pitch_y, pitch_c), np.uint8)
+        return self.render_yuv_resize_into(strength, out, out_width, out_height, format, pitch_y, pitch_c)
+
+    def render_yuv_resize_into(self, strength, out, out_width, out_height, format=YUV_I420, pitch_y=0, pitch_c=0, offsets_y=None,
+                               offsets_cb=None, offsets_cr=None, resize=None):
+        """h263mi_render_yuv_resize into `out` (a uint8 array of at least the resize's extent); bytes outside the planes stay"""
+        keep = None
+        if resize is None:
+            resize, keep = make_yuv_resize(out_width, out_height, format, pitch_y, pitch_c, offsets_y, offsets_cb, offsets_cr)
+        _check(lib().h263mi_render_yuv_resize(self._h, strength, C.byref(resize), _p(out)), "render_yuv_resize")
         del keep
         return out
 
@@ -827,6 +886,19 @@ class Batch:
         if layout is None:
             layout, keep = make_yuv_layout(format, pitch_y, pitch_c, offsets_y, offsets_cb, offsets_cr)
         _check(lib().h263mi_batch_set_yuv_layout(self._h, C.byref(layout)), "batch_set_yuv_layout")
+        del keep
+
+    def set_yuv_resize(self, out_width=0, out_height=0, format=YUV_I420, pitch_y=0, pitch_c=0, offsets_y=None, offsets_cb=None,
+                       offsets_cr=None, default=False, resize=None):
+        """h263mi_batch_set_yuv_resize: d_deblocked holds out_width x out_height planes from now on (default=True: back to
+        tightly packed full-size I420)"""
+        if default:
+            _check(lib().h263mi_batch_set_yuv_resize(self._h, None), "batch_set_yuv_resize")
+            return
+        keep = None
+        if resize is None:
+            resize, keep = make_yuv_resize(out_width, out_height, format, pitch_y, pitch_c, offsets_y, offsets_cb, offsets_cr)
+        _check(lib().h263mi_batch_set_yuv_resize(self._h, C.byref(resize)), "batch_set_yuv_resize")
         del keep
 
     def set_rgba_resize(self, out_width=0, out_height=0, row_pitch=0, offsets=None, default=False):

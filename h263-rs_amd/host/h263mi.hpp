@@ -172,6 +172,15 @@ public:
         check(h263mi_render_yuv(s_, strength, layout, out.data()));
         return out;
     }
+    // the same resized to W' x H' (h263mi_yuv_resize): the resize's extent in bytes, the ones outside the planes zero
+    std::vector<uint8_t> render_yuv(uint8_t strength, const h263mi_yuv_resize &r) const
+    {
+        uint64_t bytes = 0;
+        check(h263mi_yuv_resize_extent(1, &r, &bytes));
+        std::vector<uint8_t> out((size_t)bytes);
+        check(h263mi_render_yuv_resize(s_, strength, &r, out.data()));
+        return out;
+    }
 
     // the same straight into page-locked memory of the caller (h263mi_host_alloc / h263mi_host_register): the buffer a
     // renderer reuses for every picture instead of the fresh Vec<u8> of bt601.rs:128; `rgba` holds width * height * 4 bytes

@@ -428,8 +428,8 @@ int h263mi_render_rgba_resize(const h263mi_state *s, uint8_t strength, const h26
 
 /*
  * DEBLOCKED YUV 4:2:0 OUTPUT LAYOUT (additive, ABI 7): where the filtered planes go inside d_deblocked.  The planes are always
- * full size (w x h luma, cw x ch chroma, cw = ceil(w/2), ch = ceil(h/2)); the RGBA layouts and resizes above apply to d_rgba
- * only and the two shapes are independent.  I420: three planes Y, Cb, Cr.  NV12: a Y plane and one plane of ch rows of cw
+ * full size (w x h luma, cw x ch chroma, cw = ceil(w/2), ch = ceil(h/2)) under a layout -- h263mi_yuv_resize below resizes them --;
+ * the RGBA layouts and resizes above apply to d_rgba only and the two shapes are independent.  I420: three planes Y, Cb, Cr.  NV12: a Y plane and one plane of ch rows of cw
  * interleaved Cb,Cr byte pairs.  Luma rows are pitch_y bytes apart, chroma rows pitch_c.
  * Default placement (all offset arrays NULL): picture s starts at s * P with P = h*pitch_y + k*ch*pitch_c (k = 2 for I420, 1 for
  * NV12); Y at 0, Cb (NV12: the CbCr plane) at h*pitch_y, Cr at h*pitch_y + ch*pitch_c.  I420 with both pitches 0 is the tightly
@@ -468,10 +468,50 @@ int h263mi_batch_set_yuv_layout(h263mi_batch *b, const h263mi_yuv_layout *layout
  * Bytes outside the planes' rectangles are untouched. */
 int h263mi_render_yuv(const h263mi_state *s, uint8_t strength, const h263mi_yuv_layout *layout, uint8_t *out);
 
+/*
+ * DEBLOCKED YUV 4:2:0 OUTPUT RESIZED TO ANY W' x H' (additive, ABI 7): the planes of h263mi_yuv_layout, each resized on its own
+ * by the area average that h263mi_rgba_resize documents, applied to one 8-bit channel.  For a source plane P of pw x ph and an
+ * output plane of pw' x ph', with ox(X, i) and oy(Y, j) the interval intersections of that comment (taken with pw, pw' and ph, ph'):
+ *     out[Y][X] = (sum_j sum_i oy(Y,j) * ox(X,i) * P[j][i] + floor(pw*ph/2)) div (pw*ph).
+ * Luma: (pw, ph, pw', ph') = (w, h, W', H').  Cb and Cr: (cw, ch, cW', cH') with cw = ceil(w/2), ch = ceil(h/2), cW' = ceil(W'/2),
+ * cH' = ceil(H'/2).  Exact integer arithmetic, one rounding (half up).  P is the picture's planes after deblock(strength)
+ * (0 = as decoded; H263MI_STRENGTH_FROM_HEADER where h263mi_render_rgba takes it).  Each chroma grid is treated as covering the
+ * picture area, as the luma grid does: that is the 4:2:0 siting of H.263 (chroma samples centred in their 2 x 2 luma blocks), so
+ * the resize introduces no phase shift between luma and chroma.
+ * Placement is exactly that of an h263mi_yuv_layout for a W' x H' picture: format, pitches (0 = W'; cW' for I420, 2*cW' for NV12),
+ * offset arrays and default placement as there.  W' = w, H' = h is the full-size layout byte for byte (and goes through the same
+ * kernels: no scratch, no second pass).
+ */
+typedef struct h263mi_yuv_resize {
+    uint16_t out_width, out_height;   /* W', H' >= 1: the luma size.  Chroma: cW' = ceil(W'/2), cH' = ceil(H'/2) */
+    uint8_t  format;                  /* H263MI_YUV_I420 or H263MI_YUV_NV12 */
+    uint8_t  reserved[3];             /* zero */
+    uint64_t pitch_y, pitch_c;        /* 0 = W'; cW' (I420) or 2*cW' (NV12) */
+    const uint64_t *offsets_y, *offsets_cb, *offsets_cr;   /* as h263mi_yuv_layout */
+} h263mi_yuv_resize;
+
+/* Pure host function, no HIP call: validates what h263mi_yuv_layout_extent(n_streams, W', H', ...) validates and returns the same
+ * byte count.  H263MI_ERR_INVALID_ARGUMENT additionally for r NULL, n_streams 0, W' or H' 0, or a reserved byte set. */
+int h263mi_yuv_resize_extent(uint32_t n_streams, const h263mi_yuv_resize *r, uint64_t *bytes);
+/* A batch has ONE YUV shape in force: a layout or a resize; each setter replaces the other, NULL restores the default (tightly
+ * packed full-size I420).  A refused resize leaves the shape in force untouched.  The YUV shape and the RGBA shape are
+ * independent: one call may write resized planes and RGBA in any of its shapes.  Every later call that writes d_deblocked follows
+ * the resize, as with h263mi_batch_set_yuv_layout (a deferred rendering of H263MI_CFG_PIPELINE_POST keeps the shape of its
+ * request; a checked batch holds d_deblocked to the resize extent before anything is queued).  Streams with nothing to render are
+ * not written, nor is any byte outside the planes' rectangles.  A destination whose pitches and offsets (and d_deblocked itself)
+ * are all multiples of 4 is written with word stores; any other is written correctly with byte stores.  Unless W' = w and
+ * H' = h, the batch keeps a device scratch of n_streams * (w*h + 2*cw*ch) bytes (the full-size planes) while the resize is in
+ * force; a second kernel (k_plane_resize) behind the rendering reads it. */
+int h263mi_batch_set_yuv_resize(h263mi_batch *b, const h263mi_yuv_resize *r);
+/* One state, into HOST memory: the last picture's planes, deblocked with `strength` and resized, in the shape of `r` for one
+ * stream (the offset arrays may be given, one entry each, as in h263mi_render_yuv).  Bytes outside the planes' rectangles are
+ * untouched. */
+int h263mi_render_yuv_resize(const h263mi_state *s, uint8_t strength, const h263mi_yuv_resize *r, uint8_t *out);
+
 /* deblock (strength 0 = off) + BT.601 of every stream's last picture into d_rgba
  * (DEVICE, n_streams * w*h*4 bytes, stream-major); d_deblocked (DEVICE, may be NULL)
  * additionally receives the filtered planes, n_streams * (w*h + 2*cw*ch) bytes as
- * Y,Cb,Cr per stream, tightly packed -- or in the shape of h263mi_batch_set_yuv_layout. */
+ * Y,Cb,Cr per stream, tightly packed -- or in the shape of h263mi_batch_set_yuv_layout / _set_yuv_resize. */
 /*
  * The same from HOST records, one picture per stream: the batch counterpart of h263mi_submit_picture for a server
  * whose parser threads fill one record array per stream.  mbs[s] / coeffs[s] hold stream s' macroblocks
