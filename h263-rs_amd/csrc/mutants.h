@@ -13,8 +13,18 @@
 //                                        Ha + Hb has absorbed it: +1 in some pixels of (1/2, 1/2) pieces, nowhere else
 //   -DH263MI_MUTATE_INTEGER_BORDER       border lanes of a wave whose vectors are all integer skip the clamped re-gather and
 //                                        use the bytes of their window as loaded
-// Included by recon_kernel.inl behind the definitions it uses (f32x2, splat2, BasisPtr, basis_pair).
-#pragma once
+// ... and three of the deblocking post-filter (tests/test_gpu_mutation.py with tests/post_mutation_probe.py):
+//   -DH263MI_MUTATE_DEBLOCK_HALF_ROUNDING    quartet_consts sets c1 = 0: |d1 / 2| rounds toward zero also where the reference
+//                                            shifts a negative d1 (deblock.rs:109): A and D off by one where that limit clips
+//   -DH263MI_MUTATE_DEBLOCK_FLOOR_EVERYWHERE trunc_mask is always 0: the scalar tails of the reference (deblock.rs:34-36) divide
+//                                            with shifts like its SIMD lanes
+//   -DH263MI_MUTATE_DEBLOCK_WRAP_COLUMNS     post_phase_hedges hands hfilter2 the strip column, not the picture column: the
+//                                            columns that ride in the last tile (post_tile_columns) miss the horizontal edges
+// Two parts.  The switches need nothing and are included by post_kernel.inl and recon_kernel.inl; the IDCT helper is included
+// by recon_kernel.inl (which defines H263MI_MUTANTS_WITH_IDCT) behind the definitions it uses (f32x2, splat2, BasisPtr,
+// basis_pair).
+#ifndef H263MI_MUTANTS_SWITCHES_H
+#define H263MI_MUTANTS_SWITCHES_H
 
 namespace h263mi {
 namespace mutants {
@@ -44,6 +54,30 @@ constexpr bool kIntegerBorder = true;
 #else
 constexpr bool kIntegerBorder = false;
 #endif
+#if defined(H263MI_MUTATE_DEBLOCK_HALF_ROUNDING)
+constexpr bool kDeblockHalfRounding = true;
+#else
+constexpr bool kDeblockHalfRounding = false;
+#endif
+#if defined(H263MI_MUTATE_DEBLOCK_FLOOR_EVERYWHERE)
+constexpr bool kDeblockFloorEverywhere = true;
+#else
+constexpr bool kDeblockFloorEverywhere = false;
+#endif
+#if defined(H263MI_MUTATE_DEBLOCK_WRAP_COLUMNS)
+constexpr bool kDeblockWrapColumns = true;
+#else
+constexpr bool kDeblockWrapColumns = false;
+#endif
+
+}  // namespace mutants
+}  // namespace h263mi
+#endif  // H263MI_MUTANTS_SWITCHES_H
+
+#if defined(H263MI_MUTANTS_WITH_IDCT) && !defined(H263MI_MUTANTS_IDCT_H)
+#define H263MI_MUTANTS_IDCT_H
+namespace h263mi {
+namespace mutants {
 
 // kPairwise: the eight rounded products summed as a balanced tree instead of in the order of the frequency index
 H263_DEV void idct_1d_pairwise(BasisPtr B, const float in[8], f32x2 out[4], f32x2 first)
@@ -60,3 +94,4 @@ H263_DEV void idct_1d_pairwise(BasisPtr B, const float in[8], f32x2 out[4], f32x
 
 }  // namespace mutants
 }  // namespace h263mi
+#endif  // H263MI_MUTANTS_WITH_IDCT

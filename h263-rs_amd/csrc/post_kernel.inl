@@ -21,6 +21,7 @@
 #pragma once
 
 #include "dev_common.h"
+#include "mutants.h"         // the switches of the tests' mutant builds (compile-time false in the product)
 
 namespace h263mi {
 
@@ -145,7 +146,7 @@ H263_HD QuartetConsts quartet_consts(int strength, int tm)
     k.s2 = (uint32_t)(2 * strength) * 0x00010001u;
     k.c7 = 0x00070007u & (uint32_t)tm;
     k.c3 = 0x00030003u & (uint32_t)tm;
-    k.c1 = 0x00010001u & ~(uint32_t)tm;
+    k.c1 = mutants::kDeblockHalfRounding ? 0u : (0x00010001u & ~(uint32_t)tm);      // (mutants.h: false in the product)
     return k;
 }
 // FLOOR: both quartets lie where the reference divides with arithmetic shifts (every quartet of an interior tile): the
@@ -199,7 +200,7 @@ H263_DEV uint32_t pair_low_bytes(uint32_t p)
 }
 
 // tm for position `pos` against the end of the reference's SIMD region: 0 (floor) for pos < simd_end, else -1
-H263_HD int trunc_mask(int pos, int simd_end) { return (simd_end - 1 - pos) >> 31; }
+H263_HD int trunc_mask(int pos, int simd_end) { return mutants::kDeblockFloorEverywhere ? 0 : (simd_end - 1 - pos) >> 31; }   // (mutants.h)
 
 // byte shuffles of the filtered samples (v_perm_b32 picks byte 0 of each operand: no masks, no shifts)
 // bytes 0,1 of `keep_lo` below bytes 0,1 of `put_hi`
@@ -417,14 +418,14 @@ H263_DEV void post_phase_hedges(const PostArgs &a, PostStrip &s, int lane, int s
         // luma: the edge's C row is picture row 8*sy = strip row 4; every lane takes 2 columns
         const int gy = sy * POST_SH, w = (int)a.L.width, h = (int)a.L.height;
         if (gy >= 8 && gy <= h - 2)                                      // edge_y <= height - 2 (deblock.rs:140)
-            hfilter2(s.y, POST_TW, 2, lane * 2, strength, post_wrap_x(a, xl + lane * 2), (w / 8) * 8, w, edge_tile);
+            hfilter2(s.y, POST_TW, 2, lane * 2, strength, mutants::kDeblockWrapColumns ? xl + lane * 2 : post_wrap_x(a, xl + lane * 2), (w / 8) * 8, w, edge_tile);   // (mutants.h)
     }
     if (!a.luma_only && (sy & 1) == 0) {
         // chroma strip rows [4*sy-2, 4*sy+2) hold an edge only when 4*sy is a multiple of 8
         const int gy = sy * POST_CSH, w = (int)a.L.cwidth, h = (int)a.L.cheight;
         const int plane = lane >> 5, col = (lane & 31) * 2;
         if (gy >= 8 && gy <= h - 2)
-            hfilter2(s.c[plane], POST_CW, 0, col, strength, post_wrap_cx(a, xl / 2 + col), (w / 8) * 8, w, edge_tile);
+            hfilter2(s.c[plane], POST_CW, 0, col, strength, mutants::kDeblockWrapColumns ? xl / 2 + col : post_wrap_cx(a, xl / 2 + col), (w / 8) * 8, w, edge_tile);
     }
 }
 

@@ -308,6 +308,7 @@ H263_DEV BasisPtr basis_table_sixteenth()
 H263_DEV f32x2 basis_pair(BasisPtr B, int f, int ip) { f32x2 r = {B[f][2 * ip], B[f][2 * ip + 1]}; return r; }
 
 }  // namespace h263mi
+#define H263MI_MUTANTS_WITH_IDCT
 #include "mutants.h"         // the arithmetic mutants of the tests (compile-time off in the product)
 namespace h263mi {
 

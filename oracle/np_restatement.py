@@ -9,6 +9,7 @@ gathers) so that a transcription slip in either shows up as a disagreement:
   idct               : h263/src/decoder/cpu/idct.rs:39-65, 82-201
   motion compensation: h263/src/decoder/cpu/gather.rs:16-204, h263/src/types.rs:721-768
   picture assembly   : h263/src/decoder/state.rs:173-191, 421-458
+  deblocking filter  : deblock/src/deblock.rs:13-42, 99-127, 136-181, 185-299 (whole passes at once, with a trace)
 
 Parity status: UNPINNED by the reference's own tests (it has none for these functions).
 """
@@ -305,3 +306,106 @@ def predict_picture(width, height, mbs, ref):
     cb = gather_plane(np.asarray(ref[1], np.uint8).reshape(ch, cw), c[..., 0], c[..., 1])
     cr = gather_plane(np.asarray(ref[2], np.uint8).reshape(ch, cw), c[..., 0], c[..., 1])
     return 0, (y[:h, :w].astype(np.uint8).ravel(), cb[:ch, :cw].astype(np.uint8).ravel(), cr[:ch, :cw].astype(np.uint8).ravel())
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The deblocking post-filter (deblock.rs).  Structure: each of the two passes is ONE array expression over all of its
+# quartets (they are disjoint inside a pass), with the division semantics a per-quartet flag: the reference's SIMD
+# lanes shift (floor, deblock.rs:107-109), its scalar tails divide (truncation, deblock.rs:34-36).
+# ---------------------------------------------------------------------------------------------------------------
+QUARTET_DTYPE = np.dtype([("dir", "u1"), ("x", "<i4"), ("y", "<i4"), ("abcd", "u1", (4,)), ("floor", "?")])
+DIR_H, DIR_V = 0, 1     # a horizontal block edge (deblock_horiz: A..D are four rows), a vertical one (four columns)
+
+
+def _div_pow2(x, k, floor):
+    """x / 2^k as the position divides: `>> k` of an i16 (floor) where `floor`, Rust's `/` (toward zero) elsewhere"""
+    x = np.asarray(x, np.int64)
+    return np.where(floor | (x >= 0), x >> k, -((-x) >> k))
+
+
+def process_quartets(A, B, C, D, strength, floor, half_rounds_toward_zero=False):
+    """deblock.rs:29-42 (floor False) / 99-127 (floor True) for arrays of quartets; returns the four byte arrays.
+    half_rounds_toward_zero: NOT the reference -- d1 / 2 divides toward zero at every position (the model of the
+    `dbhalf` mutant of csrc/mutants.h)."""
+    A, B, C, D = (np.asarray(v, np.int64) for v in (A, B, C, D))
+    floor = np.broadcast_to(np.asarray(floor, bool), A.shape)
+    S = int(strength)
+    d = _div_pow2(A - 4 * B + 4 * C - D, 3, floor)
+    d1 = np.sign(d) * np.maximum(np.abs(d) - np.maximum(2 * (np.abs(d) - S), 0), 0)        # up_down_ramp
+    lim = np.abs(_div_pow2(d1, 1, floor & (not half_rounds_toward_zero)))
+    d2 = np.clip(_div_pow2(A - D, 2, floor), -lim, lim)                                       # clipd1
+    return ((A - d2) & 255).astype(np.uint8), np.clip(B + d1, 0, 255).astype(np.uint8), \
+        np.clip(C - d1, 0, 255).astype(np.uint8), ((D + d2) & 255).astype(np.uint8)
+
+
+def _pass_trace(direction, xs, ys, quad, floor):
+    t = np.zeros(quad[0].size, QUARTET_DTYPE)
+    t["dir"] = direction
+    t["x"], t["y"] = np.broadcast_to(xs, quad[0].shape).ravel(), np.broadcast_to(ys, quad[0].shape).ravel()
+    t["abcd"] = np.stack([q.ravel() for q in quad], axis=1)
+    t["floor"] = np.broadcast_to(floor, quad[0].shape).ravel()
+    return t
+
+
+def _deblock_horiz(p, strength, floor_everywhere=False, skip_columns=0, half_rounds_toward_zero=False):
+    """deblock.rs:136-181 in place on the 2-D plane p; returns the pass's trace (x, y = position of the A sample).
+    The C rows are 8, 16, ... <= height - 2; columns below 8 * (width / 8) go through process_simd, the rest through
+    process.  (A plane of fewer than 2 rows is outside the reference's domain -- `height - 2` underflows -- and is left
+    alone here.)"""
+    h, w = p.shape
+    edges = np.arange(8, h - 1, 8) if h >= 10 else np.zeros(0, np.int64)
+    if edges.size == 0 or skip_columns >= w:
+        return np.zeros(0, QUARTET_DTYPE)
+    cols = np.arange(skip_columns, w)
+    floor = (cols < 8 * (w // 8)) | floor_everywhere
+    quad = [p[np.ix_(edges - 2 + k, cols)] for k in range(4)]
+    trace = _pass_trace(DIR_H, cols[None, :], (edges - 2)[:, None], quad, floor[None, :])
+    out = process_quartets(*quad, strength, floor[None, :], half_rounds_toward_zero)
+    for k in range(4):
+        p[np.ix_(edges - 2 + k, cols)] = out[k]
+    return trace
+
+
+def _deblock_vert(p, strength, floor_everywhere=False, half_rounds_toward_zero=False):
+    """deblock.rs:185-299 in place: nothing below a width of 10; else, in every row, the 8-sample chunks of row[2..]
+    carry A..D in their samples 4..7 (columns 8j + 6 .. 8j + 9).  The rows of whole groups of 8 (chunks_exact_mut(width * 8))
+    go through process_simd, the remaining rows through process."""
+    h, w = p.shape
+    if w < 10:
+        return np.zeros(0, QUARTET_DTYPE)
+    a_cols = 2 + 8 * np.arange((w - 2) // 8) + 4
+    rows = np.arange(h)
+    floor = (rows < 8 * (h // 8)) | floor_everywhere
+    quad = [p[:, a_cols + k] for k in range(4)]
+    trace = _pass_trace(DIR_V, a_cols[None, :], rows[:, None], quad, floor[:, None])
+    out = process_quartets(*quad, strength, floor[:, None], half_rounds_toward_zero)
+    for k in range(4):
+        p[:, a_cols + k] = out[k]
+    return trace
+
+
+def deblock_trace(plane, width, strength, mutation=None, skip_columns=0):
+    """deblock.rs:305-315 with everything it does on the way: returns (result, plane after the horizontal-edge pass
+    alone, trace), flat uint8 planes and one QUARTET_DTYPE row per filtered quartet, the pass of the horizontal edges
+    first: direction, position of the A sample, the four bytes AS THAT PASS READS THEM, floor or truncating division.
+    mutation (never the reference; the models of the post-filter mutants of csrc/mutants.h):
+      "dbhalf"  d1 / 2 divides toward zero at every position
+      "dbfloor" every position divides with shifts
+      "dbwrap"  the pass of the horizontal edges leaves the first `skip_columns` columns alone"""
+    assert mutation in (None, "dbhalf", "dbfloor", "dbwrap")
+    data = np.asarray(plane, np.uint8).ravel()
+    assert width > 0 and data.size % width == 0
+    p = data.reshape(-1, width).copy()
+    kw = dict(floor_everywhere=mutation == "dbfloor", half_rounds_toward_zero=mutation == "dbhalf")
+    th = _deblock_horiz(p, strength, skip_columns=skip_columns if mutation == "dbwrap" else 0, **kw)
+    after_h = p.ravel().copy()
+    tv = _deblock_vert(p, strength, **kw)
+    return p.ravel(), after_h, np.concatenate([th, tv])
+
+
+def deblock(plane, width, strength):
+    return deblock_trace(plane, width, strength)[0]
+
+
+def deblock_horizontal_pass(plane, width, strength):
+    return deblock_trace(plane, width, strength)[1]

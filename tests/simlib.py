@@ -23,7 +23,8 @@ _libs = {}
 
 
 def lib(asan=False, variant=None):
-    """variant: "blend" / "intborder" = the checker built with that motion-compensation mutation (csrc/mutants.h)"""
+    """variant: "blend" / "intborder" = the checker built with that motion-compensation mutation, "dbhalf" / "dbfloor" /
+    "dbwrap" = with that mutation of the post-filter (csrc/mutants.h)"""
     name = "libh263mi_sim_%s.so" % variant if variant else ("libh263mi_sim_asan.so" if asan else "libh263mi_sim.so")
     if name not in _libs:
         subprocess.check_call(["make", "-C", SIM_DIR, "-s", name])
@@ -163,14 +164,14 @@ def _recon_with(Lib, L, w, h, mbs, coeffs, ref):
     return int(status[0]), unpack_frame(L, cur)
 
 
-def post(w, h, planes, strength, want_rgba=True, want_planes=True, luma_only=False, asan=False):
+def post(w, h, planes, strength, want_rgba=True, want_planes=True, luma_only=False, asan=False, variant=None):
     L = layout(w, h)
     if luma_only:
         planes = (planes[0], np.zeros(L.cwidth * L.cheight, np.uint8), np.zeros(L.cwidth * L.cheight, np.uint8))
     f = pack_frame(L, planes)
     rgba = np.full(w * h * 4, 0x11, np.uint8) if want_rgba else None
     po = np.full(w * h + 2 * L.cwidth * L.cheight, 0x22, np.uint8) if want_planes else None
-    lib(asan).sim_post(w, h, 1, _p(f), strength, _p(rgba), _p(po), 1 if luma_only else 0)
+    lib(asan, variant).sim_post(w, h, 1, _p(f), strength, _p(rgba), _p(po), 1 if luma_only else 0)
     out_planes = None
     if po is not None:
         n, c = w * h, L.cwidth * L.cheight

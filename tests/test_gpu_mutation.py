@@ -9,7 +9,13 @@ library must reproduce the reference arithmetic (idct.rs:52-65, 171-196) pixel f
 Two more mutants are of the MOTION COMPENSATION (csrc/mutants.h; probe and models: tests/mc_mutation_probe.py):
   libh263mi_blend.so      blend_rows without its `^ (both & dm)` exclusion: +1 in some pixels of (1/2, 1/2) pieces
   libh263mi_intborder.so  border lanes of an all-integer wave skip the clamped re-gather
-Their arithmetic is integer: each must differ from the oracle AND equal its numpy model on every byte."""
+Their arithmetic is integer: each must differ from the oracle AND equal its numpy model on every byte.
+
+Three more are of the DEBLOCKING POST-FILTER (csrc/mutants.h; probe and models: tests/post_mutation_probe.py):
+  libh263mi_dbhalf.so     |d1 / 2| rounds toward zero where the reference shifts a negative d1
+  libh263mi_dbfloor.so    the scalar tails of the reference divide with shifts like its SIMD lanes
+  libh263mi_dbwrap.so     the columns that ride in the last post tile miss the horizontal block edges
+Likewise: each differs from the oracle and equals, on every byte, the numpy restatement with that mutation switched on."""
 import json
 import os
 import subprocess
@@ -191,3 +197,46 @@ def test_mc_probe_through_the_product_build_is_clean(tmp_path, mc_probe_expected
     for name, pic, ref, want in mc_probe_expected:
         diff = mc.first_difference(pic, tuple(clean["%s_%d" % (name, i)] for i in range(3)), want)
         assert diff is None, "the product build, picture %s: %s" % (name, diff)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the post-filter mutants
+# ---------------------------------------------------------------------------------------------------------------
+def _post_probe(lib_path, tmp_path, name):
+    out = str(tmp_path / (name + ".npz"))
+    env = dict(os.environ, H263MI_LIB=lib_path)
+    subprocess.run([sys.executable, os.path.join(HERE, "post_mutation_probe.py"), out], env=env, check=True, timeout=300)
+    return np.load(out)
+
+
+@pytest.fixture(scope="module")
+def post_probe_oracle():
+    import post_mutation_probe as probe
+    return probe.expectations()
+
+
+@pytest.mark.parametrize("mutant", ["dbhalf", "dbfloor", "dbwrap"])
+def test_post_mutant_build_fails_exactly_as_its_model_predicts(mutant, tmp_path, post_probe_oracle):
+    """table pictures of tests/post_cases.py through a mutant build (child process): it must differ from the oracle, every
+    byte must be the one the numpy model of the mutation predicts, and on the table (a) planes it must differ where the
+    classifier says that mutation can show (test_sim_post_sweep.check_where_the_mutant_differs)"""
+    import post_mutation_probe as probe
+    import test_sim_post_sweep as cpu
+    lib = os.path.join(PKG, "mutants", "libh263mi_%s.so" % mutant)
+    if not os.path.exists(lib):                                  # normally built by __graft_entry__.build()
+        subprocess.check_call(["make", "-C", PKG, "-s", "mutants"])
+    got = _post_probe(lib, tmp_path, mutant)
+    names, n = probe.compare(got, probe.expectations(mutant))
+    assert n == 0, "the %s mutant (got) against its model (expected): %d bytes differ, in %s" % (mutant, n, names[:5])
+    names, n = probe.compare(got, post_probe_oracle)
+    print("%s mutant: %d bytes differ from the oracle, in %d of %d planes; all as its model predicts" % (mutant, n, len(names), len(post_probe_oracle)))
+    assert n > 0, "the %s mutant went unnoticed" % mutant
+    cpu.check_where_the_mutant_differs(mutant, got, post_probe_oracle)
+
+
+def test_post_probe_through_the_product_build_is_clean(tmp_path, post_probe_oracle):
+    """the same child-process path with the product library: every byte is the oracle's"""
+    import post_mutation_probe as probe
+    clean = _post_probe(os.path.join(PKG, "libh263mi.so"), tmp_path, "product")
+    names, n = probe.compare(clean, post_probe_oracle)
+    assert n == 0, "the product build: %d bytes differ, in %s" % (n, names[:5])
