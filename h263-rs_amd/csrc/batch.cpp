@@ -590,7 +590,64 @@ int h263mi_batch::copy_yuv(uint32_t s, uint8_t *y, uint8_t *cb, uint8_t *cr)
     return H263MI_OK;
 }
 
+int h263mi_batch::digest_yuv(uint32_t seed, uint32_t *digests, int *stream_rc)
+{
+    if (!digests || !digest_seed_valid(seed)) return H263MI_ERR_INVALID_ARGUMENT;
+    RC_TRY(time_close());                        // a digest is not part of any kernel's time
+    // DecodedPicture planes are exact-size (picture.rs:39-58): the windows of the pitched planes, where they are
+    digest_planes.clear();
+    bool missing = false;
+    for (uint32_t i = 0; i < n; i++) {
+        if (ss[i].cur < 0) {
+            missing = true;
+            continue;
+        }
+        const uint64_t f = (uint64_t)(frames[ss[i].cur] - frames[0]) + (uint64_t)i * L.frame_bytes;
+        digest_planes.push_back(h263mi_digest_span{f, L.pitch_y, L.width, L.height, i, 0});
+        digest_planes.push_back(h263mi_digest_span{f + L.off_cb, L.pitch_c, L.cwidth, L.cheight, i, 0});
+        digest_planes.push_back(h263mi_digest_span{f + L.off_cr, L.pitch_c, L.cwidth, L.cheight, i, 0});
+    }
+    if (!digest_planes.empty())
+        RC_TRY(digest_spans(digest_words, placement, frames[0], 2ull * n * L.frame_bytes, digest_planes.data(),
+                            (uint32_t)digest_planes.size(), seed, digests, n, stream));
+    for (uint32_t i = 0; i < n; i++) {
+        if (ss[i].cur < 0) digests[i] = 0;
+        if (stream_rc) stream_rc[i] = ss[i].cur < 0 ? H263MI_ERR_NO_PICTURE : H263MI_OK;
+    }
+    return missing && !stream_rc ? H263MI_ERR_NO_PICTURE : H263MI_OK;
+}
+
 namespace h263mi {
+
+int digest_spans(PinnedPair<uint64_t> &buf, const HostPlacement &where, const uint8_t *d_base, uint64_t buffer_bytes,
+                 const h263mi_digest_span *spans, uint32_t n_spans, uint32_t seed, uint32_t *digests, uint32_t n_digests,
+                 hipStream_t stream)
+{
+    if (!digests || !digest_table(spans, n_spans, n_digests, buffer_bytes, d_base != nullptr, seed, nullptr, nullptr, nullptr))
+        return H263MI_ERR_INVALID_ARGUMENT;
+    if (!launch_digest) return H263MI_ERR_HIP;             // (kernels.h: only a stub runtime lacks it)
+    // one buffer, in 64-bit words: [the spans][A, B per digest][the digests, two to a word]
+    static_assert(sizeof(DigestSpan) % 8 == 0, "the span table is addressed in 64-bit words");
+    const size_t w_spans = (size_t)n_spans * (sizeof(DigestSpan) / 8), w_acc = 2 * (size_t)n_digests, w_out = ((size_t)n_digests + 1) / 2;
+    RC_TRY(buf.reserve(w_spans + w_acc + w_out, 0, where));
+    DigestArgs a{};
+    digest_table(spans, n_spans, n_digests, buffer_bytes, d_base != nullptr, seed, reinterpret_cast<DigestSpan *>(buf.h),
+                 reinterpret_cast<unsigned long long *>(buf.h + w_spans), &a.n_items);
+    a.base = d_base;
+    a.spans = reinterpret_cast<const DigestSpan *>(buf.d);
+    a.acc = reinterpret_cast<unsigned long long *>(buf.d + w_spans);
+    a.n_spans = n_spans;
+    DigestFinalArgs f{};
+    f.acc = a.acc;
+    f.out = reinterpret_cast<uint32_t *>(buf.d + w_spans + w_acc);
+    f.n_digests = n_digests;
+    HIP_TRY(hipMemcpyAsync(buf.d, buf.h, (w_spans + w_acc) * 8, hipMemcpyHostToDevice, stream));
+    HIP_TRY(launch_digest(a, f, stream));
+    HIP_TRY(hipMemcpyAsync(buf.h + w_spans + w_acc, f.out, (size_t)n_digests * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    memcpy(digests, buf.h + w_spans + w_acc, (size_t)n_digests * 4);
+    return H263MI_OK;
+}
 
 int make_strengths(uint8_t strength, const uint8_t *strengths, uint32_t n, bool from_header_allowed, h263mi_batch::Strengths &out)
 {
@@ -1299,6 +1356,46 @@ int h263mi_batch_copy_yuv(h263mi_batch *b, uint32_t stream, uint8_t *y, uint8_t 
     if (!b) return H263MI_ERR_INVALID_ARGUMENT;
     DeviceGuard g(b->device);
     return b->copy_yuv(stream, y, cb, cr);
+}
+
+int h263mi_batch_digest_yuv(h263mi_batch *b, uint32_t seed, uint32_t *digests, int *stream_rc)
+{
+    if (!b) return H263MI_ERR_INVALID_ARGUMENT;
+    DeviceGuard g(b->device);
+    return digest_rc(b->digest_yuv(seed, digests, stream_rc));
+}
+
+// the staging of h263mi_adler32_spans_on: per host thread and device, and it only grows (as the scratch of h263mi_deblock)
+struct DigestScratch {
+    int device = -1;
+    PinnedPair<uint64_t> words;
+};
+static thread_local DigestScratch tls_digest;
+
+int h263mi_adler32_spans_on(const h263mi_backend_cfg *cfg, const uint8_t *d_base, uint64_t buffer_bytes, const h263mi_digest_span *spans,
+                            uint32_t n_spans, uint32_t seed, uint32_t *digests, uint32_t n_digests)
+{
+    if (!digests || !digest_table(spans, n_spans, n_digests, buffer_bytes, d_base != nullptr, seed, nullptr, nullptr, nullptr))
+        return H263MI_ERR_INVALID_ARGUMENT;
+    const int dev = cfg ? cfg->device_id : 0;
+    RC_TRY(check_device(dev));
+    DeviceGuard g(dev);
+    if (tls_digest.device != dev) {
+        tls_digest.words.release();
+        tls_digest.device = dev;
+    }
+    return digest_rc(digest_spans(tls_digest.words, HostPlacement(), d_base, buffer_bytes, spans, n_spans, seed, digests, n_digests,
+                                  cfg ? (hipStream_t)cfg->stream : nullptr));
+}
+
+int h263mi_batch_adler32_spans(h263mi_batch *b, const uint8_t *d_base, uint64_t buffer_bytes, const h263mi_digest_span *spans,
+                               uint32_t n_spans, uint32_t seed, uint32_t *digests, uint32_t n_digests)
+{
+    if (!b || !digests || !digest_table(spans, n_spans, n_digests, buffer_bytes, d_base != nullptr, seed, nullptr, nullptr, nullptr))
+        return H263MI_ERR_INVALID_ARGUMENT;
+    DeviceGuard g(b->device);
+    RC_TRY(digest_rc(b->sync()));                // (the deferred rendering of a pipelined batch, the second stream of an overlapped one)
+    return digest_rc(digest_spans(b->digest_words, b->placement, d_base, buffer_bytes, spans, n_spans, seed, digests, n_digests, b->stream));
 }
 
 int h263mi_batch_timing_begin(h263mi_batch *b)

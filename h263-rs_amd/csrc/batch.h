@@ -313,10 +313,26 @@ struct h263mi_batch {
     // stream_rc (may be null): per stream 0, H263MI_ERR_UNCODED_IFRAME_BLOCKS or H263MI_ERR_INVALID_ARGUMENT
     int sync(int *stream_rc = nullptr);
     int copy_yuv(uint32_t s, uint8_t *y, uint8_t *cb, uint8_t *cr);
+    // ---- digests (h263mi_batch_digest_yuv, h263mi_batch_adler32_spans): the span table, the accumulators and the results of a
+    // call, pinned and on the device (h263mi::digest_spans), and the table of the frame store's planes
+    h263mi::PinnedPair<uint64_t> digest_words;
+    std::vector<h263mi_digest_span> digest_planes;
+    // the Adler-32 of Y, Cb, Cr of every stream's last picture, read in place (3 spans per stream, one launch pair); a stream
+    // without a picture: digest 0, stream_rc H263MI_ERR_NO_PICTURE -- which is also what the call returns when stream_rc is null
+    int digest_yuv(uint32_t seed, uint32_t *digests, int *stream_rc);
 };
 
 namespace h263mi {
 
+// h263mi_adler32_spans_on on `stream` of the current device, staged through `buf` (grown when a call needs more).  The table is
+// checked before any device call.
+int digest_spans(PinnedPair<uint64_t> &buf, const HostPlacement &where, const uint8_t *d_base, uint64_t buffer_bytes,
+                 const h263mi_digest_span *spans, uint32_t n_spans, uint32_t seed, uint32_t *digests, uint32_t n_digests,
+                 hipStream_t stream);
+// what the digest entry points report for a failure of the HIP runtime: H263MI_ERR_HIP, an allocation included
+inline int digest_rc(int rc) { return rc == H263MI_ERR_OUT_OF_MEMORY ? H263MI_ERR_HIP : rc; }
+// both halves of an Adler-32 start value are residues
+inline bool digest_seed_valid(uint32_t seed) { return (seed & 0xffffu) < DIGEST_MOD && (seed >> 16) < DIGEST_MOD; }
 // h263mi_rgba_layout_extent; out_kernel (may be null): what the kernels are told (pitch 0 = today's layout)
 int rgba_layout_extent(uint32_t n_streams, uint32_t w, uint32_t h, const h263mi_rgba_layout *layout, uint32_t *out_w,
                        uint32_t *out_h, uint64_t *bytes, h263mi_batch::OutLayout *out_kernel = nullptr);

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "dev_common.h"
+#include "digest_kernel.inl"
 #include "plane_resize_kernel.inl"
 #include "resize_kernel.inl"
 
@@ -52,6 +53,9 @@ hipError_t launch_rgba_resize(const ResizeArgs &args, hipStream_t stream) __attr
 // chroma planes of every picture in ONE launch.  Weak like launch_rgba_resize; h263mi_batch::launch_plane_resize refuses to run
 // without it.
 hipError_t launch_plane_resize(const PlaneResizeArgs &args, hipStream_t stream) __attribute__((weak));
+// k_digest over args.n_items work items, then k_digest_final over fin.n_digests digests (digest_kernel.inl): the launch pair of one
+// digest call, whatever it covers.  Weak like launch_rgba_resize; the digest entry points refuse to run without it.
+hipError_t launch_digest(const DigestArgs &args, const DigestFinalArgs &fin, hipStream_t stream) __attribute__((weak));
 hipError_t launch_synth_headers(const SynthArgs &args, hipStream_t stream);
 hipError_t launch_synth_coeffs(const SynthArgs &args, hipStream_t stream);
 // streaming probes: mode 0 copy in -> out, 1 read in (out = 16-byte sink), 2 write out; bytes is a multiple of 16;

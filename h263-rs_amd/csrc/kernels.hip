@@ -2,6 +2,7 @@
 // Built with: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (no fast-math).
 #include "kernels.h"
 
+#include "digest_kernel.inl"
 #include "post_kernel.inl"
 #include "recon_kernel.inl"
 #include "plane_resize_kernel.inl"
@@ -798,6 +799,41 @@ hipError_t launch_plane_resize(const PlaneResizeArgs &args, hipStream_t stream)
     a.segs_y = (a.ow + PLANE_OUT - 1) / PLANE_OUT;
     const dim3 grid(a.chunk * 8, a.n_pictures, a.segs_y + (a.cow + PLANE_OUT - 1) / PLANE_OUT);
     hipLaunchKernelGGL(k_plane_resize, grid, dim3(64), 0, stream, a);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
+// k_digest, k_digest_final: Adler-32 of pitched rows in device memory (digest_kernel.inl).  One wave per workgroup, no barrier;
+// a wave takes the work items blockIdx.x, blockIdx.x + gridDim.x, ... -- one each unless a call has more items than
+// DIGEST_GRID_MAX -- and adds their terms to the digests' accumulators; the second launch reduces and packs them.
+// ---------------------------------------------------------------------------------------
+constexpr uint64_t DIGEST_GRID_MAX = 1u << 20;
+
+__global__ __launch_bounds__(64) void k_digest(DigestArgs a)
+{
+    __shared__ __attribute__((aligned(16))) DigestLds lds;
+    const int lane = threadIdx.x & 63;
+    DigestLane t;
+    for (uint64_t item = blockIdx.x; item < a.n_items; item += gridDim.x)
+        digest_item(a, lds, item, [&](auto f) { f(lane, t); });
+}
+
+__global__ __launch_bounds__(256) void k_digest_final(DigestFinalArgs f)
+{
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k < f.n_digests) digest_final(f, k);
+}
+
+hipError_t launch_digest(const DigestArgs &args, const DigestFinalArgs &fin, hipStream_t stream)
+{
+    if (!fin.n_digests) return hipSuccess;
+    if (args.n_items) {
+        const uint32_t grid = (uint32_t)(args.n_items < DIGEST_GRID_MAX ? args.n_items : DIGEST_GRID_MAX);
+        hipLaunchKernelGGL(k_digest, dim3(grid), dim3(64), 0, stream, args);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_digest_final, dim3((fin.n_digests + 255u) / 256u), dim3(256), 0, stream, fin);
     return hipGetLastError();
 }
 

@@ -478,6 +478,41 @@ int h263mi_mixed_copy_yuv(h263mi_mixed *m, uint32_t stream, uint8_t *y, uint8_t 
     return m->classes[m->cls[stream]].b->copy_yuv((uint32_t)m->slot[stream], y, cb, cr);
 }
 
+int h263mi_mixed_digest_yuv(h263mi_mixed *m, uint32_t seed, uint32_t *digests, int *stream_rc)
+{
+    if (!m || !digests || !digest_seed_valid(seed)) return H263MI_ERR_INVALID_ARGUMENT;
+    DeviceGuard g(m->cfg.device_id);
+    for (uint32_t i = 0; i < m->n; i++) {
+        digests[i] = 0;
+        if (stream_rc) stream_rc[i] = H263MI_ERR_NO_PICTURE;
+    }
+    // one launch pair per size class that has pictures; a slot nobody sits in digests nothing (its stream state is empty)
+    bool missing = false;
+    std::vector<uint32_t> of_slot;
+    std::vector<int> rc_of_slot;
+    for (h263mi_mixed::SizeClass &c : m->classes) {
+        if (!c.b || !c.b->any_picture()) continue;
+        of_slot.assign(c.b->n, 0u);
+        rc_of_slot.assign(c.b->n, H263MI_OK);
+        RC_TRY(digest_rc(c.b->digest_yuv(seed, of_slot.data(), rc_of_slot.data())));
+        for (uint32_t s = 0; s < c.b->n; s++) {
+            const int i = c.stream_of_slot[s];
+            if (i < 0 || m->cls[i] < 0 || &m->classes[m->cls[i]] != &c || m->slot[i] != (int)s) continue;
+            digests[i] = of_slot[s];
+            if (stream_rc) stream_rc[i] = rc_of_slot[s];
+        }
+    }
+    for (uint32_t i = 0; i < m->n; i++) {
+        const bool has = m->cls[i] >= 0 && m->classes[m->cls[i]].b && m->classes[m->cls[i]].b->ss[m->slot[i]].cur >= 0;
+        if (!has) {
+            missing = true;
+            digests[i] = 0;
+            if (stream_rc) stream_rc[i] = H263MI_ERR_NO_PICTURE;
+        }
+    }
+    return missing && !stream_rc ? H263MI_ERR_NO_PICTURE : H263MI_OK;
+}
+
 int h263mi_mixed_reset_stream(h263mi_mixed *m, uint32_t stream)
 {
     if (!m || stream >= m->n) return H263MI_ERR_INVALID_ARGUMENT;

@@ -245,6 +245,14 @@ int h263mi_copy_yuv(const h263mi_state *s, uint8_t *y, uint8_t *cb, uint8_t *cr)
     return s->b->copy_yuv(0, y, cb, cr);
 }
 
+int h263mi_digest_yuv(const h263mi_state *s, uint32_t seed, uint32_t *digest)
+{
+    if (!s || !digest || !digest_seed_valid(seed)) return H263MI_ERR_INVALID_ARGUMENT;
+    if (!s->has_last || !s->b) return H263MI_ERR_NO_PICTURE;
+    DeviceGuard g(s->cfg.device_id);
+    return digest_rc(s->b->digest_yuv(seed, digest, nullptr));
+}
+
 // `strength` of the rendering calls: 0..12, or H263MI_STRENGTH_FROM_HEADER = what the last picture's own header asks for
 // (QUANT_TO_STRENGTH[quantizer] when USE_DEBLOCKER is set: deblock.rs:5-8, picture.rs:61-64)
 static int state_strength(const h263mi_state *s, uint8_t strength, h263mi_batch::Strengths &st)

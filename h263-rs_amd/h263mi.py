@@ -93,6 +93,9 @@ EXPORTS = [
     "h263mi_yuv_layout_extent", "h263mi_batch_set_yuv_layout", "h263mi_render_yuv",
     # ABI 7, additive: the same planes resized to any W' x H' by area averaging
     "h263mi_yuv_resize_extent", "h263mi_batch_set_yuv_resize", "h263mi_render_yuv_resize",
+    # ABI 7, additive: Adler-32 digests of decoded pictures and output buffers, made on the device
+    "h263mi_adler32_spans_on", "h263mi_batch_adler32_spans", "h263mi_digest_yuv", "h263mi_batch_digest_yuv",
+    "h263mi_mixed_digest_yuv",
 ]
 YUV_I420, YUV_NV12 = 0, 1
 STRENGTH_FROM_HEADER = 0xFF
@@ -263,6 +266,82 @@ def yuv_resize_extent(n_streams, out_width, out_height, format=YUV_I420, pitch_y
     return nb.value
 
 
+class DigestSpan(C.Structure):
+    """h263mi_digest_span: `rows` rows of `row_bytes` bytes, `pitch` bytes apart, `offset` bytes behind the device pointer; the
+    rows continue the byte string of output `digest` (non-decreasing over a table)."""
+    _fields_ = [("offset", C.c_uint64), ("pitch", C.c_uint64), ("row_bytes", C.c_uint32), ("rows", C.c_uint32),
+                ("digest", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+DIGEST_PIECE = 16384      # bytes one wave digests at most (csrc/digest_kernel.inl: DIGEST_PIECE); tests put sizes around it
+
+
+def _span_array(spans):
+    """DigestSpan instances or (offset, pitch, row_bytes, rows, digest) tuples -> (ctypes array or None, count)"""
+    spans = list(spans)
+    arr = (DigestSpan * max(len(spans), 1))()
+    for i, sp in enumerate(spans):
+        arr[i] = sp if isinstance(sp, DigestSpan) else DigestSpan(*sp)
+    return (arr if spans else None), len(spans)
+
+
+def _digest_count(spans, n_digests):
+    if n_digests is not None:
+        return n_digests
+    return max([(sp.digest if isinstance(sp, DigestSpan) else sp[4]) for sp in spans], default=0) + 1
+
+
+def adler32_spans(dev_ptr, buffer_bytes, spans, seed=1, n_digests=None, device_id=0, stream=None):
+    """h263mi_adler32_spans_on: the Adler-32 (zlib.adler32(data, seed)) of the rows the spans name in the device buffer at dev_ptr,
+    one per digest index (n_digests None: as many as the spans use) -> list of ints.  seed 1 is zlib's start value."""
+    spans = list(spans)
+    n_digests = _digest_count(spans, n_digests)
+    arr, n = _span_array(spans)
+    out = (C.c_uint32 * max(n_digests, 1))()
+    cfg = BackendCfg(device_id, 0, stream)
+    _check(lib().h263mi_adler32_spans_on(C.byref(cfg), dev_ptr, buffer_bytes, arr, n, seed, out, n_digests), "adler32_spans")
+    return list(out)[:n_digests]
+
+
+def _back_to_back(n_streams, picture_bytes):
+    return [s * picture_bytes for s in range(n_streams)]
+
+
+def spans_of_rgba(n_streams, out_w, out_h, row_pitch=0, offsets=None):
+    """One digest per stream over its out_w x out_h RGBA picture in a buffer shaped by h263mi_rgba_layout / _resize: rows of
+    4 * out_w bytes, row_pitch apart (0 = tight), stream s at offsets[s] (None: s * out_h * pitch)."""
+    row = 4 * out_w
+    pitch = row_pitch or row
+    offs = _back_to_back(n_streams, out_h * pitch) if offsets is None else offsets
+    return [DigestSpan(int(offs[s]), pitch, row, out_h, s, 0) for s in range(n_streams)]
+
+
+def spans_of_yuv(n_streams, w, h, format=YUV_I420, pitch_y=0, pitch_c=0, offsets_y=None, offsets_cb=None, offsets_cr=None):
+    """One digest per stream over its w x h planes in a buffer shaped by h263mi_yuv_layout / _resize: the Y rows, then the Cb rows,
+    then the Cr rows (NV12: the Y rows, then the interleaved rows).  All offsets None: back to back, as h263mi_yuv_layout_extent."""
+    cw, ch = (w + 1) // 2, (h + 1) // 2
+    row_c = cw if format == YUV_I420 else 2 * cw
+    py, pc = pitch_y or w, pitch_c or row_c
+    planes_c = 2 if format == YUV_I420 else 1
+    if offsets_y is None:
+        picture = h * py + planes_c * ch * pc
+        offsets_y = _back_to_back(n_streams, picture)
+        offsets_cb = [o + h * py for o in offsets_y]
+        offsets_cr = [o + ch * pc for o in offsets_cb]
+    out = []
+    for s in range(n_streams):
+        out.append(DigestSpan(int(offsets_y[s]), py, w, h, s, 0))
+        out.append(DigestSpan(int(offsets_cb[s]), pc, row_c, ch, s, 0))
+        if format == YUV_I420:
+            out.append(DigestSpan(int(offsets_cr[s]), pc, cw, ch, s, 0))
+    return out
+
+
+def spans_of_planes_default(n_streams, w, h):
+    """One digest per stream over the tightly packed Y, Cb, Cr that a batch without a YUV layout writes to d_deblocked"""
+    return spans_of_yuv(n_streams, w, h, YUV_I420)
+
+
 class KernelTimes(C.Structure):
     _fields_ = [("recon_ms", C.c_double), ("recon_launches", C.c_uint32), ("pad0", C.c_uint32),
                 ("post_ms", C.c_double), ("post_launches", C.c_uint32), ("pad1", C.c_uint32),
@@ -405,6 +484,11 @@ def lib():
         L.h263mi_yuv_resize_extent.argtypes = [u32, vp, C.POINTER(C.c_uint64)]
         L.h263mi_batch_set_yuv_resize.argtypes = [vp, vp]
         L.h263mi_render_yuv_resize.argtypes = [vp, u8, vp, vp]
+        L.h263mi_adler32_spans_on.argtypes = [C.POINTER(BackendCfg), vp, C.c_uint64, vp, u32, u32, vp, u32]
+        L.h263mi_batch_adler32_spans.argtypes = [vp, vp, C.c_uint64, vp, u32, u32, vp, u32]
+        L.h263mi_digest_yuv.argtypes = [vp, u32, C.POINTER(u32)]
+        L.h263mi_batch_digest_yuv.argtypes = [vp, u32, vp, vp]
+        L.h263mi_mixed_digest_yuv.argtypes = [vp, u32, vp, vp]
         L.h263mi_default_parser_threads.restype = u32
         L.h263mi_default_parser_threads.argtypes = [u32, C.POINTER(u32)]
         _lib = L
@@ -568,6 +652,12 @@ class H263State:
 
     def has_reference_picture(self):
         return self._view(lib().h263mi_get_reference_picture, "get_reference_picture") is not None
+
+    def digest_yuv(self, seed=1):
+        """h263mi_digest_yuv: zlib.adler32(Y + Cb + Cr of the last picture, seed), made on the device"""
+        d = C.c_uint32(0)
+        _check(lib().h263mi_digest_yuv(self._h, seed, C.byref(d)), "digest_yuv")
+        return d.value
 
     def render_rgba(self, strength=0):
         v = self._view(lib().h263mi_get_last_picture, "get_last_picture")
@@ -927,6 +1017,24 @@ class Batch:
         _check(lib().h263mi_batch_copy_yuv(self._h, stream, _p(y), _p(cb), _p(cr)), "batch_copy_yuv")
         return y, cb, cr
 
+    def digest_yuv(self, seed=1, stream_rc=True):
+        """h263mi_batch_digest_yuv -> (digests, rcs): per stream zlib.adler32(Y + Cb + Cr of its last picture, seed) and 0, or 0 and
+        ERR_NO_PICTURE.  stream_rc=None: no per-stream codes -- a stream without a picture raises ERR_NO_PICTURE; -> digests"""
+        out = (C.c_uint32 * self.n)()
+        rcs = (C.c_int * self.n)() if stream_rc is not None else None
+        _check(lib().h263mi_batch_digest_yuv(self._h, seed, out, rcs), "batch_digest_yuv")
+        return (list(out), list(rcs)) if rcs is not None else list(out)
+
+    def adler32_spans(self, dev_ptr, buffer_bytes, spans, seed=1, n_digests=None):
+        """h263mi_batch_adler32_spans: sync, then adler32_spans on the batch's device and stream -- for what the batch has written
+        into d_rgba or d_deblocked (spans_of_rgba, spans_of_yuv, spans_of_planes_default)"""
+        spans = list(spans)
+        n_digests = _digest_count(spans, n_digests)
+        arr, n = _span_array(spans)
+        out = (C.c_uint32 * max(n_digests, 1))()
+        _check(lib().h263mi_batch_adler32_spans(self._h, dev_ptr, buffer_bytes, arr, n, seed, out, n_digests), "batch_adler32_spans")
+        return list(out)[:n_digests]
+
     def timing_begin(self):
         _check(lib().h263mi_batch_timing_begin(self._h), "timing_begin")
 
@@ -1030,8 +1138,18 @@ class MixedBatch:
         _check(lib().h263mi_mixed_copy_yuv(self._h, stream, _p(y), _p(cb), _p(cr)), "mixed_copy_yuv")
         return y, cb, cr
 
+    def digest_yuv(self, seed=1, stream_rc=True):
+        """h263mi_mixed_digest_yuv -> (digests, rcs) as Batch.digest_yuv, one launch pair per size class"""
+        out = (C.c_uint32 * self.n)()
+        rcs = (C.c_int * self.n)() if stream_rc is not None else None
+        _check(lib().h263mi_mixed_digest_yuv(self._h, seed, out, rcs), "mixed_digest_yuv")
+        return (list(out), list(rcs)) if rcs is not None else list(out)
+
     def reset_stream(self, stream):
         _check(lib().h263mi_mixed_reset_stream(self._h, stream), "mixed_reset_stream")
+
+
+MixedSet = MixedBatch
 
 
 def probe_bandwidth(mode, nbytes=1 << 30, reps=10, device_id=0, stream=None, with_shape=False):

@@ -186,6 +186,17 @@ public:
     // renderer reuses for every picture instead of the fresh Vec<u8> of bt601.rs:128; `rgba` holds width * height * 4 bytes
     void render_rgba_into_pinned(uint8_t strength, uint8_t *rgba) const { check(h263mi_render_rgba_pinned(s_, strength, rgba)); }
 
+    // zlib's adler32(Y + Cb + Cr of the last picture, seed), made on the device: 4 bytes cross the link instead of the planes.
+    // nullopt before the first picture, like get_last_picture()
+    std::optional<uint32_t> digest_yuv(uint32_t seed = 1) const
+    {
+        uint32_t d = 0;
+        const int rc = h263mi_digest_yuv(s_, seed, &d);
+        if (rc == H263MI_ERR_NO_PICTURE) return std::nullopt;
+        check(rc);
+        return d;
+    }
+
     h263mi_state *raw() { return s_; }
 
 private:
@@ -352,12 +363,34 @@ public:
     // every stream rendered as W' x H' (offsets NULL); nullptr = full size again
     void set_rgba_resize(const h263mi_rgba_resize *r) { check(h263mi_mixed_set_rgba_resize(m_, r)); }
     uint64_t frame_store_bytes() const { return h263mi_mixed_frame_store_bytes(m_); }
+    // per stream zlib's adler32(Y + Cb + Cr of its last picture, seed), nullopt for a stream without a picture; one launch pair
+    // per picture size
+    std::vector<std::optional<uint32_t>> digest_yuv(uint32_t seed = 1)
+    {
+        std::vector<uint32_t> d(n_);
+        std::vector<int> rc(n_);
+        check(h263mi_mixed_digest_yuv(m_, seed, d.data(), rc.data()));
+        std::vector<std::optional<uint32_t>> out(n_);
+        for (uint32_t i = 0; i < n_; i++)
+            if (rc[i] == H263MI_OK) out[i] = d[i];
+        return out;
+    }
     h263mi_mixed *raw() { return m_; }
 
 private:
     h263mi_mixed *m_ = nullptr;
     uint32_t n_ = 0, options_ = 0;
 };
+
+// zlib's adler32 of the rows the spans name in device memory, one per digest index (h263mi_adler32_spans_on); seed 1 is zlib's
+// start value
+inline std::vector<uint32_t> adler32_spans(const uint8_t *d_base, uint64_t buffer_bytes, const std::vector<h263mi_digest_span> &spans,
+                                           uint32_t n_digests, uint32_t seed = 1, const h263mi_backend_cfg *cfg = nullptr)
+{
+    std::vector<uint32_t> out(n_digests);
+    check(h263mi_adler32_spans_on(cfg, d_base, buffer_bytes, spans.data(), (uint32_t)spans.size(), seed, out.data(), n_digests));
+    return out;
+}
 
 }  // namespace h263
 

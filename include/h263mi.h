@@ -724,6 +724,53 @@ int h263mi_mixed_reset_stream(h263mi_mixed *m, uint32_t stream);
  * timed region. */
 int h263mi_batch_timing_reserve(h263mi_batch *b, uint32_t n_launches);
 
+/*
+ * ADLER-32 DIGESTS MADE ON THE DEVICE (additive, ABI 7): whether two pictures or two output buffers are equal, for 4 bytes per
+ * stream across the link instead of every byte.  The digest is Adler-32 (RFC 1950), the function of zlib's adler32(data, value):
+ * with N the string's length, a0 = seed & 0xffff, b0 = seed >> 16, M = 65521 and d_i its bytes, i from 0,
+ *     A = (a0 + sum d_i) mod M,   B = (b0 + N * a0 + sum (N - i) * d_i) mod M,   digest = B << 16 | A.
+ * seed 1 is zlib's start value (adler32(0, NULL, 0)); tools that start from 0 pass 0; a digest continues an earlier one when the
+ * earlier one is the seed.  Both halves of the seed must be below 65521.
+ *
+ * A SPAN is `rows` rows of `row_bytes` bytes, `pitch` bytes apart, `offset` bytes behind a device pointer.  Digest k is the
+ * Adler-32 of ONE byte string: the rows of every span with digest == k, in table order, row after row.  Bytes between rows never
+ * enter.  Spans may overlap (they are only read).  All spans and digests of a call go through one pair of kernel launches.
+ */
+typedef struct h263mi_digest_span {
+    uint64_t offset;      /* bytes from d_base to the first row */
+    uint64_t pitch;       /* bytes from a row to the next; >= row_bytes when rows > 1 */
+    uint32_t row_bytes, rows;   /* either may be 0: the span adds nothing */
+    uint32_t digest;      /* output this span continues; non-decreasing over the table */
+    uint32_t reserved;    /* 0 */
+} h263mi_digest_span;     /* 32 bytes */
+
+/* spans and digests are HOST pointers, d_base is a DEVICE pointer to buffer_bytes bytes.  Runs on cfg's device and stream (NULL:
+ * device 0, the null stream) and returns when the n_digests digests are in `digests`; a digest without spans is `seed`.
+ * H263MI_ERR_INVALID_ARGUMENT, decided on the host before any device call: digests NULL or n_digests 0; spans NULL with
+ * n_spans > 0; n_spans > 65536; a reserved word set; a digest index >= n_digests or below the one of the span before; rows > 1
+ * with pitch < row_bytes; a span with bytes that ends behind the buffer (offset + (rows-1) * pitch + row_bytes > buffer_bytes,
+ * computed without wrapping); d_base NULL while a span has bytes; a digest that covers 2^32 bytes or more; a half of seed
+ * >= 65521.  Any failure of the HIP runtime, an allocation included, is H263MI_ERR_HIP; the same call then succeeds. */
+int h263mi_adler32_spans_on(const h263mi_backend_cfg *cfg, const uint8_t *d_base, uint64_t buffer_bytes,
+                            const h263mi_digest_span *spans, uint32_t n_spans, uint32_t seed,
+                            uint32_t *digests, uint32_t n_digests);
+/* h263mi_batch_sync(b) -- which delivers a deferred rendering of H263MI_CFG_PIPELINE_POST and waits for the second stream of
+ * H263MI_CFG_OVERLAP_POST --, then the call above on the batch's device and stream: the way to digest what the batch has written
+ * into d_rgba or d_deblocked in any of the output shapes.  An error of the sync is returned and nothing is digested. */
+int h263mi_batch_adler32_spans(h263mi_batch *b, const uint8_t *d_base, uint64_t buffer_bytes,
+                               const h263mi_digest_span *spans, uint32_t n_spans, uint32_t seed,
+                               uint32_t *digests, uint32_t n_digests);
+/* The Adler-32 of Y || Cb || Cr of a stream's last decoded picture, exact size, tightly packed: the digest of the bytes that
+ * h263mi_copy_yuv / h263mi_batch_copy_yuv / h263mi_mixed_copy_yuv would deliver at that moment (the reference planes, not the
+ * deblocked ones), read in place from the frame store.  Ordered behind the decodes already queued; returns when the digests are
+ * on the host.  A stream without a picture: digests[s] = 0 and stream_rc[s] = H263MI_ERR_NO_PICTURE (else 0); with stream_rc
+ * NULL the call returns H263MI_ERR_NO_PICTURE after writing the other streams' digests.  All streams of a batch go through one
+ * pair of launches, a mixed set takes one pair per size class that has pictures.  An open timing bracket is closed first, as by
+ * h263mi_batch_copy_yuv.  A failure of the HIP runtime is H263MI_ERR_HIP and leaves state and pictures untouched. */
+int h263mi_digest_yuv(const h263mi_state *s, uint32_t seed, uint32_t *digest);
+int h263mi_batch_digest_yuv(h263mi_batch *b, uint32_t seed, uint32_t *digests, int *stream_rc);
+int h263mi_mixed_digest_yuv(h263mi_mixed *m, uint32_t seed, uint32_t *digests, int *stream_rc);
+
 /* ======================================================================= */
 /* Device memory + synthetic macroblock records (bench / test support)      */
 /* ======================================================================= */
