@@ -45,32 +45,12 @@ int h263mi_batch::alloc(uint32_t n_streams, uint32_t w, uint32_t h)
     return H263MI_OK;
 }
 
-bool h263mi_batch::layout_ptrs(uint8_t *d_rgba, std::vector<uint8_t *> &ptrs) const
+bool h263mi_batch::layout_ptrs(const RgbaLayout &lay, uint8_t *d_rgba, std::vector<uint8_t *> &ptrs) const
 {
-    if (!layout.placed() || !d_rgba) return false;
+    if (!lay.placed() || !d_rgba) return false;
     ptrs.resize(n);
-    for (uint32_t i = 0; i < n; i++) ptrs[i] = d_rgba + layout.offsets[i];
+    for (uint32_t i = 0; i < n; i++) ptrs[i] = d_rgba + lay.offsets[i];
     return true;
-}
-
-h263mi_yuv_offsets::~h263mi_yuv_offsets()
-{
-    DeviceGuard g(device);
-    if (d) (void)hipFree(d);
-}
-
-h263mi_resize_scratch::~h263mi_resize_scratch()
-{
-    DeviceGuard g(device);
-    if (rgba) (void)hipFree(rgba);
-    if (spans) (void)hipFree(spans);
-}
-
-h263mi_plane_scratch::~h263mi_plane_scratch()
-{
-    DeviceGuard g(device);
-    if (planes) (void)hipFree(planes);
-    if (spans) (void)hipFree(spans);
 }
 
 int h263mi_batch::plane_resize_dst(const YuvLayout::Resize &rz, const std::vector<int8_t> &sets, uint8_t *d_planes, hipStream_t on,
@@ -95,11 +75,11 @@ int h263mi_batch::launch_plane_resize(const YuvLayout::Resize &rz, const std::ve
     for (int8_t v : sets) any = any || v >= 0;
     if (!any) return H263MI_OK;
     PlaneResizeArgs a{};
-    a.src = rz.scratch->planes;
+    a.src = rz.scratch->pixels.as<uint8_t>();
     a.dst = d_dst;
     a.w = L.width, a.h = L.height, a.cw = L.cwidth, a.ch = L.cheight;
     a.ow = rz.ow, a.oh = rz.oh, a.cow = (rz.ow + 1) / 2, a.coh = (rz.oh + 1) / 2;
-    a.cols_y = rz.scratch->spans;
+    a.cols_y = rz.scratch->spans.as<ResizeSpan>();
     a.rows_y = a.cols_y + a.ow;
     a.cols_c = a.rows_y + a.oh;
     a.rows_c = a.cols_c + a.cow;
@@ -118,12 +98,12 @@ int h263mi_batch::launch_plane_resize(const YuvLayout::Resize &rz, const std::ve
     return H263MI_OK;
 }
 
-int h263mi_batch::resize_dst(const std::vector<int8_t> &sets, uint8_t *d_rgba, uint8_t *const *host_ptrs, hipStream_t on,
-                             uint8_t *const **d_out)
+int h263mi_batch::resize_dst(const RgbaLayout &lay, const std::vector<int8_t> &sets, uint8_t *d_rgba, uint8_t *const *host_ptrs,
+                             hipStream_t on, uint8_t *const **d_out)
 {
     std::vector<uint8_t *> p(n, nullptr);
     for (uint32_t i = 0; i < n; i++)
-        if (sets[i] >= 0) p[i] = host_ptrs ? host_ptrs[i] : d_rgba + layout.offsets[i];
+        if (sets[i] >= 0) p[i] = host_ptrs ? host_ptrs[i] : d_rgba + lay.offsets[i];
     return upload(ptr_ring, p.data(), d_out, on);
 }
 
@@ -133,10 +113,10 @@ int h263mi_batch::launch_resize(const RgbaLayout::Resize &rz, const std::vector<
     for (int8_t v : sets) any = any || v >= 0;
     if (!any) return H263MI_OK;
     ResizeArgs a{};
-    a.src = rz.scratch->rgba;
+    a.src = rz.scratch->pixels.as<uint8_t>();
     a.dst = d_dst;
-    a.cols = rz.scratch->spans;
-    a.rows = rz.scratch->spans + rz.ow;
+    a.cols = rz.scratch->spans.as<ResizeSpan>();
+    a.rows = a.cols + rz.ow;
     a.w = L.width;
     a.h = L.height;
     a.ow = rz.ow;
@@ -453,7 +433,7 @@ int h263mi_batch::note_pending(const Strengths &strength, uint8_t *d_rgba, uint8
     auto note_planes = [&]() -> int {
         if (!pending.yuv.resize.on()) return H263MI_OK;
         RC_TRY(plane_resize_dst(pending.yuv.resize, pending.set, d_planes, stream, &pending.plane_dst, &pending.plane_wide));
-        pending.planes = pending.yuv.resize.scratch->planes;
+        pending.planes = pending.yuv.resize.scratch->pixels.as<uint8_t>();
         return H263MI_OK;
     };
     if (layout.resize.on() && (d_rgba || host_ptrs)) {
@@ -461,19 +441,19 @@ int h263mi_batch::note_pending(const Strengths &strength, uint8_t *d_rgba, uint8
         // resize -- scratch, size, destinations -- is captured here, at the request)
         for (uint32_t i = 0; i < n; i++)
             pending.set[i] = (ss[i].active && (!host_ptrs || host_ptrs[i])) ? ss[i].cur : (int8_t)-1;
-        RC_TRY(resize_dst(pending.set, d_rgba, host_ptrs, stream, &pending.resize_dst));
+        RC_TRY(resize_dst(layout, pending.set, d_rgba, host_ptrs, stream, &pending.resize_dst));
         pending.planes = d_planes;
         RC_TRY(note_planes());
         pending.resize = layout.resize;
         pending.out = OutLayout();
         pending.valid = true;
         pending.strength = strength;
-        pending.rgba = layout.resize.scratch->rgba;
+        pending.rgba = layout.resize.scratch->pixels.as<uint8_t>();
         return H263MI_OK;
     }
     // (an output layout places each stream's picture through a per-stream pointer; the layout is captured here, at the request)
     std::vector<uint8_t *> placed;
-    if (!host_ptrs && layout_ptrs(d_rgba, placed)) host_ptrs = placed.data();
+    if (!host_ptrs && layout_ptrs(layout, d_rgba, placed)) host_ptrs = placed.data();
     pending.out = layout.kernel;
     if (host_ptrs) RC_TRY(upload(ptr_ring, host_ptrs, &pending.rgba_ptrs, stream));
     for (uint32_t i = 0; i < n; i++)
@@ -499,14 +479,17 @@ int h263mi_batch::flush_pending()
     return yrz.on() && pending.plane_dst ? launch_plane_resize(yrz, pending.set, pending.plane_dst, pending.plane_wide, stream) : H263MI_OK;
 }
 
-int h263mi_batch::render(const Strengths &strength, uint8_t *d_rgba, uint8_t *d_planes, bool only_active, uint8_t *const *host_ptrs)
+int h263mi_batch::render(const Strengths &strength, uint8_t *d_rgba, uint8_t *d_planes, bool only_active, uint8_t *const *host_ptrs,
+                         const RgbaLayout *rgba_shape, const YuvLayout *yuv_shape)
 {
     if (!any_picture()) return H263MI_ERR_NO_PICTURE;
     RC_TRY(flush_pending());
-    const RgbaLayout::Resize &rz = layout.resize;
+    const RgbaLayout &lay = rgba_shape ? *rgba_shape : layout;
+    const YuvLayout &yl = yuv_shape ? *yuv_shape : yuv;
+    const RgbaLayout::Resize &rz = lay.resize;
     const bool resized = rz.on() && (d_rgba || host_ptrs);
     std::vector<uint8_t *> placed;
-    if (!resized && !host_ptrs && layout_ptrs(d_rgba, placed)) host_ptrs = placed.data();
+    if (!resized && !host_ptrs && layout_ptrs(lay, d_rgba, placed)) host_ptrs = placed.data();
     std::vector<int8_t> sets(n);
     bool reads[2] = {false, false};
     for (uint32_t i = 0; i < n; i++) {
@@ -516,23 +499,23 @@ int h263mi_batch::render(const Strengths &strength, uint8_t *d_rgba, uint8_t *d_
     if (overlap_post) HIP_TRY(hipStreamWaitEvent(post_stream, ev_recon_done, 0));
     uint8_t *const *d_out_ptrs = nullptr;
     // a YUV resize: the full-size planes into its scratch (the default kernels), k_plane_resize behind the rendering
-    const bool planes_resized = yuv.resize.on() && d_planes;
+    const bool planes_resized = yl.resize.on() && d_planes;
     const PlaneDst *d_plane_dst = nullptr;
     bool plane_wide = false;
     if (planes_resized) {
-        RC_TRY(plane_resize_dst(yuv.resize, sets, d_planes, stream_of(1), &d_plane_dst, &plane_wide));
-        d_planes = yuv.resize.scratch->planes;
+        RC_TRY(plane_resize_dst(yl.resize, sets, d_planes, stream_of(1), &d_plane_dst, &plane_wide));
+        d_planes = yl.resize.scratch->pixels.as<uint8_t>();
     }
     if (resized) {
         // full size into the scratch (the default kernels), then k_rgba_resize right behind it on the same stream
-        RC_TRY(resize_dst(sets, d_rgba, host_ptrs, stream_of(1), &d_out_ptrs));
-        RC_TRY(launch_post_sets(sets, strength, rz.scratch->rgba, d_planes, stream_of(1), nullptr, OutLayout(), &yuv));
+        RC_TRY(resize_dst(lay, sets, d_rgba, host_ptrs, stream_of(1), &d_out_ptrs));
+        RC_TRY(launch_post_sets(sets, strength, rz.scratch->pixels.as<uint8_t>(), d_planes, stream_of(1), nullptr, OutLayout(), &yl));
         RC_TRY(launch_resize(rz, sets, d_out_ptrs, stream_of(1)));
     } else {
         if (host_ptrs) RC_TRY(upload(ptr_ring, host_ptrs, &d_out_ptrs, stream_of(1)));
-        RC_TRY(launch_post_sets(sets, strength, d_rgba, d_planes, stream_of(1), d_out_ptrs, layout.kernel, &yuv));
+        RC_TRY(launch_post_sets(sets, strength, d_rgba, d_planes, stream_of(1), d_out_ptrs, lay.kernel, &yl));
     }
-    if (planes_resized) RC_TRY(launch_plane_resize(yuv.resize, sets, d_plane_dst, plane_wide, stream_of(1)));
+    if (planes_resized) RC_TRY(launch_plane_resize(yl.resize, sets, d_plane_dst, plane_wide, stream_of(1)));
     // a later reconstruction may overwrite a frame set only when every post-processing that reads it is done: streams
     // that have drifted apart read both sets
     if (overlap_post)
@@ -817,322 +800,6 @@ static int bound_output_buffers(const h263mi_batch *b, const uint8_t *d_rgba, co
     return H263MI_OK;
 }
 
-int rgba_layout_extent(uint32_t n_streams, uint32_t w, uint32_t h, const h263mi_rgba_layout *lay, uint32_t *out_w, uint32_t *out_h,
-                       uint64_t *bytes, h263mi_batch::OutLayout *out_kernel)
-{
-    if (!n_streams || !w || !h) return H263MI_ERR_INVALID_ARGUMENT;
-    const uint32_t scale = lay ? lay->scale_log2 : 0u;
-    if (scale > 2) return H263MI_ERR_INVALID_ARGUMENT;
-    if (lay)
-        for (uint8_t r : lay->reserved)
-            if (r) return H263MI_ERR_INVALID_ARGUMENT;
-    const uint32_t ow = (w + (1u << scale) - 1) >> scale, oh = (h + (1u << scale) - 1) >> scale;
-    const uint64_t row = 4ull * ow, pitch = (lay && lay->row_pitch) ? lay->row_pitch : row;
-    if (pitch < row || pitch % 4) return H263MI_ERR_INVALID_ARGUMENT;
-    const uint64_t span = (uint64_t)(oh - 1) * pitch + row;              // bytes from a picture's first byte to behind its last
-    if (oh > 1 && pitch >= (1ull << 32)) return H263MI_ERR_INVALID_ARGUMENT;
-    if (span >= (1ull << 32)) return H263MI_ERR_INVALID_ARGUMENT;         // lane offsets are 32-bit
-    uint64_t total = 0;
-    const uint64_t *off = lay ? lay->offsets : nullptr;
-    if (!off) {
-        const unsigned __int128 t = (unsigned __int128)(n_streams - 1) * oh * pitch + span;
-        if (t > UINT64_MAX) return H263MI_ERR_INVALID_ARGUMENT;
-        total = (uint64_t)t;
-    } else {
-        // every picture on its own rows and byte columns: rows [o / pitch, + H'), columns [o % pitch, + 4W')
-        struct Rect { uint64_t r0, c0; };
-        std::vector<Rect> rs(n_streams);
-        for (uint32_t i = 0; i < n_streams; i++) {
-            const uint64_t o = off[i];
-            if (o % 4 || o % pitch + row > pitch || o > UINT64_MAX - span) return H263MI_ERR_INVALID_ARGUMENT;
-            total = std::max(total, o + span);
-            rs[i] = {o / pitch, o % pitch};
-        }
-        std::sort(rs.begin(), rs.end(), [](const Rect &x, const Rect &y) { return x.r0 < y.r0 || (x.r0 == y.r0 && x.c0 < y.c0); });
-        for (uint32_t i = 0; i < n_streams; i++)
-            for (uint32_t j = i + 1; j < n_streams && rs[j].r0 < rs[i].r0 + oh; j++)      // (sorted by first row: later ones start lower)
-                if (rs[j].c0 < rs[i].c0 + row && rs[i].c0 < rs[j].c0 + row) return H263MI_ERR_INVALID_ARGUMENT;
-    }
-    if (out_w) *out_w = ow;
-    if (out_h) *out_h = oh;
-    if (bytes) *bytes = total;
-    if (out_kernel) {
-        // the default layout (full size, tight rows, pictures back to back) keeps the default kernels
-        const bool dflt = scale == 0 && pitch == row && !off;
-        out_kernel->scale = dflt ? 0u : scale;
-        out_kernel->pitch = dflt ? 0u : (uint32_t)(oh > 1 ? pitch : row);     // (one row: the pitch is never used)
-    }
-    return H263MI_OK;
-}
-
-// h263mi_yuv_layout_extent (include/h263mi.h has the rules)
-int yuv_layout_extent(uint32_t n_streams, uint32_t w, uint32_t h, const h263mi_yuv_layout *lay, uint64_t *bytes,
-                      h263mi_batch::YuvLayout *shape, std::vector<uint64_t> *offsets_out)
-{
-    if (!n_streams || !w || !h || w > 65535 || h > 65535) return H263MI_ERR_INVALID_ARGUMENT;
-    const uint32_t fmt = lay ? lay->format : (uint32_t)H263MI_YUV_I420;
-    if (fmt != H263MI_YUV_I420 && fmt != H263MI_YUV_NV12) return H263MI_ERR_INVALID_ARGUMENT;
-    if (lay)
-        for (uint8_t r : lay->reserved)
-            if (r) return H263MI_ERR_INVALID_ARGUMENT;
-    const bool nv12 = fmt == H263MI_YUV_NV12;
-    const uint64_t cw = (w + 1) / 2, ch = (h + 1) / 2;
-    const uint64_t row_y = w, row_c = nv12 ? 2 * cw : cw;
-    const uint64_t pitch_y = (lay && lay->pitch_y) ? lay->pitch_y : row_y, pitch_c = (lay && lay->pitch_c) ? lay->pitch_c : row_c;
-    if (pitch_y < row_y || pitch_c < row_c) return H263MI_ERR_INVALID_ARGUMENT;
-    // bytes from a plane's first byte to behind its last: lane offsets are 32-bit
-    if ((h > 1 && pitch_y >= (1ull << 32)) || (ch > 1 && pitch_c >= (1ull << 32))) return H263MI_ERR_INVALID_ARGUMENT;
-    const uint64_t span_y = (uint64_t)(h - 1) * pitch_y + row_y, span_c = (ch - 1) * pitch_c + row_c;
-    if (span_y >= (1ull << 32) || span_c >= (1ull << 32)) return H263MI_ERR_INVALID_ARGUMENT;
-    const uint64_t *oy = lay ? lay->offsets_y : nullptr, *ocb = lay ? lay->offsets_cb : nullptr, *ocr = lay ? lay->offsets_cr : nullptr;
-    if (nv12 && ocr) return H263MI_ERR_INVALID_ARGUMENT;
-    const int given = (oy ? 1 : 0) + (ocb ? 1 : 0) + (ocr ? 1 : 0), all = nv12 ? 2 : 3;
-    if (given != 0 && given != all) return H263MI_ERR_INVALID_ARGUMENT;
-    const uint32_t chroma_planes = nv12 ? 1u : 2u;
-    std::vector<uint64_t> offs((size_t)3 * n_streams);
-    uint64_t total = 0;
-    if (!given) {
-        // planes back to back, pictures back to back: P bytes each
-        const unsigned __int128 P = (unsigned __int128)h * pitch_y + (unsigned __int128)chroma_planes * ch * pitch_c;
-        if (P * n_streams > UINT64_MAX) return H263MI_ERR_INVALID_ARGUMENT;
-        for (uint32_t i = 0; i < n_streams; i++) {
-            const uint64_t base = (uint64_t)P * i;
-            offs[3 * i + 0] = base;
-            offs[3 * i + 1] = base + h * pitch_y;
-            offs[3 * i + 2] = nv12 ? offs[3 * i + 1] : base + h * pitch_y + ch * pitch_c;
-        }
-        total = (uint64_t)(P * n_streams);
-    } else {
-        // every plane a rectangle on the grid of its pitch: rows [o / pitch, + rows), byte columns [o % pitch, + row)
-        struct Rect { uint64_t r0, c0, rows, cols; };
-        struct Span { uint64_t lo, hi; bool chroma; };
-        std::vector<Rect> ry, rc;
-        std::vector<Span> spans;
-        for (uint32_t i = 0; i < n_streams; i++) {
-            const uint64_t o[3] = {oy[i], ocb[i], nv12 ? ocb[i] : ocr[i]};
-            for (uint32_t k = 0; k < 1 + chroma_planes; k++) {
-                const uint64_t pitch = k ? pitch_c : pitch_y, row = k ? row_c : row_y, rows = k ? ch : h, span = k ? span_c : span_y;
-                if (o[k] % pitch + row > pitch || o[k] > UINT64_MAX - span) return H263MI_ERR_INVALID_ARGUMENT;
-                total = std::max(total, o[k] + span);
-                (k ? rc : ry).push_back(Rect{o[k] / pitch, o[k] % pitch, rows, row});
-                spans.push_back(Span{o[k], o[k] + span, k != 0});
-            }
-            for (int k = 0; k < 3; k++) offs[3 * i + k] = o[k];
-        }
-        auto intersect = [](std::vector<Rect> &rs) {
-            std::sort(rs.begin(), rs.end(), [](const Rect &x, const Rect &y) { return x.r0 < y.r0 || (x.r0 == y.r0 && x.c0 < y.c0); });
-            for (size_t i = 0; i < rs.size(); i++)
-                for (size_t j = i + 1; j < rs.size() && rs[j].r0 < rs[i].r0 + rs[i].rows; j++)      // (sorted by first row: later ones start lower)
-                    if (rs[j].c0 < rs[i].c0 + rs[i].cols && rs[i].c0 < rs[j].c0 + rs[j].cols) return true;
-            return false;
-        };
-        if (pitch_y == pitch_c) {
-            // one grid for all planes: the rectangle test decides between luma and chroma too
-            ry.insert(ry.end(), rc.begin(), rc.end());
-            if (intersect(ry)) return H263MI_ERR_INVALID_ARGUMENT;
-        } else {
-            if (intersect(ry) || intersect(rc)) return H263MI_ERR_INVALID_ARGUMENT;
-            // across the two grids: no luma plane's byte span may meet a chroma plane's
-            std::sort(spans.begin(), spans.end(), [](const Span &x, const Span &y) { return x.lo < y.lo; });
-            uint64_t end_luma = 0, end_chroma = 0;
-            for (const Span &sp : spans) {
-                if (sp.lo < (sp.chroma ? end_luma : end_chroma)) return H263MI_ERR_INVALID_ARGUMENT;
-                uint64_t &e = sp.chroma ? end_chroma : end_luma;
-                e = std::max(e, sp.hi);
-            }
-        }
-    }
-    if (bytes) *bytes = total;
-    if (shape) {
-        shape->format = nv12 ? YUV_OUT_NV12 : YUV_OUT_I420;
-        shape->pitch_y = (uint32_t)(h > 1 ? pitch_y : row_y);      // (one row: the pitch is never used)
-        shape->pitch_c = (uint32_t)(ch > 1 ? pitch_c : row_c);
-        shape->bytes = total;
-        bool wide = shape->pitch_y % 4 == 0 && shape->pitch_c % 4 == 0;
-        for (uint64_t o : offs) wide = wide && o % 4 == 0;
-        shape->wide = wide;
-    }
-    if (offsets_out) *offsets_out = std::move(offs);
-    return H263MI_OK;
-}
-
-int make_yuv_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_yuv_layout *lay, h263mi_batch::YuvLayout &out)
-{
-    h263mi_batch::YuvLayout shape;
-    if (!lay) {
-        out = std::move(shape);
-        return H263MI_OK;
-    }
-    std::vector<uint64_t> offs;
-    RC_TRY(yuv_layout_extent(n, w, h, lay, nullptr, &shape, &offs));
-    DeviceGuard g(device);
-    if (!g.ok) return H263MI_ERR_NO_DEVICE;
-    std::shared_ptr<h263mi_yuv_offsets> d(new (std::nothrow) h263mi_yuv_offsets());
-    if (!d) return H263MI_ERR_OUT_OF_MEMORY;
-    d->device = device;
-    HIP_TRY(hipMalloc((void **)&d->d, offs.size() * sizeof(uint64_t)));
-    HIP_TRY(hipMemcpy(d->d, offs.data(), offs.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
-    shape.offsets = std::move(d);
-    out = std::move(shape);
-    return H263MI_OK;
-}
-
-int yuv_resize_extent(uint32_t n_streams, const h263mi_yuv_resize *r, uint64_t *bytes, h263mi_batch::YuvLayout *shape,
-                      std::vector<uint64_t> *offsets)
-{
-    if (!r || !r->out_width || !r->out_height) return H263MI_ERR_INVALID_ARGUMENT;
-    for (uint8_t v : r->reserved)
-        if (v) return H263MI_ERR_INVALID_ARGUMENT;
-    // the rules of a layout: a layout of a W' x H' picture has exactly the resize's shape
-    h263mi_yuv_layout lay{};
-    lay.format = r->format;
-    lay.pitch_y = r->pitch_y;
-    lay.pitch_c = r->pitch_c;
-    lay.offsets_y = r->offsets_y;
-    lay.offsets_cb = r->offsets_cb;
-    lay.offsets_cr = r->offsets_cr;
-    return yuv_layout_extent(n_streams, r->out_width, r->out_height, &lay, bytes, shape, offsets);
-}
-
-int make_yuv_resize_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_yuv_resize *r, h263mi_batch::YuvLayout &out)
-{
-    if (!r) {
-        out = h263mi_batch::YuvLayout();
-        return H263MI_OK;
-    }
-    h263mi_batch::YuvLayout placed;
-    std::vector<uint64_t> offs;
-    RC_TRY(yuv_resize_extent(n, r, nullptr, &placed, &offs));
-    const uint32_t ow = r->out_width, oh = r->out_height;
-    if (ow == w && oh == h) {                   // identical by definition: the YUV instantiations, no scratch, no extra pass
-        h263mi_yuv_layout lay{};
-        lay.format = r->format;
-        lay.pitch_y = r->pitch_y;
-        lay.pitch_c = r->pitch_c;
-        lay.offsets_y = r->offsets_y;
-        lay.offsets_cb = r->offsets_cb;
-        lay.offsets_cr = r->offsets_cr;
-        return make_yuv_shape(device, n, w, h, &lay, out);
-    }
-    const uint32_t cw = (w + 1) / 2, ch = (h + 1) / 2, cow = (ow + 1) / 2, coh = (oh + 1) / 2;
-    std::vector<ResizeSpan> spans((size_t)ow + oh + cow + coh);
-    resize_spans(w, ow, spans.data());
-    resize_spans(h, oh, spans.data() + ow);
-    resize_spans(cw, cow, spans.data() + ow + oh);
-    resize_spans(ch, coh, spans.data() + ow + oh + cow);
-    DeviceGuard g(device);
-    if (!g.ok) return H263MI_ERR_NO_DEVICE;
-    std::shared_ptr<h263mi_plane_scratch> sc(new (std::nothrow) h263mi_plane_scratch());
-    if (!sc) return H263MI_ERR_OUT_OF_MEMORY;
-    sc->device = device;
-    const size_t plane_bytes = (size_t)n * ((size_t)w * h + 2 * (size_t)cw * ch), span_bytes = spans.size() * sizeof(ResizeSpan);
-    HIP_TRY(hipMalloc((void **)&sc->planes, plane_bytes));
-    HIP_TRY(hipMalloc((void **)&sc->spans, span_bytes));
-    HIP_TRY(hipMemcpy(sc->spans, spans.data(), span_bytes, hipMemcpyHostToDevice));
-    sc->bytes = plane_bytes + span_bytes;
-    h263mi_batch::YuvLayout shape;              // (format 0: the rendering kernels write their default planes, into the scratch)
-    shape.bytes = placed.bytes;
-    shape.resize.scratch = std::move(sc);
-    shape.resize.format = placed.format;
-    shape.resize.ow = ow;
-    shape.resize.oh = oh;
-    shape.resize.pitch_y = placed.pitch_y;
-    shape.resize.pitch_c = placed.pitch_c;
-    shape.resize.wide = placed.wide;
-    shape.resize.offsets = std::move(offs);
-    out = std::move(shape);
-    return H263MI_OK;
-}
-
-int rgba_resize_extent(uint32_t n_streams, const h263mi_rgba_resize *r, uint64_t *bytes)
-{
-    if (!r || !r->out_width || !r->out_height) return H263MI_ERR_INVALID_ARGUMENT;
-    for (uint8_t v : r->reserved)
-        if (v) return H263MI_ERR_INVALID_ARGUMENT;
-    // the rules of a layout: a full-size layout of a W' x H' picture has exactly the resize's shape
-    h263mi_rgba_layout lay{};
-    lay.row_pitch = r->row_pitch;
-    lay.offsets = r->offsets;
-    return rgba_layout_extent(n_streams, r->out_width, r->out_height, &lay, nullptr, nullptr, bytes);
-}
-
-bool resize_as_layout(uint32_t w, uint32_t h, const h263mi_rgba_resize &r, h263mi_rgba_layout *lay)
-{
-    int scale = -1;
-    for (int f = 0; f <= 2 && scale < 0; f++) {
-        const uint32_t m = (1u << f) - 1;
-        if (!(w & m) && !(h & m) && r.out_width == (w >> f) && r.out_height == (h >> f)) scale = f;
-    }
-    if (scale < 0) return false;
-    *lay = h263mi_rgba_layout{};
-    lay->scale_log2 = (uint8_t)scale;
-    lay->row_pitch = r.row_pitch;
-    lay->offsets = r.offsets;
-    return true;
-}
-
-// h263mi_batch_set_rgba_layout's shape for n streams of w x h
-static int layout_shape(uint32_t n, uint32_t w, uint32_t h, const h263mi_rgba_layout *layout, h263mi_batch::RgbaLayout &lay)
-{
-    uint32_t ow = 0, oh = 0;
-    RC_TRY(rgba_layout_extent(n, w, h, layout, &ow, &oh, &lay.bytes, &lay.kernel));
-    if (lay.placed()) {
-        lay.offsets.resize(n);
-        const uint64_t pitch = (layout->row_pitch ? layout->row_pitch : 4ull * ow);
-        for (uint32_t i = 0; i < n; i++) lay.offsets[i] = layout->offsets ? layout->offsets[i] : (uint64_t)i * oh * pitch;
-    }
-    return H263MI_OK;
-}
-
-uint64_t resize_scratch_bytes(uint32_t w, uint32_t h, uint32_t slots, const h263mi_rgba_resize &r)
-{
-    h263mi_rgba_layout lay;
-    if (resize_as_layout(w, h, r, &lay)) return 0;
-    return (uint64_t)slots * w * h * 4 + ((uint64_t)r.out_width + r.out_height) * sizeof(ResizeSpan);
-}
-
-int make_output_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_rgba_resize *r, h263mi_batch::RgbaLayout &out)
-{
-    h263mi_batch::RgbaLayout shape;
-    if (!r) {
-        RC_TRY(layout_shape(n, w, h, nullptr, shape));
-        out = std::move(shape);
-        return H263MI_OK;
-    }
-    uint64_t bytes = 0;
-    RC_TRY(rgba_resize_extent(n, r, &bytes));
-    h263mi_rgba_layout lay;
-    if (resize_as_layout(w, h, *r, &lay)) {     // identical by definition: the fused layout kernels, no scratch, no extra pass
-        RC_TRY(layout_shape(n, w, h, &lay, shape));
-        out = std::move(shape);
-        return H263MI_OK;
-    }
-    const uint32_t ow = r->out_width, oh = r->out_height;
-    const uint64_t pitch = r->row_pitch ? r->row_pitch : 4ull * ow;
-    std::vector<ResizeSpan> spans((size_t)ow + oh);
-    resize_spans(w, ow, spans.data());
-    resize_spans(h, oh, spans.data() + ow);
-    DeviceGuard g(device);
-    if (!g.ok) return H263MI_ERR_NO_DEVICE;
-    std::shared_ptr<h263mi_resize_scratch> sc(new (std::nothrow) h263mi_resize_scratch());
-    if (!sc) return H263MI_ERR_OUT_OF_MEMORY;
-    sc->device = device;
-    const size_t rgba_bytes = (size_t)n * w * h * 4, span_bytes = spans.size() * sizeof(ResizeSpan);
-    HIP_TRY(hipMalloc((void **)&sc->rgba, rgba_bytes));
-    HIP_TRY(hipMalloc((void **)&sc->spans, span_bytes));
-    HIP_TRY(hipMemcpy(sc->spans, spans.data(), span_bytes, hipMemcpyHostToDevice));
-    sc->bytes = rgba_bytes + span_bytes;
-    shape.bytes = bytes;
-    shape.offsets.resize(n);
-    for (uint32_t i = 0; i < n; i++) shape.offsets[i] = r->offsets ? r->offsets[i] : (uint64_t)i * oh * pitch;
-    shape.resize.scratch = std::move(sc);
-    shape.resize.ow = ow;
-    shape.resize.oh = oh;
-    shape.resize.pitch = (uint32_t)(oh > 1 ? pitch : 4ull * ow);     // (one row: the pitch is never used)
-    out = std::move(shape);
-    return H263MI_OK;
-}
-
 }  // namespace h263mi
 
 // =========================================================================================
@@ -1239,29 +906,14 @@ int h263mi_batch_render_rgba_ps(h263mi_batch *b, uint8_t strength, const uint8_t
     return b->render(st, d_rgba, d_deblocked);
 }
 
-int h263mi_rgba_layout_extent(uint32_t n_streams, uint16_t width, uint16_t height, const h263mi_rgba_layout *layout,
-                              uint16_t *out_w, uint16_t *out_h, uint64_t *bytes)
-{
-    uint32_t ow = 0, oh = 0;
-    RC_TRY(rgba_layout_extent(n_streams, width, height, layout, &ow, &oh, bytes));
-    if (out_w) *out_w = (uint16_t)ow;
-    if (out_h) *out_h = (uint16_t)oh;
-    return H263MI_OK;
-}
-
 int h263mi_batch_set_rgba_layout(h263mi_batch *b, const h263mi_rgba_layout *layout)
 {
     if (!b) return H263MI_ERR_INVALID_ARGUMENT;
     h263mi_batch::RgbaLayout lay;
-    RC_TRY(layout_shape(b->n, b->L.width, b->L.height, layout, lay));
+    RC_TRY(make_rgba_layout_shape(b->n, b->L.width, b->L.height, layout, lay));
     DeviceGuard g(b->device);                  // (a resize it replaces frees its scratch)
     b->layout = std::move(lay);
     return H263MI_OK;
-}
-
-int h263mi_yuv_layout_extent(uint32_t n_streams, uint16_t width, uint16_t height, const h263mi_yuv_layout *layout, uint64_t *bytes)
-{
-    return yuv_layout_extent(n_streams, width, height, layout, bytes);
 }
 
 int h263mi_batch_set_yuv_layout(h263mi_batch *b, const h263mi_yuv_layout *layout)
@@ -1274,11 +926,6 @@ int h263mi_batch_set_yuv_layout(h263mi_batch *b, const h263mi_yuv_layout *layout
     return H263MI_OK;
 }
 
-int h263mi_yuv_resize_extent(uint32_t n_streams, const h263mi_yuv_resize *r, uint64_t *bytes)
-{
-    return yuv_resize_extent(n_streams, r, bytes);
-}
-
 int h263mi_batch_set_yuv_resize(h263mi_batch *b, const h263mi_yuv_resize *r)
 {
     if (!b) return H263MI_ERR_INVALID_ARGUMENT;
@@ -1287,11 +934,6 @@ int h263mi_batch_set_yuv_resize(h263mi_batch *b, const h263mi_yuv_resize *r)
     DeviceGuard g(b->device);                  // (the shape it replaces frees its memory, unless a pending rendering holds it)
     b->yuv = std::move(shape);
     return H263MI_OK;
-}
-
-int h263mi_rgba_resize_extent(uint32_t n_streams, const h263mi_rgba_resize *r, uint64_t *bytes)
-{
-    return rgba_resize_extent(n_streams, r, bytes);
 }
 
 int h263mi_batch_set_rgba_resize(h263mi_batch *b, const h263mi_rgba_resize *r)

@@ -2,6 +2,8 @@
 // store, the per-stream reference bookkeeping of state.rs:464-483, the deferred post-processing of pipeline mode, launch
 // timing, and the pinned staging slots of the entry points that take host data.
 //   batch.cpp          frame store, submit / render / sync, timing, the entry points over DEVICE records
+//   output_shape.h     the shapes a rendering writes in (RGBA and YUV layouts and resizes): placement rules, what the kernels
+//   output_shape.cpp   are told, the device memory a shape holds, and the *_extent entry points
 //   batch_staging.cpp  host records and bitstreams -> pinned staging -> one launch (h263mi_batch_submit_host*,
 //                      h263mi_batch_decode_next_pictures*), and the checks of a caller's host arrays
 //   mixed_set.cpp      streams of different picture sizes: one batch per size class
@@ -14,6 +16,7 @@
 
 #include "../host/bitstream.hpp"
 #include "host_common.h"
+#include "output_shape.h"
 #include "pinned.h"
 #include "worker_pool.h"
 
@@ -30,41 +33,6 @@ struct h263mi_coeff_source {
     bool checked = false;                        // the waves refuse to read beyond pool_blocks / n_events
     const uint32_t *group_index = nullptr;       // sparse RECORDS (ReconArgs::mb_group_index), with ...
     const uint64_t *mb_base = nullptr;           // ... each picture's first record
-};
-
-// What the kernels are told of an RGBA output layout (PostArgs::rgba_scale, rgba_pitch; pitch 0 = today's layout)
-struct h263mi_rgba_out {
-    uint32_t scale = 0, pitch = 0;
-};
-
-// What k_rgba_resize reads (h263mi_batch_set_rgba_resize): the full-size pictures that the rendering kernels write for it, and
-// the spans of its geometry.  Shared between the batch's shape and the pending rendering that was requested under it, so that
-// switching the shape while a pipelined rendering waits frees nothing that rendering still needs.
-struct h263mi_resize_scratch {
-    int device = 0;
-    uint8_t *rgba = nullptr;                   // n * w*h*4 bytes
-    h263mi::ResizeSpan *spans = nullptr;       // W' column spans, then H' row spans
-    uint64_t bytes = 0;                        // device memory held (both allocations)
-    ~h263mi_resize_scratch();
-};
-
-// The per-stream plane offsets of a YUV layout in device memory (3 per stream: Y, Cb or CbCr, Cr), uploaded once when the layout
-// is set.  Shared between the batch's layout and a pending rendering requested under it, like the resize scratch.
-struct h263mi_yuv_offsets {
-    int device = 0;
-    uint64_t *d = nullptr;
-    ~h263mi_yuv_offsets();
-};
-
-// What k_plane_resize reads (h263mi_batch_set_yuv_resize): the full-size planes, tightly packed I420 per stream, that the
-// rendering kernels write for it by default, and the spans of its two geometries.  Shared with a pending rendering like the
-// RGBA scratch above.
-struct h263mi_plane_scratch {
-    int device = 0;
-    uint8_t *planes = nullptr;                 // n * (w*h + 2*cw*ch) bytes
-    h263mi::ResizeSpan *spans = nullptr;       // W' luma column spans, H' luma row spans, cW' chroma column spans, cH' chroma row spans
-    uint64_t bytes = 0;                        // device memory held (both allocations)
-    ~h263mi_plane_scratch();
 };
 
 struct h263mi_batch {
@@ -98,57 +66,13 @@ struct h263mi_batch {
             return true;
         }
     };
-    // The output layout of the RGBA (h263mi_batch_set_rgba_layout).  `kernel`: what the kernels are told (pitch 0: the default
-    // kernels); `offsets` (empty = s * H' * pitch): where stream s's picture
-    // starts in the caller's buffer -- handed to the kernels as per-stream pointers (ptr_ring).
-    typedef h263mi_rgba_out OutLayout;
-    struct RgbaLayout {
-        OutLayout kernel;
-        std::vector<uint64_t> offsets;
-        uint64_t bytes = 0;                    // what d_rgba must hold (h263mi_rgba_layout_extent)
-        bool placed() const { return kernel.pitch != 0; }
-        // a resize that is not one of the layouts (scratch != nullptr): the rendering kernels write the full-size pictures into
-        // the scratch with the default `kernel`, then k_rgba_resize writes W' x H' at `offsets` (all of them filled in)
-        struct Resize {
-            std::shared_ptr<h263mi_resize_scratch> scratch;
-            uint32_t ow = 0, oh = 0, pitch = 0;
-            bool on() const { return scratch != nullptr; }
-        } resize;
-    } layout;
-    // The layout of the deblocked planes in d_deblocked (h263mi_batch_set_yuv_layout).  format 0: none -- tightly packed I420
-    // written by the default kernels, as ever.  Else the YUV instantiations write the planes (kernels.h: launch_post_yuv,
-    // launch_frame_yuv), and RGBA asked for in the same call is rendered by a launch of its own.
-    // Or the planes are RESIZED (h263mi_batch_set_yuv_resize; then format stays 0): the default kernels write the full-size
-    // planes into the resize's scratch and k_plane_resize follows them on the same stream.  A layout or a resize, never both.
-    struct YuvLayout {
-        uint32_t format = 0;                   // 0, YUV_OUT_I420, YUV_OUT_NV12
-        uint32_t pitch_y = 0, pitch_c = 0;
-        bool wide = false;                     // pitches and offsets are all multiples of 4: the wide-store path
-        std::shared_ptr<h263mi_yuv_offsets> offsets;
-        uint64_t bytes = 0;                    // what d_deblocked must hold (h263mi_yuv_layout_extent)
-        bool on() const { return format != 0; }
-        // what the kernels are told for planes at d_planes
-        h263mi::YuvOut out(const uint8_t *d_planes) const
-        {
-            h263mi::YuvOut o{};
-            o.format = format;
-            o.wide = (wide && ((uintptr_t)d_planes & 3u) == 0) ? 1u : 0u;
-            o.pitch_y = pitch_y;
-            o.pitch_c = pitch_c;
-            o.offsets = offsets ? offsets->d : nullptr;
-            return o;
-        }
-        // a resize that is not the full-size layout (scratch != nullptr): W' x H' planes in `format` at `offsets` of d_deblocked
-        struct Resize {
-            std::shared_ptr<h263mi_plane_scratch> scratch;
-            uint32_t format = 0;               // YUV_OUT_I420, YUV_OUT_NV12
-            uint32_t ow = 0, oh = 0, pitch_y = 0, pitch_c = 0;
-            bool wide = false;                 // pitches and offsets are all multiples of 4
-            std::vector<uint64_t> offsets;     // 3 per stream: Y, Cb or CbCr, Cr
-            bool on() const { return scratch != nullptr; }
-        } resize;
-        bool shaped() const { return on() || resize.on(); }      // (then `bytes` is what d_deblocked must hold)
-    } yuv;
+    // The shapes in force (output_shape.h): of the RGBA (h263mi_batch_set_rgba_layout, _set_rgba_resize) and of the deblocked
+    // planes (h263mi_batch_set_yuv_layout, _set_yuv_resize).  A rendering is told its shapes (render), these by default.
+    typedef h263mi::OutLayout OutLayout;
+    typedef h263mi::RgbaLayout RgbaLayout;
+    typedef h263mi::YuvLayout YuvLayout;
+    RgbaLayout layout;
+    YuvLayout yuv;
     struct PendingPost {
         bool valid = false;
         YuvLayout yuv;                         // the plane layout in force when the rendering was requested
@@ -286,12 +210,13 @@ struct h263mi_batch {
     // launch of their own for the RGBA if that is asked for too
     int launch_post_sets(const std::vector<int8_t> &sets, const Strengths &strength, uint8_t *d_rgba, uint8_t *d_planes, hipStream_t on,
                          uint8_t *const *rgba_ptrs = nullptr, OutLayout out = OutLayout(), const YuvLayout *yuv = nullptr);
-    // the batch's layout applied to d_rgba: false = the default layout (d_rgba as it is); true = `ptrs` holds n DEVICE pointers,
+    // the layout `lay` applied to d_rgba: false = the default layout (d_rgba as it is); true = `ptrs` holds n DEVICE pointers,
     // stream s's picture at d_rgba + its offset
-    bool layout_ptrs(uint8_t *d_rgba, std::vector<uint8_t *> &ptrs) const;
-    // a resize in force: the DEVICE array of k_rgba_resize's destinations -- stream s at host_ptrs[s] (if given) or d_rgba +
+    bool layout_ptrs(const RgbaLayout &lay, uint8_t *d_rgba, std::vector<uint8_t *> &ptrs) const;
+    // the resize of `lay`: the DEVICE array of k_rgba_resize's destinations -- stream s at host_ptrs[s] (if given) or d_rgba +
     // its offset, nullptr where sets[s] < 0 -- uploaded on `on`
-    int resize_dst(const std::vector<int8_t> &sets, uint8_t *d_rgba, uint8_t *const *host_ptrs, hipStream_t on, uint8_t *const **d_out);
+    int resize_dst(const RgbaLayout &lay, const std::vector<int8_t> &sets, uint8_t *d_rgba, uint8_t *const *host_ptrs, hipStream_t on,
+                   uint8_t *const **d_out);
     // k_rgba_resize of `rz` into `d_dst` (resize_dst), on `on`; nothing when no stream has a set (sets[s] < 0 for all)
     int launch_resize(const RgbaLayout::Resize &rz, const std::vector<int8_t> &sets, uint8_t *const *d_dst, hipStream_t on);
     // a YUV resize `rz` of planes that go to d_planes: the DEVICE array of k_plane_resize's destinations -- stream s's planes at
@@ -308,8 +233,10 @@ struct h263mi_batch {
     int flush_pending();
     // only_active: the rendering half of a decode call -- streams that sat the call out (h263mi_batch_set_active, no data,
     // a picture that failed to parse) keep their part of the output buffers untouched, as the pipelined form (note_pending)
-    // does; h263mi_batch_render_rgba renders every stream's last picture.
-    int render(const Strengths &strength, uint8_t *d_rgba, uint8_t *d_planes, bool only_active = false, uint8_t *const *host_ptrs = nullptr);
+    // does; h263mi_batch_render_rgba renders every stream's last picture.  In the shapes `rgba_shape` and `yuv_shape` (nullptr: the
+    // batch's own, `layout` and `yuv`).
+    int render(const Strengths &strength, uint8_t *d_rgba, uint8_t *d_planes, bool only_active = false, uint8_t *const *host_ptrs = nullptr,
+               const RgbaLayout *rgba_shape = nullptr, const YuvLayout *yuv_shape = nullptr);
     // stream_rc (may be null): per stream 0, H263MI_ERR_UNCODED_IFRAME_BLOCKS or H263MI_ERR_INVALID_ARGUMENT
     int sync(int *stream_rc = nullptr);
     int copy_yuv(uint32_t s, uint8_t *y, uint8_t *cb, uint8_t *cr);
@@ -333,30 +260,6 @@ int digest_spans(PinnedPair<uint64_t> &buf, const HostPlacement &where, const ui
 inline int digest_rc(int rc) { return rc == H263MI_ERR_OUT_OF_MEMORY ? H263MI_ERR_HIP : rc; }
 // both halves of an Adler-32 start value are residues
 inline bool digest_seed_valid(uint32_t seed) { return (seed & 0xffffu) < DIGEST_MOD && (seed >> 16) < DIGEST_MOD; }
-// h263mi_rgba_layout_extent; out_kernel (may be null): what the kernels are told (pitch 0 = today's layout)
-int rgba_layout_extent(uint32_t n_streams, uint32_t w, uint32_t h, const h263mi_rgba_layout *layout, uint32_t *out_w,
-                       uint32_t *out_h, uint64_t *bytes, h263mi_batch::OutLayout *out_kernel = nullptr);
-// h263mi_yuv_layout_extent.  shape (may be null): format / pitches / wide / bytes filled in (no device memory);
-// offsets (may be null): the 3 * n_streams plane offsets the kernels take (default placement spelled out)
-int yuv_layout_extent(uint32_t n_streams, uint32_t w, uint32_t h, const h263mi_yuv_layout *layout, uint64_t *bytes,
-                      h263mi_batch::YuvLayout *shape = nullptr, std::vector<uint64_t> *offsets = nullptr);
-// the layout (NULL: none, format 0) for n streams of w x h on `device`, its offsets uploaded
-int make_yuv_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_yuv_layout *layout, h263mi_batch::YuvLayout &out);
-// h263mi_yuv_resize_extent; shape / offsets as yuv_layout_extent (of the W' x H' picture)
-int yuv_resize_extent(uint32_t n_streams, const h263mi_yuv_resize *r, uint64_t *bytes, h263mi_batch::YuvLayout *shape = nullptr,
-                      std::vector<uint64_t> *offsets = nullptr);
-// the YUV shape `r` (NULL: none) for n streams of w x h on `device`: the full-size layout it is by definition when W' = w and
-// H' = h, else the resize with a new scratch
-int make_yuv_resize_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_yuv_resize *r, h263mi_batch::YuvLayout &out);
-// h263mi_rgba_resize_extent for n streams
-int rgba_resize_extent(uint32_t n_streams, const h263mi_rgba_resize *r, uint64_t *bytes);
-// the layout that a resize of a w x h picture is by definition (full size, or 1/2 or 1/4 of sizes that 2 or 4 divide), into
-// *lay (offsets and pitch copied); false: none, the resize needs k_rgba_resize
-bool resize_as_layout(uint32_t w, uint32_t h, const h263mi_rgba_resize &r, h263mi_rgba_layout *lay);
-// the shape `r` (NULL: the default) for a batch of n streams of w x h: the layout it routes to, or the resize with a new scratch
-int make_output_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_rgba_resize *r, h263mi_batch::RgbaLayout &out);
-// device memory a resize of `slots` pictures of w x h holds (0: it is a layout)
-uint64_t resize_scratch_bytes(uint32_t w, uint32_t h, uint32_t slots, const h263mi_rgba_resize &r);
 int batch_create(uint32_t n_streams, uint32_t w, uint32_t h, const h263mi_backend_cfg *cfg, h263mi_batch **out);
 // where the host side of device `dev`'s work belongs (worker_pool.h): the PCI addresses of the visible devices -> sysfs
 HostPlacement placement_of_device(int dev);

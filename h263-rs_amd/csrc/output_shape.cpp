@@ -1,0 +1,371 @@
+// output_shape.cpp -- output shapes (output_shape.h): the placement rules of include/h263mi.h, what the kernels are told of a
+// placement, and the device memory a shape needs.
+#include "output_shape.h"
+
+#include <algorithm>
+#include <new>
+
+namespace h263mi {
+
+void DeviceBlock::release()
+{
+    if (!p) return;
+    DeviceGuard g(device);
+    (void)hipFree(p);
+    p = nullptr;
+    bytes = 0;
+}
+
+int DeviceBlock::make(int dev, uint64_t n, const void *from)
+{
+    device = dev;
+    HIP_TRY(hipMalloc(&p, n));
+    bytes = n;
+    if (from) HIP_TRY(hipMemcpy(p, from, n, hipMemcpyHostToDevice));
+    return H263MI_OK;
+}
+
+int DeviceBlock::reserve(int dev, uint64_t n)
+{
+    if (n <= bytes) return H263MI_OK;
+    release();
+    return make(dev, n);
+}
+
+// =========================================================================================
+// placement
+// =========================================================================================
+// One plane of a placed output (an RGBA picture is the one plane of its stream): `rows` rows of `row` bytes, `pitch` bytes
+// apart, at byte `offset` of the caller's buffer -- a rectangle on the grid of its pitch: rows [offset / pitch, + rows), byte
+// columns [offset % pitch, + row).
+struct PlaneRect {
+    uint64_t pitch, row, rows, offset, align;
+    bool chroma;                           // on the grid of the chroma pitch
+    uint64_t span() const { return (rows - 1) * pitch + row; }       // bytes from the plane's first byte to behind its last
+    uint64_t r0() const { return offset / pitch; }
+    uint64_t c0() const { return offset % pitch; }
+};
+
+// what holds of a plane wherever it lies: its rows fit the pitch, and lane offsets are 32-bit
+static bool plane_fits(uint64_t pitch, uint64_t row, uint64_t rows)
+{
+    if (pitch < row || (rows > 1 && pitch >= (1ull << 32))) return false;
+    return (rows - 1) * pitch + row < (1ull << 32);
+}
+// what the kernels are told of a pitch (one row: the pitch is never used)
+static uint32_t kernel_pitch(uint64_t pitch, uint64_t row, uint64_t rows) { return (uint32_t)(rows > 1 ? pitch : row); }
+
+// The placement check: every plane aligned, inside the rows of its grid and inside 64 bits; no two planes of a grid
+// sharing a byte; and, where the luma and the chroma grid differ, no luma plane's byte span meeting a chroma plane's.
+// *extent: the bytes the buffer must hold.
+static int planes_extent(std::vector<PlaneRect> planes, uint64_t *extent)
+{
+    uint64_t total = 0;
+    bool one_grid = true;
+    for (const PlaneRect &p : planes) {
+        if (p.offset % p.align || p.c0() + p.row > p.pitch || p.offset > UINT64_MAX - p.span()) return H263MI_ERR_INVALID_ARGUMENT;
+        total = std::max(total, p.offset + p.span());
+        one_grid = one_grid && p.pitch == planes[0].pitch;
+    }
+    // within a grid (one grid for all planes: the rectangle test decides between luma and chroma too)
+    std::sort(planes.begin(), planes.end(), [](const PlaneRect &x, const PlaneRect &y) { return x.r0() < y.r0() || (x.r0() == y.r0() && x.c0() < y.c0()); });
+    for (size_t i = 0; i < planes.size(); i++)
+        for (size_t j = i + 1; j < planes.size() && planes[j].r0() < planes[i].r0() + planes[i].rows; j++) {      // (sorted by first row: later ones start lower)
+            const PlaneRect &a = planes[i], &b = planes[j];
+            if ((one_grid || a.chroma == b.chroma) && b.c0() < a.c0() + a.row && a.c0() < b.c0() + b.row) return H263MI_ERR_INVALID_ARGUMENT;
+        }
+    if (!one_grid) {
+        std::sort(planes.begin(), planes.end(), [](const PlaneRect &x, const PlaneRect &y) { return x.offset < y.offset; });
+        uint64_t end_luma = 0, end_chroma = 0;
+        for (const PlaneRect &p : planes) {
+            if (p.offset < (p.chroma ? end_luma : end_chroma)) return H263MI_ERR_INVALID_ARGUMENT;
+            uint64_t &e = p.chroma ? end_chroma : end_luma;
+            e = std::max(e, p.offset + p.span());
+        }
+    }
+    *extent = total;
+    return H263MI_OK;
+}
+
+int rgba_layout_extent(uint32_t n_streams, uint32_t w, uint32_t h, const h263mi_rgba_layout *lay, uint32_t *out_w, uint32_t *out_h,
+                       uint64_t *bytes, OutLayout *out_kernel)
+{
+    if (!n_streams || !w || !h) return H263MI_ERR_INVALID_ARGUMENT;
+    const uint32_t scale = lay ? lay->scale_log2 : 0u;
+    if (scale > 2) return H263MI_ERR_INVALID_ARGUMENT;
+    if (lay)
+        for (uint8_t r : lay->reserved)
+            if (r) return H263MI_ERR_INVALID_ARGUMENT;
+    const uint32_t ow = (w + (1u << scale) - 1) >> scale, oh = (h + (1u << scale) - 1) >> scale;
+    const uint64_t row = 4ull * ow, pitch = (lay && lay->row_pitch) ? lay->row_pitch : row;
+    if (pitch % 4 || !plane_fits(pitch, row, oh)) return H263MI_ERR_INVALID_ARGUMENT;
+    uint64_t total = 0;
+    const uint64_t *off = lay ? lay->offsets : nullptr;
+    if (!off) {
+        const unsigned __int128 t = (unsigned __int128)(n_streams - 1) * oh * pitch + (uint64_t)(oh - 1) * pitch + row;
+        if (t > UINT64_MAX) return H263MI_ERR_INVALID_ARGUMENT;
+        total = (uint64_t)t;
+    } else {
+        std::vector<PlaneRect> planes(n_streams);
+        for (uint32_t i = 0; i < n_streams; i++) planes[i] = PlaneRect{pitch, row, oh, off[i], 4, false};
+        RC_TRY(planes_extent(std::move(planes), &total));
+    }
+    if (out_w) *out_w = ow;
+    if (out_h) *out_h = oh;
+    if (bytes) *bytes = total;
+    if (out_kernel) {
+        // the default layout (full size, tight rows, pictures back to back) keeps the default kernels
+        const bool dflt = scale == 0 && pitch == row && !off;
+        out_kernel->scale = dflt ? 0u : scale;
+        out_kernel->pitch = dflt ? 0u : kernel_pitch(pitch, row, oh);
+    }
+    return H263MI_OK;
+}
+
+// h263mi_yuv_layout_extent (include/h263mi.h has the rules)
+int yuv_layout_extent(uint32_t n_streams, uint32_t w, uint32_t h, const h263mi_yuv_layout *lay, uint64_t *bytes, YuvLayout *shape,
+                      std::vector<uint64_t> *offsets_out)
+{
+    if (!n_streams || !w || !h || w > 65535 || h > 65535) return H263MI_ERR_INVALID_ARGUMENT;
+    const uint32_t fmt = lay ? lay->format : (uint32_t)H263MI_YUV_I420;
+    if (fmt != H263MI_YUV_I420 && fmt != H263MI_YUV_NV12) return H263MI_ERR_INVALID_ARGUMENT;
+    if (lay)
+        for (uint8_t r : lay->reserved)
+            if (r) return H263MI_ERR_INVALID_ARGUMENT;
+    const bool nv12 = fmt == H263MI_YUV_NV12;
+    const uint64_t cw = (w + 1) / 2, ch = (h + 1) / 2;
+    const uint64_t row_y = w, row_c = nv12 ? 2 * cw : cw;
+    const uint64_t pitch_y = (lay && lay->pitch_y) ? lay->pitch_y : row_y, pitch_c = (lay && lay->pitch_c) ? lay->pitch_c : row_c;
+    if (!plane_fits(pitch_y, row_y, h) || !plane_fits(pitch_c, row_c, ch)) return H263MI_ERR_INVALID_ARGUMENT;
+    const uint64_t *oy = lay ? lay->offsets_y : nullptr, *ocb = lay ? lay->offsets_cb : nullptr, *ocr = lay ? lay->offsets_cr : nullptr;
+    if (nv12 && ocr) return H263MI_ERR_INVALID_ARGUMENT;
+    const int given = (oy ? 1 : 0) + (ocb ? 1 : 0) + (ocr ? 1 : 0), all = nv12 ? 2 : 3;
+    if (given != 0 && given != all) return H263MI_ERR_INVALID_ARGUMENT;
+    const uint32_t chroma_planes = nv12 ? 1u : 2u;
+    std::vector<uint64_t> offs((size_t)3 * n_streams);
+    uint64_t total = 0;
+    if (!given) {
+        // planes back to back, pictures back to back: P bytes each
+        const unsigned __int128 P = (unsigned __int128)h * pitch_y + (unsigned __int128)chroma_planes * ch * pitch_c;
+        if (P * n_streams > UINT64_MAX) return H263MI_ERR_INVALID_ARGUMENT;
+        for (uint32_t i = 0; i < n_streams; i++) {
+            const uint64_t base = (uint64_t)P * i;
+            offs[3 * i + 0] = base;
+            offs[3 * i + 1] = base + h * pitch_y;
+            offs[3 * i + 2] = nv12 ? offs[3 * i + 1] : base + h * pitch_y + ch * pitch_c;
+        }
+        total = (uint64_t)(P * n_streams);
+    } else {
+        std::vector<PlaneRect> planes;
+        for (uint32_t i = 0; i < n_streams; i++) {
+            offs[3 * i + 0] = oy[i];
+            offs[3 * i + 1] = ocb[i];
+            offs[3 * i + 2] = nv12 ? ocb[i] : ocr[i];
+            planes.push_back(PlaneRect{pitch_y, row_y, h, oy[i], 1, false});
+            for (uint32_t k = 1; k <= chroma_planes; k++) planes.push_back(PlaneRect{pitch_c, row_c, ch, offs[3 * i + k], 1, true});
+        }
+        RC_TRY(planes_extent(std::move(planes), &total));
+    }
+    if (bytes) *bytes = total;
+    if (shape) {
+        shape->format = nv12 ? YUV_OUT_NV12 : YUV_OUT_I420;
+        shape->pitch_y = kernel_pitch(pitch_y, row_y, h);
+        shape->pitch_c = kernel_pitch(pitch_c, row_c, ch);
+        shape->bytes = total;
+        bool wide = shape->pitch_y % 4 == 0 && shape->pitch_c % 4 == 0;
+        for (uint64_t o : offs) wide = wide && o % 4 == 0;
+        shape->wide = wide;
+    }
+    if (offsets_out) *offsets_out = std::move(offs);
+    return H263MI_OK;
+}
+
+h263mi_rgba_layout layout_of(const h263mi_rgba_resize &r)
+{
+    h263mi_rgba_layout lay{};
+    lay.row_pitch = r.row_pitch;
+    lay.offsets = r.offsets;
+    return lay;
+}
+
+h263mi_yuv_layout layout_of(const h263mi_yuv_resize &r)
+{
+    h263mi_yuv_layout lay{};
+    lay.format = r.format;
+    lay.pitch_y = r.pitch_y;
+    lay.pitch_c = r.pitch_c;
+    lay.offsets_y = r.offsets_y;
+    lay.offsets_cb = r.offsets_cb;
+    lay.offsets_cr = r.offsets_cr;
+    return lay;
+}
+
+// what a resize must say before the rules of a layout apply to it
+template <typename R>
+static bool resize_named(const R *r)
+{
+    if (!r || !r->out_width || !r->out_height) return false;
+    for (uint8_t v : r->reserved)
+        if (v) return false;
+    return true;
+}
+
+int rgba_resize_extent(uint32_t n_streams, const h263mi_rgba_resize *r, uint64_t *bytes)
+{
+    if (!resize_named(r)) return H263MI_ERR_INVALID_ARGUMENT;
+    const h263mi_rgba_layout lay = layout_of(*r);
+    return rgba_layout_extent(n_streams, r->out_width, r->out_height, &lay, nullptr, nullptr, bytes);
+}
+
+int yuv_resize_extent(uint32_t n_streams, const h263mi_yuv_resize *r, uint64_t *bytes, YuvLayout *shape, std::vector<uint64_t> *offsets)
+{
+    if (!resize_named(r)) return H263MI_ERR_INVALID_ARGUMENT;
+    const h263mi_yuv_layout lay = layout_of(*r);
+    return yuv_layout_extent(n_streams, r->out_width, r->out_height, &lay, bytes, shape, offsets);
+}
+
+bool resize_as_layout(uint32_t w, uint32_t h, const h263mi_rgba_resize &r, h263mi_rgba_layout *lay)
+{
+    for (int f = 0; f <= 2; f++) {
+        const uint32_t m = (1u << f) - 1;
+        if ((w & m) || (h & m) || r.out_width != (w >> f) || r.out_height != (h >> f)) continue;
+        *lay = layout_of(r);
+        lay->scale_log2 = (uint8_t)f;
+        return true;
+    }
+    return false;
+}
+
+uint64_t resize_scratch_bytes(uint32_t w, uint32_t h, uint32_t slots, const h263mi_rgba_resize &r)
+{
+    h263mi_rgba_layout lay;
+    if (resize_as_layout(w, h, r, &lay)) return 0;
+    return (uint64_t)slots * w * h * 4 + ((uint64_t)r.out_width + r.out_height) * sizeof(ResizeSpan);
+}
+
+// =========================================================================================
+// shapes
+// =========================================================================================
+int make_rgba_layout_shape(uint32_t n, uint32_t w, uint32_t h, const h263mi_rgba_layout *layout, RgbaLayout &out)
+{
+    RgbaLayout lay;
+    uint32_t ow = 0, oh = 0;
+    RC_TRY(rgba_layout_extent(n, w, h, layout, &ow, &oh, &lay.bytes, &lay.kernel));
+    if (lay.placed()) {
+        lay.offsets.resize(n);
+        const uint64_t pitch = (layout->row_pitch ? layout->row_pitch : 4ull * ow);
+        for (uint32_t i = 0; i < n; i++) lay.offsets[i] = layout->offsets ? layout->offsets[i] : (uint64_t)i * oh * pitch;
+    }
+    out = std::move(lay);
+    return H263MI_OK;
+}
+
+// The scratch of a resize on `device`: `pixel_bytes` for the full-size pictures, and the span tables of the geometries
+// (source length -> output length, in the order the kernel's tables lie) uploaded.
+struct SpanGeometry { uint32_t in, out; };
+static int make_scratch(int device, size_t pixel_bytes, std::initializer_list<SpanGeometry> geometries, std::shared_ptr<ResizeScratch> &out)
+{
+    std::vector<ResizeSpan> spans;
+    for (const SpanGeometry &g : geometries) {
+        spans.resize(spans.size() + g.out);
+        resize_spans(g.in, g.out, spans.data() + spans.size() - g.out);
+    }
+    DeviceGuard g(device);
+    if (!g.ok) return H263MI_ERR_NO_DEVICE;
+    std::shared_ptr<ResizeScratch> sc(new (std::nothrow) ResizeScratch());
+    if (!sc) return H263MI_ERR_OUT_OF_MEMORY;
+    RC_TRY(sc->pixels.make(device, pixel_bytes));
+    RC_TRY(sc->spans.make(device, spans.size() * sizeof(ResizeSpan), spans.data()));
+    out = std::move(sc);
+    return H263MI_OK;
+}
+
+int make_output_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_rgba_resize *r, RgbaLayout &out)
+{
+    if (!r) return make_rgba_layout_shape(n, w, h, nullptr, out);
+    RgbaLayout shape;
+    RC_TRY(rgba_resize_extent(n, r, &shape.bytes));
+    h263mi_rgba_layout lay;
+    // identical by definition: the fused layout kernels, no scratch, no extra pass
+    if (resize_as_layout(w, h, *r, &lay)) return make_rgba_layout_shape(n, w, h, &lay, out);
+    const uint32_t ow = r->out_width, oh = r->out_height;
+    const uint64_t row = 4ull * ow, pitch = r->row_pitch ? r->row_pitch : row;
+    RC_TRY(make_scratch(device, (size_t)n * w * h * 4, {{w, ow}, {h, oh}}, shape.resize.scratch));
+    shape.offsets.resize(n);
+    for (uint32_t i = 0; i < n; i++) shape.offsets[i] = r->offsets ? r->offsets[i] : (uint64_t)i * oh * pitch;
+    shape.resize.ow = ow;
+    shape.resize.oh = oh;
+    shape.resize.pitch = kernel_pitch(pitch, row, oh);
+    out = std::move(shape);
+    return H263MI_OK;
+}
+
+int make_yuv_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_yuv_layout *lay, YuvLayout &out)
+{
+    YuvLayout shape;
+    if (!lay) {
+        out = std::move(shape);
+        return H263MI_OK;
+    }
+    std::vector<uint64_t> offs;
+    RC_TRY(yuv_layout_extent(n, w, h, lay, nullptr, &shape, &offs));
+    DeviceGuard g(device);
+    if (!g.ok) return H263MI_ERR_NO_DEVICE;
+    std::shared_ptr<DeviceBlock> d(new (std::nothrow) DeviceBlock());
+    if (!d) return H263MI_ERR_OUT_OF_MEMORY;
+    RC_TRY(d->make(device, offs.size() * sizeof(uint64_t), offs.data()));
+    shape.offsets = std::move(d);
+    out = std::move(shape);
+    return H263MI_OK;
+}
+
+int make_yuv_resize_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_yuv_resize *r, YuvLayout &out)
+{
+    if (!r) {
+        out = YuvLayout();
+        return H263MI_OK;
+    }
+    YuvLayout placed, shape;                    // (shape.format 0: the rendering kernels write their default planes, into the scratch)
+    RC_TRY(yuv_resize_extent(n, r, nullptr, &placed, &shape.resize.offsets));
+    const uint32_t ow = r->out_width, oh = r->out_height;
+    if (ow == w && oh == h) {                   // identical by definition: the YUV instantiations, no scratch, no extra pass
+        const h263mi_yuv_layout lay = layout_of(*r);
+        return make_yuv_shape(device, n, w, h, &lay, out);
+    }
+    const uint32_t cw = (w + 1) / 2, ch = (h + 1) / 2, cow = (ow + 1) / 2, coh = (oh + 1) / 2;
+    RC_TRY(make_scratch(device, (size_t)n * ((size_t)w * h + 2 * (size_t)cw * ch), {{w, ow}, {h, oh}, {cw, cow}, {ch, coh}}, shape.resize.scratch));
+    shape.bytes = placed.bytes;
+    shape.resize.format = placed.format;
+    shape.resize.ow = ow;
+    shape.resize.oh = oh;
+    shape.resize.pitch_y = placed.pitch_y;
+    shape.resize.pitch_c = placed.pitch_c;
+    shape.resize.wide = placed.wide;
+    out = std::move(shape);
+    return H263MI_OK;
+}
+
+}  // namespace h263mi
+
+// =========================================================================================
+// C ABI: what a placement comes to
+// =========================================================================================
+extern "C" {
+
+int h263mi_rgba_layout_extent(uint32_t n_streams, uint16_t width, uint16_t height, const h263mi_rgba_layout *layout,
+                              uint16_t *out_w, uint16_t *out_h, uint64_t *bytes)
+{
+    uint32_t ow = 0, oh = 0;
+    RC_TRY(h263mi::rgba_layout_extent(n_streams, width, height, layout, &ow, &oh, bytes));
+    if (out_w) *out_w = (uint16_t)ow;
+    if (out_h) *out_h = (uint16_t)oh;
+    return H263MI_OK;
+}
+int h263mi_yuv_layout_extent(uint32_t n_streams, uint16_t width, uint16_t height, const h263mi_yuv_layout *layout, uint64_t *bytes)
+{
+    return h263mi::yuv_layout_extent(n_streams, width, height, layout, bytes);
+}
+int h263mi_rgba_resize_extent(uint32_t n_streams, const h263mi_rgba_resize *r, uint64_t *bytes) { return h263mi::rgba_resize_extent(n_streams, r, bytes); }
+int h263mi_yuv_resize_extent(uint32_t n_streams, const h263mi_yuv_resize *r, uint64_t *bytes) { return h263mi::yuv_resize_extent(n_streams, r, bytes); }
+
+}  // extern "C"

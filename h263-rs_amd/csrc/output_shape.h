@@ -1,0 +1,132 @@
+// output_shape.h -- the SHAPE a rendering writes its output in: the RGBA layouts and resizes (h263mi_rgba_layout,
+// h263mi_rgba_resize) and the plane layouts and resizes (h263mi_yuv_layout, h263mi_yuv_resize).  A caller's placement is
+// validated here (the *_extent entry points), turned into what the kernels are told, and given the device memory it needs: the
+// plane offsets of a YUV layout, the scratch and the span tables of a resize.  Nothing here knows a frame store: a batch holds
+// one RgbaLayout and one YuvLayout (batch.h) and hands them to its renderings.
+#pragma once
+
+#include <memory>
+#include <vector>
+
+#include "host_common.h"
+
+namespace h263mi {
+
+// One allocation of device memory and its owner: freed on the device it was made on.  Shared (shared_ptr) between a batch's
+// shape and the pending rendering that was requested under it, so that switching the shape while a pipelined rendering waits
+// frees nothing that rendering still needs.
+struct DeviceBlock {
+    int device = 0;
+    void *p = nullptr;
+    uint64_t bytes = 0;
+    DeviceBlock() = default;
+    DeviceBlock(const DeviceBlock &) = delete;
+    DeviceBlock &operator=(const DeviceBlock &) = delete;
+    ~DeviceBlock() { release(); }
+    void release();
+    // `n` bytes on `dev`, the current device (the caller holds a DeviceGuard); with `from`: filled from that host memory
+    int make(int dev, uint64_t n, const void *from = nullptr);
+    // a scratch that only grows: room for `n` bytes (what it held is not kept)
+    int reserve(int dev, uint64_t n);
+    template <typename T>
+    T *as() const { return static_cast<T *>(p); }
+};
+
+// What a resize kernel reads (k_rgba_resize, k_plane_resize): the full-size pictures that the rendering kernels write for it --
+// RGBA, n * w*h*4 bytes, or planes, tightly packed I420 per stream, n * (w*h + 2*cw*ch) bytes -- and the spans of its geometry:
+// W' column spans then H' row spans, for planes followed by the cW' and cH' spans of the chroma planes.
+struct ResizeScratch {
+    DeviceBlock pixels, spans;             // (two allocations: resize_scratch_bytes counts both)
+};
+
+// What the kernels are told of an RGBA output layout (PostArgs::rgba_scale, rgba_pitch; pitch 0 = the default layout)
+struct OutLayout {
+    uint32_t scale = 0, pitch = 0;
+};
+
+// The output shape of the RGBA (h263mi_batch_set_rgba_layout, _set_rgba_resize).  `kernel`: what the kernels are told (pitch 0:
+// the default kernels); `offsets` (empty = s * H' * pitch): where stream s's picture starts in the caller's buffer -- handed to
+// the kernels as per-stream pointers.
+struct RgbaLayout {
+    OutLayout kernel;
+    std::vector<uint64_t> offsets;
+    uint64_t bytes = 0;                    // what d_rgba must hold (h263mi_rgba_layout_extent)
+    bool placed() const { return kernel.pitch != 0; }
+    // a resize that is not one of the layouts (scratch != nullptr): the rendering kernels write the full-size pictures into
+    // the scratch with the default `kernel`, then k_rgba_resize writes W' x H' at `offsets` (all of them filled in)
+    struct Resize {
+        std::shared_ptr<ResizeScratch> scratch;
+        uint32_t ow = 0, oh = 0, pitch = 0;
+        bool on() const { return scratch != nullptr; }
+    } resize;
+};
+
+// The shape of the deblocked planes in d_deblocked (h263mi_batch_set_yuv_layout).  format 0: none -- tightly packed I420
+// written by the default kernels.  Else the YUV instantiations write the planes (kernels.h: launch_post_yuv,
+// launch_frame_yuv), and RGBA asked for in the same call is rendered by a launch of its own.
+// Or the planes are RESIZED (h263mi_batch_set_yuv_resize; then format stays 0): the default kernels write the full-size
+// planes into the resize's scratch and k_plane_resize follows them on the same stream.  A layout or a resize, never both.
+struct YuvLayout {
+    uint32_t format = 0;                   // 0, YUV_OUT_I420, YUV_OUT_NV12
+    uint32_t pitch_y = 0, pitch_c = 0;
+    bool wide = false;                     // pitches and offsets are all multiples of 4: the wide-store path
+    std::shared_ptr<DeviceBlock> offsets;  // DEVICE: 3 per stream (Y, Cb or CbCr, Cr), uploaded once when the layout is set
+    uint64_t bytes = 0;                    // what d_deblocked must hold (h263mi_yuv_layout_extent)
+    bool on() const { return format != 0; }
+    // what the kernels are told for planes at d_planes
+    YuvOut out(const uint8_t *d_planes) const
+    {
+        YuvOut o{};
+        o.format = format;
+        o.wide = (wide && ((uintptr_t)d_planes & 3u) == 0) ? 1u : 0u;
+        o.pitch_y = pitch_y;
+        o.pitch_c = pitch_c;
+        o.offsets = offsets ? offsets->as<uint64_t>() : nullptr;
+        return o;
+    }
+    // a resize that is not the full-size layout (scratch != nullptr): W' x H' planes in `format` at `offsets` of d_deblocked
+    struct Resize {
+        std::shared_ptr<ResizeScratch> scratch;
+        uint32_t format = 0;               // YUV_OUT_I420, YUV_OUT_NV12
+        uint32_t ow = 0, oh = 0, pitch_y = 0, pitch_c = 0;
+        bool wide = false;                 // pitches and offsets are all multiples of 4
+        std::vector<uint64_t> offsets;     // 3 per stream: Y, Cb or CbCr, Cr
+        bool on() const { return scratch != nullptr; }
+    } resize;
+    bool shaped() const { return on() || resize.on(); }      // (then `bytes` is what d_deblocked must hold)
+};
+
+// ---- what a caller's placement comes to (pure host functions: the *_extent entry points)
+// h263mi_rgba_layout_extent; out_kernel (may be null): what the kernels are told (pitch 0 = the default layout)
+int rgba_layout_extent(uint32_t n_streams, uint32_t w, uint32_t h, const h263mi_rgba_layout *layout, uint32_t *out_w,
+                       uint32_t *out_h, uint64_t *bytes, OutLayout *out_kernel = nullptr);
+// h263mi_yuv_layout_extent.  shape (may be null): format / pitches / wide / bytes filled in (no device memory);
+// offsets (may be null): the 3 * n_streams plane offsets the kernels take (default placement spelled out)
+int yuv_layout_extent(uint32_t n_streams, uint32_t w, uint32_t h, const h263mi_yuv_layout *layout, uint64_t *bytes,
+                      YuvLayout *shape = nullptr, std::vector<uint64_t> *offsets = nullptr);
+// A resize is placed as a layout of the W' x H' picture is: that layout (full size for RGBA: scale_log2 0)
+h263mi_rgba_layout layout_of(const h263mi_rgba_resize &r);
+h263mi_yuv_layout layout_of(const h263mi_yuv_resize &r);
+// h263mi_rgba_resize_extent for n streams
+int rgba_resize_extent(uint32_t n_streams, const h263mi_rgba_resize *r, uint64_t *bytes);
+// h263mi_yuv_resize_extent; shape / offsets as yuv_layout_extent (of the W' x H' picture)
+int yuv_resize_extent(uint32_t n_streams, const h263mi_yuv_resize *r, uint64_t *bytes, YuvLayout *shape = nullptr,
+                      std::vector<uint64_t> *offsets = nullptr);
+// the layout that a resize of a w x h picture is by definition (full size, or 1/2 or 1/4 of sizes that 2 or 4 divide), into
+// *lay (offsets and pitch copied); false: none, the resize needs k_rgba_resize
+bool resize_as_layout(uint32_t w, uint32_t h, const h263mi_rgba_resize &r, h263mi_rgba_layout *lay);
+// device memory a resize of `slots` pictures of w x h holds (0: it is a layout)
+uint64_t resize_scratch_bytes(uint32_t w, uint32_t h, uint32_t slots, const h263mi_rgba_resize &r);
+
+// ---- the shapes, with the device memory they need, for n streams of w x h on `device`
+// h263mi_batch_set_rgba_layout's (NULL: the default); no device memory
+int make_rgba_layout_shape(uint32_t n, uint32_t w, uint32_t h, const h263mi_rgba_layout *layout, RgbaLayout &out);
+// the RGBA shape `r` (NULL: the default): the layout it is by definition, or the resize with a new scratch
+int make_output_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_rgba_resize *r, RgbaLayout &out);
+// the layout (NULL: none, format 0), its offsets uploaded
+int make_yuv_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_yuv_layout *layout, YuvLayout &out);
+// the YUV shape `r` (NULL: none): the full-size layout it is by definition when W' = w and H' = h, else the resize with a new
+// scratch
+int make_yuv_resize_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_yuv_resize *r, YuvLayout &out);
+
+}  // namespace h263mi

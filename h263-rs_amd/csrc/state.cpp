@@ -17,20 +17,17 @@ struct h263mi_state {
     bool has_last = false;
     bits::ParserContext parser_ctx;   // header + format of the last picture decoded from a bitstream (state.rs:143-167)
     bits::ParsedPicture parsed;       // parse results of h263mi_decode_next_picture: kept, so that its buffers are reused
-    uint8_t *d_rgba = nullptr;  size_t cap_rgba = 0;   // rendering scratch of h263mi_render_rgba[_layout]
+    DeviceBlock rgba, planes;         // grow-only scratches: what the h263mi_render_rgba* / h263mi_render_yuv* entries render into
     // h263mi_render_yuv: the device-side shape it renders in (per format: 256-byte pitches, the wide-store path for every
     // picture size), kept for as long as the picture size stays, and the scratch that holds the planes
     struct YuvScratch {
         h263mi_batch::YuvLayout shape;
         uint32_t w = 0, h = 0;
     } yuv[2];
-    uint8_t *d_yuv = nullptr;  size_t cap_yuv = 0;
     ~h263mi_state()
     {
         DeviceGuard g(cfg.device_id);
         if (b) (void)hipStreamSynchronize(b->stream);
-        if (d_rgba) (void)hipFree(d_rgba);
-        if (d_yuv) (void)hipFree(d_yuv);
         delete b;
     }
 };
@@ -266,6 +263,41 @@ static int state_strength(const h263mi_state *s, uint8_t strength, h263mi_batch:
     return H263MI_OK;
 }
 
+// The last picture as W' x H' RGBA in `shape`: rendered with tight rows into the state's scratch (which holds them), then copied out
+// at the caller's pitch -- row by row when that is wider -- and waited for.
+static int render_rgba_shaped(h263mi_state *s, const h263mi_batch::Strengths &st, const h263mi_batch::RgbaLayout &shape, uint32_t ow,
+                              uint32_t oh, uint64_t row_pitch, uint8_t *rgba)
+{
+    const hipStream_t on = s->b->stream;
+    uint8_t *d = s->rgba.as<uint8_t>();
+    RC_TRY(s->b->render(st, d, nullptr, false, nullptr, &shape));
+    const size_t row = (size_t)ow * 4, pitch = row_pitch ? (size_t)row_pitch : row;
+    if (pitch == row) HIP_TRY(hipMemcpyAsync(rgba, d, row * oh, hipMemcpyDeviceToHost, on));
+    else HIP_TRY(hipMemcpy2DAsync(rgba, pitch, d, row, row, oh, hipMemcpyDeviceToHost, on));
+    HIP_TRY(hipStreamSynchronize(on));
+    return H263MI_OK;
+}
+
+// The last picture's planes in `shape`: rendered into the state's plane scratch (made to hold them) -- a w x h luma plane at pitch
+// dpy, behind it the chroma planes (I420: Cb, Cr; NV12: one of CbCr pairs) of ch rows of row_c bytes at pitch dpc -- then each plane
+// copied out row by row into the caller's rectangle (`host` has its pitches, `off` its offsets: nothing else of `out` is touched)
+// and waited for.
+static int render_planes_shaped(h263mi_state *s, const h263mi_batch::Strengths &st, const h263mi_batch::YuvLayout &shape, uint8_t *out,
+                                const h263mi_batch::YuvLayout &host, const std::vector<uint64_t> &off, uint32_t w, uint32_t h, uint32_t row_c,
+                                uint32_t ch, size_t dpy, size_t dpc)
+{
+    RC_TRY(s->planes.reserve(s->cfg.device_id, shape.bytes));
+    RC_TRY(s->b->render(st, nullptr, s->planes.as<uint8_t>(), false, nullptr, nullptr, &shape));
+    const hipStream_t on = s->b->stream;
+    const uint8_t *d_y = s->planes.as<uint8_t>(), *d_c0 = d_y + (size_t)h * dpy;
+    HIP_TRY(hipMemcpy2DAsync(out + off[0], h > 1 ? host.pitch_y : w, d_y, dpy, w, h, hipMemcpyDeviceToHost, on));
+    HIP_TRY(hipMemcpy2DAsync(out + off[1], ch > 1 ? host.pitch_c : row_c, d_c0, dpc, row_c, ch, hipMemcpyDeviceToHost, on));
+    if (host.format != YUV_OUT_NV12)
+        HIP_TRY(hipMemcpy2DAsync(out + off[2], ch > 1 ? host.pitch_c : row_c, d_c0 + (size_t)ch * dpc, dpc, row_c, ch, hipMemcpyDeviceToHost, on));
+    HIP_TRY(hipStreamSynchronize(on));
+    return H263MI_OK;
+}
+
 int h263mi_render_rgba(const h263mi_state *cs, uint8_t strength, uint8_t *rgba)
 {
     h263mi_state *s = const_cast<h263mi_state *>(cs);
@@ -273,19 +305,10 @@ int h263mi_render_rgba(const h263mi_state *cs, uint8_t strength, uint8_t *rgba)
     if (!s->has_last || !s->b) return H263MI_ERR_NO_PICTURE;
     DeviceGuard g(s->cfg.device_id);
     h263mi_batch *b = s->b;
-    const size_t bytes = (size_t)b->L.width * b->L.height * 4;
-    if (bytes > s->cap_rgba) {
-        if (s->d_rgba) (void)hipFree(s->d_rgba);
-        s->d_rgba = nullptr; s->cap_rgba = 0;
-        HIP_TRY(hipMalloc((void **)&s->d_rgba, bytes));
-        s->cap_rgba = bytes;
-    }
+    RC_TRY(s->rgba.reserve(s->cfg.device_id, (size_t)b->L.width * 4 * b->L.height));
     h263mi_batch::Strengths st;
     RC_TRY(state_strength(s, strength, st));
-    RC_TRY(b->render(st, s->d_rgba, nullptr));
-    HIP_TRY(hipMemcpyAsync(rgba, s->d_rgba, bytes, hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    return H263MI_OK;
+    return render_rgba_shaped(s, st, b->layout, b->L.width, b->L.height, 0, rgba);
 }
 
 int h263mi_render_rgba_layout(const h263mi_state *cs, uint8_t strength, const h263mi_rgba_layout *layout, uint8_t *rgba)
@@ -295,32 +318,16 @@ int h263mi_render_rgba_layout(const h263mi_state *cs, uint8_t strength, const h2
     if (!s->has_last || !s->b) return H263MI_ERR_NO_PICTURE;
     h263mi_batch *b = s->b;
     uint32_t ow = 0, oh = 0;
-    uint64_t extent = 0;
-    RC_TRY(rgba_layout_extent(1, b->L.width, b->L.height, layout, &ow, &oh, &extent));
+    RC_TRY(rgba_layout_extent(1, b->L.width, b->L.height, layout, &ow, &oh, nullptr));
     h263mi_batch::Strengths st;
     RC_TRY(state_strength(s, strength, st));
     DeviceGuard g(s->cfg.device_id);
-    // rendered tightly (W' x H') into the device scratch, then copied out row by row when the caller's pitch is wider
-    const size_t row = (size_t)ow * 4, bytes = row * oh, pitch = layout && layout->row_pitch ? (size_t)layout->row_pitch : row;
-    if (bytes > s->cap_rgba) {
-        if (s->d_rgba) (void)hipFree(s->d_rgba);
-        s->d_rgba = nullptr; s->cap_rgba = 0;
-        HIP_TRY(hipMalloc((void **)&s->d_rgba, bytes));
-        s->cap_rgba = bytes;
-    }
+    RC_TRY(s->rgba.reserve(s->cfg.device_id, (size_t)ow * 4 * oh));
     h263mi_rgba_layout tight{};
     tight.scale_log2 = layout ? layout->scale_log2 : 0;
-    h263mi_batch::RgbaLayout saved = std::move(b->layout), lay;
-    RC_TRY(rgba_layout_extent(1, b->L.width, b->L.height, &tight, nullptr, nullptr, &lay.bytes, &lay.kernel));
-    if (lay.placed()) lay.offsets.assign(1, 0);
-    b->layout = std::move(lay);
-    const int rc = b->render(st, s->d_rgba, nullptr);
-    b->layout = std::move(saved);
-    RC_TRY(rc);
-    if (pitch == row) HIP_TRY(hipMemcpyAsync(rgba, s->d_rgba, bytes, hipMemcpyDeviceToHost, b->stream));
-    else HIP_TRY(hipMemcpy2DAsync(rgba, pitch, s->d_rgba, row, row, oh, hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    return H263MI_OK;
+    h263mi_batch::RgbaLayout shape;
+    RC_TRY(make_rgba_layout_shape(1, b->L.width, b->L.height, &tight, shape));
+    return render_rgba_shaped(s, st, shape, ow, oh, layout ? layout->row_pitch : 0, rgba);
 }
 
 int h263mi_render_rgba_resize(const h263mi_state *cs, uint8_t strength, const h263mi_rgba_resize *r, uint8_t *rgba)
@@ -333,28 +340,12 @@ int h263mi_render_rgba_resize(const h263mi_state *cs, uint8_t strength, const h2
     h263mi_batch::Strengths st;
     RC_TRY(state_strength(s, strength, st));
     DeviceGuard g(s->cfg.device_id);
-    // rendered tightly (W' x H') into the device scratch, then copied out row by row when the caller's pitch is wider
-    const size_t row = (size_t)r->out_width * 4, bytes = row * r->out_height, pitch = r->row_pitch ? (size_t)r->row_pitch : row;
-    if (bytes > s->cap_rgba) {
-        if (s->d_rgba) (void)hipFree(s->d_rgba);
-        s->d_rgba = nullptr; s->cap_rgba = 0;
-        HIP_TRY(hipMalloc((void **)&s->d_rgba, bytes));
-        s->cap_rgba = bytes;
-    }
+    RC_TRY(s->rgba.reserve(s->cfg.device_id, (size_t)r->out_width * 4 * r->out_height));
     h263mi_rgba_resize tight = *r;
     tight.row_pitch = 0;
-    h263mi_batch::RgbaLayout lay;
-    RC_TRY(make_output_shape(s->cfg.device_id, 1, b->L.width, b->L.height, &tight, lay));
-    h263mi_batch::RgbaLayout saved = std::move(b->layout);
-    b->layout = std::move(lay);
-    const int rc = b->render(st, s->d_rgba, nullptr);
-    lay = std::move(b->layout);                 // (its scratch, if any, goes at the end, once the copy below has waited for it)
-    b->layout = std::move(saved);
-    RC_TRY(rc);
-    if (pitch == row) HIP_TRY(hipMemcpyAsync(rgba, s->d_rgba, bytes, hipMemcpyDeviceToHost, b->stream));
-    else HIP_TRY(hipMemcpy2DAsync(rgba, pitch, s->d_rgba, row, row, r->out_height, hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    return H263MI_OK;
+    h263mi_batch::RgbaLayout shape;            // (its scratch, if any, goes at the end, once the copy out has waited for it)
+    RC_TRY(make_output_shape(s->cfg.device_id, 1, b->L.width, b->L.height, &tight, shape));
+    return render_rgba_shaped(s, st, shape, r->out_width, r->out_height, r->row_pitch, rgba);
 }
 
 int h263mi_render_yuv(const h263mi_state *cs, uint8_t strength, const h263mi_yuv_layout *layout, uint8_t *out)
@@ -372,41 +363,22 @@ int h263mi_render_yuv(const h263mi_state *cs, uint8_t strength, const h263mi_yuv
     RC_TRY(state_strength(s, strength, st));
     DeviceGuard g(s->cfg.device_id);
     // rendered on the device at pitches of 256 bytes, planes back to back (every layout of that kind takes the wide stores),
-    // then each plane copied out row by row into the caller's rectangle: nothing else of `out` is touched
+    // then each plane copied out row by row into the caller's rectangle
     const bool nv12 = host.format == YUV_OUT_NV12;
     const uint32_t row_c = nv12 ? 2 * cw : cw;
+    const size_t dpy = ((size_t)w + 255) / 256 * 256, dpc = ((size_t)row_c + 255) / 256 * 256;
     h263mi_state::YuvScratch &sc = s->yuv[nv12 ? 1 : 0];
     if (!sc.shape.on() || sc.w != w || sc.h != h) {
         h263mi_yuv_layout dev{};
         dev.format = nv12 ? H263MI_YUV_NV12 : H263MI_YUV_I420;
-        dev.pitch_y = ((uint64_t)w + 255) / 256 * 256;
-        dev.pitch_c = ((uint64_t)row_c + 255) / 256 * 256;
+        dev.pitch_y = dpy;
+        dev.pitch_c = dpc;
         sc.shape = h263mi_batch::YuvLayout();
         RC_TRY(make_yuv_shape(s->cfg.device_id, 1, w, h, &dev, sc.shape));
         sc.w = w;
         sc.h = h;
     }
-    const size_t bytes = (size_t)sc.shape.bytes;
-    if (bytes > s->cap_yuv) {
-        if (s->d_yuv) (void)hipFree(s->d_yuv);
-        s->d_yuv = nullptr; s->cap_yuv = 0;
-        HIP_TRY(hipMalloc((void **)&s->d_yuv, bytes));
-        s->cap_yuv = bytes;
-    }
-    h263mi_batch::YuvLayout saved = std::move(b->yuv);
-    b->yuv = sc.shape;
-    const int rc = b->render(st, nullptr, s->d_yuv);
-    b->yuv = std::move(saved);
-    RC_TRY(rc);
-    // (pitch_y, pitch_c of the device shape; default placement: Y at 0, the chroma planes behind it)
-    const size_t dpy = ((size_t)w + 255) / 256 * 256, dpc = ((size_t)row_c + 255) / 256 * 256;
-    const uint8_t *d_c0 = s->d_yuv + (size_t)h * dpy;
-    HIP_TRY(hipMemcpy2DAsync(out + off[0], h > 1 ? host.pitch_y : w, s->d_yuv, dpy, w, h, hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipMemcpy2DAsync(out + off[1], ch > 1 ? host.pitch_c : row_c, d_c0, dpc, row_c, ch, hipMemcpyDeviceToHost, b->stream));
-    if (!nv12)
-        HIP_TRY(hipMemcpy2DAsync(out + off[2], ch > 1 ? host.pitch_c : row_c, d_c0 + (size_t)ch * dpc, dpc, row_c, ch, hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    return H263MI_OK;
+    return render_planes_shaped(s, st, sc.shape, out, host, off, w, h, row_c, ch, dpy, dpc);
 }
 
 int h263mi_render_yuv_resize(const h263mi_state *cs, uint8_t strength, const h263mi_yuv_resize *r, uint8_t *out)
@@ -420,51 +392,24 @@ int h263mi_render_yuv_resize(const h263mi_state *cs, uint8_t strength, const h26
     std::vector<uint64_t> off;
     RC_TRY(yuv_resize_extent(1, r, nullptr, &host, &off));
     if (r->out_width == b->L.width && r->out_height == b->L.height) {      // the full-size layout, by definition
-        h263mi_yuv_layout lay{};
-        lay.format = r->format;
-        lay.pitch_y = r->pitch_y;
-        lay.pitch_c = r->pitch_c;
-        lay.offsets_y = r->offsets_y;
-        lay.offsets_cb = r->offsets_cb;
-        lay.offsets_cr = r->offsets_cr;
+        const h263mi_yuv_layout lay = layout_of(*r);
         return h263mi_render_yuv(cs, strength, &lay, out);
     }
     h263mi_batch::Strengths st;
     RC_TRY(state_strength(s, strength, st));
     DeviceGuard g(s->cfg.device_id);
     // resized on the device at pitches that are multiples of 4, planes back to back (the word stores), then each plane copied
-    // out row by row into the caller's rectangle: nothing else of `out` is touched
+    // out row by row into the caller's rectangle
     const bool nv12 = host.format == YUV_OUT_NV12;
     const uint32_t ow = r->out_width, oh = r->out_height, cow = (ow + 1) / 2, coh = (oh + 1) / 2, row_c = nv12 ? 2 * cow : cow;
     const size_t dpy = ((size_t)ow + 3) / 4 * 4, dpc = ((size_t)row_c + 3) / 4 * 4;
-    h263mi_yuv_resize dev{};
-    dev.out_width = r->out_width;
-    dev.out_height = r->out_height;
-    dev.format = r->format;
+    h263mi_yuv_resize dev = *r;
     dev.pitch_y = dpy;
     dev.pitch_c = dpc;
-    h263mi_batch::YuvLayout shape;
+    dev.offsets_y = dev.offsets_cb = dev.offsets_cr = nullptr;
+    h263mi_batch::YuvLayout shape;              // (its scratch goes at the end, once the copies out have waited for it)
     RC_TRY(make_yuv_resize_shape(s->cfg.device_id, 1, b->L.width, b->L.height, &dev, shape));
-    const size_t bytes = (size_t)shape.bytes;
-    if (bytes > s->cap_yuv) {
-        if (s->d_yuv) (void)hipFree(s->d_yuv);
-        s->d_yuv = nullptr; s->cap_yuv = 0;
-        HIP_TRY(hipMalloc((void **)&s->d_yuv, bytes));
-        s->cap_yuv = bytes;
-    }
-    h263mi_batch::YuvLayout saved = std::move(b->yuv);
-    b->yuv = std::move(shape);
-    const int rc = b->render(st, nullptr, s->d_yuv);
-    shape = std::move(b->yuv);                  // (its scratch goes at the end, once the copies below have waited for it)
-    b->yuv = std::move(saved);
-    RC_TRY(rc);
-    const uint8_t *d_c0 = s->d_yuv + (size_t)oh * dpy;
-    HIP_TRY(hipMemcpy2DAsync(out + off[0], oh > 1 ? host.pitch_y : ow, s->d_yuv, dpy, ow, oh, hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipMemcpy2DAsync(out + off[1], coh > 1 ? host.pitch_c : row_c, d_c0, dpc, row_c, coh, hipMemcpyDeviceToHost, b->stream));
-    if (!nv12)
-        HIP_TRY(hipMemcpy2DAsync(out + off[2], coh > 1 ? host.pitch_c : row_c, d_c0 + (size_t)coh * dpc, dpc, row_c, coh, hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    return H263MI_OK;
+    return render_planes_shaped(s, st, shape, out, host, off, ow, oh, row_c, coh, dpy, dpc);
 }
 
 int h263mi_render_rgba_pinned(const h263mi_state *cs, uint8_t strength, uint8_t *rgba_pinned)

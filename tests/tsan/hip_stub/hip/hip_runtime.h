@@ -1,7 +1,8 @@
 // A STUB of the HIP runtime for tests/tsan ONLY: just enough of the API for the host files of libh263mi (batch.cpp,
-// batch_staging.cpp, mixed_set.cpp, state.cpp, device_util.cpp) to compile with g++ -fsanitize=thread and run WITHOUT a GPU.
+// output_shape.cpp, batch_staging.cpp, mixed_set.cpp, state.cpp, device_util.cpp) to compile with g++ -fsanitize=thread and run WITHOUT a GPU.
 // "Device" and pinned memory are malloc; copies are memcpy executed at once on the calling thread (what a DMA engine would
-// read is read here, so ThreadSanitizer sees it); streams and events do nothing; kernel launches are stubs (stub_runtime.cpp).
+// read is read here, so ThreadSanitizer sees it); streams and events do nothing; kernel launches are stubs that can record what
+// was launched (stub_runtime.cpp).
 // Nothing here is a product path: the product is compiled by hipcc against the real runtime and has no CPU fallback.
 #pragma once
 

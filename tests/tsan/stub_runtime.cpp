@@ -1,19 +1,41 @@
 // tests/tsan: the stub HIP runtime (hip_stub/hip/hip_runtime.h) and stub kernel launchers.  Test infrastructure only.
+//
+// The launchers compute nothing.  They read what a launch would read first (per-stream words, pointer arrays, plane offsets,
+// span tables) and describe the launch in one text line.  A driver that calls stub_trace_into() gets those lines, and one line
+// per hipEventRecord / hipStreamWaitEvent: the host's decisions (which kernel, on which stream, from and to which memory, with
+// which arguments, behind which event) as text that two builds of the host sources can be compared by.  No address is ever
+// printed: a pointer is named by the allocation it lies in --
+//   out+<offset>            a buffer the driver registered as the caller's output (stub_trace_output)
+//   frames+<offset>         a frame store (an allocation a reconstruction launch was given as its frame sets)
+//   lib:<bytes>+<offset>    any other allocation, by its size
+//   null, unknown           no pointer; memory the runtime does not know
+// -- streams are `main` (the null stream) and `post` (a created one), events are numbered in the order they were created.
+// A launch is `<kernel> <stream>` and ` key=value` pairs of its arguments; a pair whose value is 0, a null pointer or no array
+// is left out.  Per-stream words are hexadecimal, `words=[..]` in the launch's arguments or `words=@<where>[..]` in device
+// memory; an array is `@<where it lies>[<elements>]`; a span table is `<where>#<entries>:<FNV-1a of its bytes>`; a float is its
+// bits.  k_frame's two halves are separated by ` | post`, the plane shape of a YUV instantiation follows ` | yuv`.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
 #include <mutex>
+#include <set>
+#include <string>
 
 #include "../../h263-rs_amd/csrc/kernels.h"
 
 namespace {
 std::mutex g_m;
 std::map<uintptr_t, size_t> g_allocs;            // "device" and pinned allocations: base -> size (hipMemGetAddressRange)
-std::atomic<long> g_events{0};                   // events created and not destroyed
+std::set<uintptr_t> g_outputs, g_frames;         // ... the ones that are caller output / a frame store (by base)
+std::map<hipEvent_t, int> g_event_no;            // live events: number by creation order
+int g_next_event = 0;
+std::map<hipStream_t, std::string> g_streams;    // live created streams: name
+std::atomic<std::string *> g_trace{nullptr};     // the recorder's sink; off unless a driver sets one
 thread_local int tl_device = 0;
 std::atomic<uint64_t> g_sink{0};                 // what the stub kernels "compute": keeps their reads alive
 
@@ -32,11 +54,87 @@ hipError_t release(void *p)
     {
         std::lock_guard<std::mutex> l(g_m);
         g_allocs.erase((uintptr_t)p);
+        g_outputs.erase((uintptr_t)p);
+        g_frames.erase((uintptr_t)p);
     }
     free(p);
     return hipSuccess;
 }
+// the allocation p lies in: its base (0: none) and size
+uintptr_t base_of(const void *p, size_t *size)
+{
+    auto it = g_allocs.upper_bound((uintptr_t)p);
+    if (it == g_allocs.begin()) return 0;
+    --it;
+    if ((uintptr_t)p >= it->first + it->second) return 0;
+    *size = it->second;
+    return it->first;
+}
+
+// ---- the recorder
+void appendf(std::string &s, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+void appendf(std::string &s, const char *fmt, ...)
+{
+    char buf[160];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    s += buf;
+}
+void emit(const std::string &line)
+{
+    std::lock_guard<std::mutex> l(g_m);
+    if (std::string *t = g_trace.load()) *t += line + "\n";
+}
+std::string where(const void *p)
+{
+    if (!p) return "null";
+    std::lock_guard<std::mutex> l(g_m);
+    size_t size = 0;
+    const uintptr_t base = base_of(p, &size);
+    if (!base) return "unknown";
+    std::string s;
+    const size_t off = (uintptr_t)p - base;
+    if (g_outputs.count(base)) appendf(s, "out+%zu", off);
+    else if (g_frames.count(base)) appendf(s, "frames+%zu", off);
+    else appendf(s, "lib:%zu+%zu", size, off);
+    return s;
+}
+std::string stream_name(hipStream_t s)
+{
+    if (!s) return "main";
+    std::lock_guard<std::mutex> l(g_m);
+    auto it = g_streams.find(s);
+    return it == g_streams.end() ? "unknown" : it->second;
+}
+std::string event_name(hipEvent_t e)
+{
+    std::lock_guard<std::mutex> l(g_m);
+    auto it = g_event_no.find(e);
+    return it == g_event_no.end() ? "e?" : "e" + std::to_string(it->second);
+}
 }  // namespace
+
+// ---- what a driver says to the recorder
+// every launch and event operation from now on appends a line to *sink (nullptr: off)
+void stub_trace_into(std::string *sink) { g_trace.store(sink); }
+// a heading line; the events made from here on are numbered from 0 again
+void stub_trace_section(const char *title)
+{
+    {
+        std::lock_guard<std::mutex> l(g_m);
+        g_next_event = 0;
+    }
+    emit(std::string("== ") + title);
+}
+// the allocation p lies in is the caller's output
+void stub_trace_output(const void *p)
+{
+    std::lock_guard<std::mutex> l(g_m);
+    size_t size = 0;
+    if (const uintptr_t base = base_of(p, &size)) g_outputs.insert(base);
+}
 
 hipError_t hipGetDeviceCount(int *count) { *count = 2; return hipSuccess; }
 hipError_t hipGetDevice(int *dev) { *dev = tl_device; return hipSuccess; }
@@ -55,12 +153,9 @@ hipError_t hipHostGetDevicePointer(void **dev, void *host, unsigned) { *dev = ho
 hipError_t hipMemGetAddressRange(hipDeviceptr_t *base, size_t *size, hipDeviceptr_t p)
 {
     std::lock_guard<std::mutex> l(g_m);
-    auto it = g_allocs.upper_bound((uintptr_t)p);
-    if (it == g_allocs.begin()) return hipErrorInvalidValue;
-    --it;
-    if ((uintptr_t)p >= it->first + it->second) return hipErrorInvalidValue;
-    *base = (void *)it->first;
-    *size = it->second;
+    const uintptr_t b = base_of(p, size);
+    if (!b) return hipErrorInvalidValue;
+    *base = (void *)b;
     return hipSuccess;
 }
 hipError_t hipMemcpy(void *dst, const void *src, size_t bytes, hipMemcpyKind) { memcpy(dst, src, bytes); return hipSuccess; }
@@ -72,26 +167,63 @@ hipError_t hipMemcpy2DAsync(void *dst, size_t dpitch, const void *src, size_t sp
 }
 hipError_t hipMemset(void *p, int v, size_t bytes) { memset(p, v, bytes); return hipSuccess; }
 hipError_t hipMemsetAsync(void *p, int v, size_t bytes, hipStream_t) { memset(p, v, bytes); return hipSuccess; }
-hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned) { *s = nullptr; return hipSuccess; }
-hipError_t hipStreamDestroy(hipStream_t) { return hipSuccess; }
+hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned)
+{
+    *s = (hipStream_t)malloc(1);
+    std::lock_guard<std::mutex> l(g_m);
+    g_streams[*s] = g_streams.empty() ? "post" : "post" + std::to_string(g_streams.size() + 1);
+    return hipSuccess;
+}
+hipError_t hipStreamDestroy(hipStream_t s)
+{
+    {
+        std::lock_guard<std::mutex> l(g_m);
+        g_streams.erase(s);
+    }
+    free(s);
+    return hipSuccess;
+}
 hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
-hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }
-hipError_t hipEventCreate(hipEvent_t *e) { *e = (hipEvent_t)malloc(1); g_events++; return hipSuccess; }
+hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned)
+{
+    emit("wait " + stream_name(s) + " " + event_name(e));
+    return hipSuccess;
+}
+hipError_t hipEventCreate(hipEvent_t *e)
+{
+    *e = (hipEvent_t)malloc(1);
+    std::lock_guard<std::mutex> l(g_m);
+    g_event_no[*e] = g_next_event++;
+    return hipSuccess;
+}
 hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) { return hipEventCreate(e); }
-hipError_t hipEventDestroy(hipEvent_t e) { if (e) g_events--; free(e); return hipSuccess; }
-hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return hipSuccess; }
+hipError_t hipEventDestroy(hipEvent_t e)
+{
+    {
+        std::lock_guard<std::mutex> l(g_m);
+        g_event_no.erase(e);
+    }
+    free(e);
+    return hipSuccess;
+}
+hipError_t hipEventRecord(hipEvent_t e, hipStream_t s)
+{
+    emit("record " + event_name(e) + " " + stream_name(s));
+    return hipSuccess;
+}
 hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
 hipError_t hipEventElapsedTime(float *ms, hipEvent_t, hipEvent_t) { *ms = 0.01f; return hipSuccess; }
 
-// what the library holds of the runtime right now: device and pinned blocks, events (tsan_driver: nothing may leak)
+// what the library holds of the runtime right now: device and pinned blocks, events, streams (the drivers: nothing may leak)
 long stub_live_allocations()
 {
     std::lock_guard<std::mutex> l(g_m);
-    return (long)g_allocs.size() + g_events.load();
+    return (long)(g_allocs.size() + g_event_no.size() + g_streams.size());
 }
 
 // ---- the "kernels": they read what a launch would read first -- the per-stream words, bases and the sparse-record index the
-// host threads have just written and the caller has just copied -- so that ThreadSanitizer sees those reads
+// host threads have just written and the caller has just copied, the pointer, offset and span arrays of a shaped rendering --
+// so that ThreadSanitizer and AddressSanitizer see those reads, and describe the launch to the recorder
 namespace h263mi {
 
 static void touch_recon(const ReconArgs &a)
@@ -99,30 +231,164 @@ static void touch_recon(const ReconArgs &a)
     uint64_t s = 0;
     if (a.coeff_base)
         for (uint32_t i = 0; i < a.n_pictures; i++) s += a.coeff_base[i];
-    if (a.stream_state)
-        for (uint32_t i = 0; i < a.n_pictures; i++) s += a.stream_state[i];
     if (a.mb_group_index)
         for (size_t i = 0; i < (size_t)a.n_pictures * a.groups_per_picture; i++) s += a.mb_group_index[i];
     g_sink.fetch_add(s, std::memory_order_relaxed);
+    std::lock_guard<std::mutex> l(g_m);
+    size_t size = 0;
+    if (const uintptr_t base = base_of(a.frame_set[0], &size)) g_frames.insert(base);
 }
-static void touch_words(const uint32_t *words, uint32_t n)
+// A launch's line is ` key=value` pairs; a pair whose value is 0, a null pointer or no array is left out.
+static void put(std::string &s, const char *key, uint64_t v)
 {
-    uint64_t s = 0;
-    for (uint32_t i = 0; words && i < n; i++) s += words[i];
-    g_sink.fetch_add(s, std::memory_order_relaxed);
+    if (v) appendf(s, " %s=%llu", key, (unsigned long long)v);
 }
-hipError_t launch_recon(const ReconArgs &a, hipStream_t, const uint32_t *words) { touch_recon(a); touch_words(words, a.n_pictures); return hipSuccess; }
-hipError_t launch_frame(const ReconArgs &a, const PostArgs &p, hipStream_t, bool, const uint32_t *words)
+static void put_ptr(std::string &s, const char *key, const void *p)
+{
+    if (p) s += std::string(" ") + key + "=" + where(p);
+}
+static void put_float(std::string &s, const char *key, float f)        // (its bits: no rounding on the way to text)
+{
+    uint32_t u;
+    memcpy(&u, &f, sizeof u);
+    appendf(s, " %s=%08x", key, u);
+}
+// n elements at p, each through `one`: @<where the array lies>[<elements>]
+template <typename T, typename F>
+static void put_array(std::string &s, const char *key, const T *p, size_t n, F one)
+{
+    if (!p) return;
+    s += std::string(" ") + key + "=@" + where(p) + "[";
+    for (size_t i = 0; i < n; i++) s += (i ? " " : "") + one(p[i]);
+    s += "]";
+}
+static std::string hex_word(uint32_t w)
+{
+    std::string s;
+    appendf(s, "%x", w);
+    return s;
+}
+// the per-stream words of a launch: in its arguments (`inline_words`, a host array) or in device memory
+static void put_words(std::string &s, const uint32_t *inline_words, const uint32_t *device_words, uint32_t n)
+{
+    if (!inline_words) return put_array(s, "words", device_words, n, hex_word);
+    s += " words=[";
+    for (uint32_t i = 0; i < n; i++) s += (i ? " " : "") + hex_word(inline_words[i]);
+    s += "]";
+}
+// a span table: where it lies, its entries, FNV-1a over its bytes
+static void put_spans(std::string &s, const char *key, const ResizeSpan *p, uint32_t n)
+{
+    uint64_t h = 0xcbf29ce484222325ull;
+    const uint8_t *bytes = reinterpret_cast<const uint8_t *>(p);
+    for (size_t i = 0; i < (size_t)n * sizeof(ResizeSpan); i++) h = (h ^ bytes[i]) * 0x100000001b3ull;
+    appendf(s, " %s=%s#%u:%016llx", key, where(p).c_str(), n, (unsigned long long)h);
+}
+static void put_recon(std::string &s, const ReconArgs &a, const uint32_t *words)
 {
     touch_recon(a);
-    touch_words(words, a.n_pictures);
-    if (p.stream_state) g_sink.fetch_add(p.stream_state[0], std::memory_order_relaxed);
+    put(s, "n", a.n_pictures);
+    put(s, "has_ref", a.has_ref);
+    put_ptr(s, "ref", a.ref);
+    put_ptr(s, "cur", a.cur);
+    put_words(s, words, a.stream_state, a.n_pictures);
+}
+static void put_post(std::string &s, const PostArgs &p, const uint32_t *words, bool with_words)
+{
+    put(s, "n", p.n_pictures);
+    put(s, "strength", p.strength);
+    put(s, "luma_only", p.luma_only);
+    put_ptr(s, "frames", p.frames);
+    put_ptr(s, "rgba", p.rgba);
+    put_ptr(s, "planes", p.planes_out);
+    put(s, "scale", p.rgba_scale);
+    put(s, "pitch", p.rgba_pitch);
+    if (with_words) put_words(s, words, p.stream_state, p.n_pictures);
+    put_array(s, "ptrs", p.rgba_ptrs, p.n_pictures, [](uint8_t *q) { return where(q); });
+}
+static void put_yuv(std::string &s, const YuvOut &y, uint32_t n)
+{
+    s += " | yuv";
+    put(s, "format", y.format);
+    put(s, "wide", y.wide);
+    put(s, "pitch_y", y.pitch_y);
+    put(s, "pitch_c", y.pitch_c);
+    put_array(s, "offsets", y.offsets, (size_t)3 * n, [](uint64_t o) { return std::to_string(o); });
+}
+hipError_t launch_recon(const ReconArgs &a, hipStream_t on, const uint32_t *words)
+{
+    std::string s = "recon " + stream_name(on);
+    put_recon(s, a, words);
+    emit(s);
     return hipSuccess;
 }
-hipError_t launch_post(const PostArgs &p, hipStream_t, const uint32_t *words)
+static void put_frame(std::string &s, const ReconArgs &a, const PostArgs &p, bool descending, const uint32_t *words)
 {
-    touch_words(words, p.n_pictures);
-    if (p.stream_state) g_sink.fetch_add(p.stream_state[0], std::memory_order_relaxed);
+    put(s, "descending", descending ? 1u : 0u);
+    put_recon(s, a, words);
+    s += " | post";
+    put_post(s, p, words, false);
+}
+hipError_t launch_frame(const ReconArgs &a, const PostArgs &p, hipStream_t on, bool descending, const uint32_t *words)
+{
+    std::string s = "frame " + stream_name(on);
+    put_frame(s, a, p, descending, words);
+    emit(s);
+    return hipSuccess;
+}
+hipError_t launch_post(const PostArgs &p, hipStream_t on, const uint32_t *words)
+{
+    std::string s = "post " + stream_name(on);
+    put_post(s, p, words, true);
+    emit(s);
+    return hipSuccess;
+}
+hipError_t launch_post_yuv(const PostArgs &p, const YuvOut &yuv, hipStream_t on, const uint32_t *words)
+{
+    std::string s = "post_yuv " + stream_name(on);
+    put_post(s, p, words, true);
+    put_yuv(s, yuv, p.n_pictures);
+    emit(s);
+    return hipSuccess;
+}
+hipError_t launch_frame_yuv(const ReconArgs &a, const PostArgs &p, const YuvOut &yuv, hipStream_t on, bool descending, const uint32_t *words)
+{
+    std::string s = "frame_yuv " + stream_name(on);
+    put_frame(s, a, p, descending, words);
+    put_yuv(s, yuv, p.n_pictures);
+    emit(s);
+    return hipSuccess;
+}
+hipError_t launch_rgba_resize(const ResizeArgs &a, hipStream_t on)
+{
+    std::string s = "rgba_resize " + stream_name(on);
+    put(s, "n", a.n_pictures);
+    put_ptr(s, "src", a.src);
+    put(s, "w", a.w), put(s, "h", a.h), put(s, "ow", a.ow), put(s, "oh", a.oh);
+    put(s, "pitch", a.pitch);
+    put(s, "bands", a.bands), put(s, "chunk", a.chunk);
+    put(s, "d", a.d), put_float(s, "inv_d", a.inv_d);
+    put_spans(s, "cols", a.cols, a.ow), put_spans(s, "rows", a.rows, a.oh);
+    put_array(s, "dst", a.dst, a.n_pictures, [](uint8_t *q) { return where(q); });
+    emit(s);
+    return hipSuccess;
+}
+hipError_t launch_plane_resize(const PlaneResizeArgs &a, hipStream_t on)
+{
+    std::string s = "plane_resize " + stream_name(on);
+    put(s, "n", a.n_pictures);
+    put_ptr(s, "src", a.src);
+    put(s, "w", a.w), put(s, "h", a.h), put(s, "cw", a.cw), put(s, "ch", a.ch);
+    put(s, "ow", a.ow), put(s, "oh", a.oh), put(s, "cow", a.cow), put(s, "coh", a.coh);
+    put(s, "pitch_y", a.pitch_y), put(s, "pitch_c", a.pitch_c);
+    put(s, "nv12", a.nv12), put(s, "wide", a.wide);
+    put(s, "d_y", a.d_y), put(s, "d_c", a.d_c), put_float(s, "inv_d_y", a.inv_d_y), put_float(s, "inv_d_c", a.inv_d_c);
+    put(s, "bands", a.bands), put(s, "chunk", a.chunk), put(s, "segs_y", a.segs_y);
+    put_spans(s, "cols_y", a.cols_y, a.ow), put_spans(s, "rows_y", a.rows_y, a.oh);
+    put_spans(s, "cols_c", a.cols_c, a.cow), put_spans(s, "rows_c", a.rows_c, a.coh);
+    put_array(s, "dst", a.dst, a.n_pictures,
+              [](const PlaneDst &d) { return "(" + where(d.p[0]) + " " + where(d.p[1]) + " " + where(d.p[2]) + ")"; });
+    emit(s);
     return hipSuccess;
 }
 hipError_t launch_synth_headers(const SynthArgs &, hipStream_t) { return hipSuccess; }

@@ -1,6 +1,6 @@
 // tests/tsan/tsan_driver.cpp -- the host pipeline of libh263mi under ThreadSanitizer.
 //
-// Built with g++ -fsanitize=thread from the PRODUCT's host sources (worker_pool.cpp, batch.cpp, batch_staging.cpp,
+// Built with g++ -fsanitize=thread from the PRODUCT's host sources (worker_pool.cpp, batch.cpp, output_shape.cpp, batch_staging.cpp,
 // mixed_set.cpp, state.cpp, device_util.cpp, host/bitstream.cpp) against a stub of the HIP runtime (hip_stub/, plain malloc
 // for device and pinned memory, stub kernel launchers): what runs here is the real WorkerPool (spin-then-park, generation
 // word), the real stream-affinity / stealing deal, the real parser writing records, events, block offsets and the group index
@@ -19,7 +19,9 @@
 //   * the packed (H263MI_DIRECT_WORDS=0) transport, and workers that never park (H263MI_SPIN_US = 50 ms, no quota, at most 6
 //     threads: every hand-over goes through the generation word alone, never through the mutex): further runs of the test.
 //   * a failure injected at every HIP call of h263mi_submit_picture[_events], h263mi_decode_next_picture, a 2-stream
-//     h263mi_batch_submit_host and h263mi_batch_decode_next_pictures_ps: the last picture stays as it was; and of a 3-stream,
+//     h263mi_batch_submit_host and h263mi_batch_decode_next_pictures_ps, and of the shaped h263mi_render_* entries of a state: the
+//     last picture stays as it was; of h263mi_batch_set_rgba_resize, _set_yuv_layout and _set_yuv_resize: the shape that was in
+//     force stays in force (the launch trace of a rendering, stub_runtime.cpp, is what it was); and of a 3-stream,
 //     two-size h263mi_mixed_decode_next_pictures_ps in which a stream moves class; every pinned block, device block and event
 //     the objects held is given back (the stub runtime counts them);
 //   * the order in which h263mi_submit_picture[_events] names what is wrong with a call, one crafted case per rule.
@@ -38,12 +40,15 @@
 #include <initializer_list>
 #include <memory>
 #include <random>
+#include <string>
 #include <thread>
 #include <vector>
 
 #include "../../include/h263mi.h"
 
 long stub_live_allocations();                                        // stub_runtime.cpp
+void stub_trace_into(std::string *sink);
+void stub_trace_output(const void *p);
 
 static std::vector<std::vector<std::vector<uint8_t>>> g_corpus;      // [stream][frame]
 static uint16_t g_w, g_h;
@@ -545,7 +550,7 @@ struct SweepSubject {
     virtual int call() = 0;
     virtual std::vector<uint64_t> view() = 0;
 };
-static void fault_sweep(const char *name, bool may_absorb, const std::function<SweepSubject *()> &make)
+static void fault_sweep(const char *name, bool may_absorb, const std::function<SweepSubject *()> &make, int min_failures = 3)
 {
     int failures = 0;
     for (int nth = 1; nth < 500; nth++) {
@@ -556,7 +561,7 @@ static void fault_sweep(const char *name, bool may_absorb, const std::function<S
         const bool fired = h263mi_debug_fail_nth_hip_call(0) <= 0;
         if (rc == H263MI_OK && !fired) {
             fprintf(stderr, "  fault sweep %s: %d failures\n", name, failures);
-            CHECK(failures >= 3);
+            CHECK(failures >= min_failures);
             return;
         }
         if (rc == H263MI_OK) {
@@ -720,6 +725,105 @@ static void drive_fault_sweeps()
         }
     };
     fault_sweep("h263mi_batch_decode_next_pictures_ps (2 streams)", false, [] { return new BatchBitstream(); });
+    // the shaped renderings of a state: each makes a shape (device offsets, or a scratch and span tables) and grows the state's
+    // own scratch on the way
+    static std::vector<uint8_t> host_out((size_t)1 << 18);
+    fault_sweep("h263mi_render_rgba_layout", false, [] {
+        return new State([](h263mi_state *st) {
+            h263mi_rgba_layout l{};
+            l.scale_log2 = 1;
+            l.row_pitch = 512;
+            return h263mi_render_rgba_layout(st, 5, &l, host_out.data());
+        }, false);
+    });
+    fault_sweep("h263mi_render_rgba_resize", false, [] {
+        return new State([](h263mi_state *st) {
+            h263mi_rgba_resize r{};
+            r.out_width = 100, r.out_height = 60, r.row_pitch = 512;
+            return h263mi_render_rgba_resize(st, 5, &r, host_out.data());
+        }, false);
+    });
+    fault_sweep("h263mi_render_yuv", false, [] {
+        return new State([](h263mi_state *st) {
+            h263mi_yuv_layout l{};
+            l.format = H263MI_YUV_NV12;
+            l.pitch_y = l.pitch_c = 200;
+            return h263mi_render_yuv(st, 5, &l, host_out.data());
+        }, false);
+    });
+    fault_sweep("h263mi_render_yuv_resize", false, [] {
+        return new State([](h263mi_state *st) {
+            h263mi_yuv_resize r{};
+            r.out_width = 100, r.out_height = 60, r.format = H263MI_YUV_I420;
+            return h263mi_render_yuv_resize(st, 5, &r, host_out.data());
+        }, false);
+    });
+    // the setters of a batch's output shape, each over a batch that has another shape of that kind in force: a setter that fails
+    // leaves it in force -- one rendering (RGBA and planes) launches what it launched before
+    struct BatchShape : Batch {
+        void *d_out = nullptr;
+        std::function<int(h263mi_batch *)> setter;
+        explicit BatchShape(std::function<int(h263mi_batch *)> f) : setter(f)
+        {
+            CHECK(h263mi_device_malloc(0, (size_t)1 << 20, &d_out) == H263MI_OK);
+            stub_trace_output(d_out);
+            h263mi_rgba_layout l{};
+            l.scale_log2 = 1;
+            l.row_pitch = 512;
+            CHECK(h263mi_batch_set_rgba_layout(b, &l) == H263MI_OK);
+            h263mi_yuv_layout y{};
+            y.format = H263MI_YUV_NV12;
+            y.pitch_y = y.pitch_c = 256;
+            CHECK(h263mi_batch_set_yuv_layout(b, &y) == H263MI_OK);
+        }
+        ~BatchShape() { CHECK(h263mi_device_free(0, d_out) == H263MI_OK); }
+        int call() override { return setter(b); }
+        std::vector<uint64_t> view() override
+        {
+            std::string trace;
+            stub_trace_into(&trace);
+            CHECK(h263mi_batch_render_rgba_ps(b, 5, nullptr, (uint8_t *)d_out, (uint8_t *)d_out + ((size_t)1 << 19)) == H263MI_OK);
+            stub_trace_into(nullptr);
+            // what the rendering launched, without what moves on from one rendering to the next: the event lines and the slot of
+            // an upload ring that an array lies in ("@lib:<bytes>+<offset>[")
+            std::vector<uint64_t> v;
+            for (size_t at = 0; at < trace.size();) {
+                const size_t end = trace.find('\n', at);
+                const std::string line = trace.substr(at, end - at);
+                at = end + 1;
+                if (line.compare(0, 7, "record ") == 0 || line.compare(0, 5, "wait ") == 0) continue;
+                for (size_t k = 0; k < line.size(); k++) {
+                    if (line[k] == '@') k = line.find('[', k);
+                    v.push_back((uint8_t)line[k]);
+                }
+                v.push_back('\n');
+            }
+            CHECK(v.size() > 100);
+            return v;
+        }
+    };
+    fault_sweep("h263mi_batch_set_rgba_resize", false, [] {
+        return new BatchShape([](h263mi_batch *b) {
+            h263mi_rgba_resize r{};
+            r.out_width = 100, r.out_height = 60;
+            return h263mi_batch_set_rgba_resize(b, &r);
+        });
+    });
+    fault_sweep("h263mi_batch_set_yuv_layout", false, [] {
+        return new BatchShape([](h263mi_batch *b) {
+            h263mi_yuv_layout l{};
+            l.format = H263MI_YUV_I420;
+            l.pitch_y = 200, l.pitch_c = 100;
+            return h263mi_batch_set_yuv_layout(b, &l);
+        });
+    }, /*min_failures=*/2);              // (an allocation and a copy)
+    fault_sweep("h263mi_batch_set_yuv_resize", false, [] {
+        return new BatchShape([](h263mi_batch *b) {
+            h263mi_yuv_resize r{};
+            r.out_width = 100, r.out_height = 60, r.format = H263MI_YUV_NV12;
+            return h263mi_batch_set_yuv_resize(b, &r);
+        });
+    });
     if (!g_corpus2.empty())
         for (bool pipeline : {false, true}) mixed_fault_sweep(pipeline);
     // every pinned and device block and every event of the objects above went with them
