@@ -125,6 +125,19 @@ int h263mi_batch::launch_resize(const RgbaLayout::Resize &rz, const std::vector<
     a.d = L.width * L.height;
     a.inv_d = 1.0f / (float)a.d;
     a.n_pictures = n;
+    if (rz.tensor.on) {                        // the same resize, ending in planar float stores (k_tensor_resize)
+        TensorArgs ta{};
+        ta.r = a;
+        for (int c = 0; c < 3; c++) ta.scale[c] = rz.tensor.scale[c], ta.bias[c] = rz.tensor.bias[c];
+        ta.dtype = rz.tensor.dtype;
+        ta.bgr = rz.tensor.bgr;
+        ta.stride_c = rz.tensor.stride_c;
+        ta.stride_h = rz.tensor.stride_h;
+        if (!launch_tensor_resize) return H263MI_ERR_HIP;  // (kernels.h: only a stub runtime lacks it)
+        RC_TRY(time_begin(3, on));
+        HIP_TRY(launch_tensor_resize(ta, on));
+        return H263MI_OK;
+    }
     if (!launch_rgba_resize) return H263MI_ERR_HIP;        // (kernels.h: only a stub runtime lacks it)
     RC_TRY(time_begin(3, on));
     HIP_TRY(launch_rgba_resize(a, on));
@@ -783,6 +796,8 @@ static int bound_device_arrays(const h263mi_batch *b, const h263mi_mb_record *d_
 // registered host memory, another runtime's memory) is taken as it is.  Checked batches only.
 static int bound_output_buffers(const h263mi_batch *b, const uint8_t *d_rgba, const uint8_t *d_deblocked)
 {
+    // (a tensor's base holds whole elements, on a trusted batch too: the kernel stores them as such)
+    if (d_rgba && (uintptr_t)d_rgba % b->layout.base_align()) return H263MI_ERR_INVALID_ARGUMENT;
     if (b->trusted_arrays) return H263MI_OK;
     const size_t rgba_bytes = b->layout.bytes;      // (n * w*h*4 unless the batch has an output layout)
     // (n tightly packed I420 pictures unless the batch has a YUV layout or resize)
@@ -942,6 +957,16 @@ int h263mi_batch_set_rgba_resize(h263mi_batch *b, const h263mi_rgba_resize *r)
     h263mi_batch::RgbaLayout lay;
     RC_TRY(make_output_shape(b->device, b->n, b->L.width, b->L.height, r, lay));
     DeviceGuard g(b->device);
+    b->layout = std::move(lay);
+    return H263MI_OK;
+}
+
+int h263mi_batch_set_tensor_output(h263mi_batch *b, const h263mi_tensor_out *t)
+{
+    if (!b) return H263MI_ERR_INVALID_ARGUMENT;
+    h263mi_batch::RgbaLayout lay;
+    RC_TRY(make_tensor_shape(b->device, b->n, b->L.width, b->L.height, t, lay));
+    DeviceGuard g(b->device);                  // (a shape it replaces frees its scratch, unless a pending rendering holds it)
     b->layout = std::move(lay);
     return H263MI_OK;
 }

@@ -66,7 +66,7 @@ struct h263mi_batch {
             return true;
         }
     };
-    // The shapes in force (output_shape.h): of the RGBA (h263mi_batch_set_rgba_layout, _set_rgba_resize) and of the deblocked
+    // The shapes in force (output_shape.h): of the RGBA (h263mi_batch_set_rgba_layout, _set_rgba_resize, _set_tensor_output) and of the deblocked
     // planes (h263mi_batch_set_yuv_layout, _set_yuv_resize).  A rendering is told its shapes (render), these by default.
     typedef h263mi::OutLayout OutLayout;
     typedef h263mi::RgbaLayout RgbaLayout;
@@ -78,7 +78,7 @@ struct h263mi_batch {
         YuvLayout yuv;                         // the plane layout in force when the rendering was requested
         Strengths strength;
         OutLayout out;                         // the layout in force when the rendering was requested
-        RgbaLayout::Resize resize;             // ... or the resize (then `rgba` is its scratch)
+        RgbaLayout::Resize resize;             // ... or the resize, with the tensor it may end in (then `rgba` is its scratch)
         uint8_t *const *resize_dst = nullptr;  // DEVICE array: stream s's resized picture, nullptr = none
         const h263mi::PlaneDst *plane_dst = nullptr;   // yuv.resize: DEVICE array of the streams' planes (then `planes` is its scratch)
         bool plane_wide = false;               // ... which all allow word stores
@@ -217,7 +217,8 @@ struct h263mi_batch {
     // its offset, nullptr where sets[s] < 0 -- uploaded on `on`
     int resize_dst(const RgbaLayout &lay, const std::vector<int8_t> &sets, uint8_t *d_rgba, uint8_t *const *host_ptrs, hipStream_t on,
                    uint8_t *const **d_out);
-    // k_rgba_resize of `rz` into `d_dst` (resize_dst), on `on`; nothing when no stream has a set (sets[s] < 0 for all)
+    // k_rgba_resize of `rz` -- or, where it ends in a tensor (rz.tensor), k_tensor_resize -- into `d_dst` (resize_dst), on `on`;
+    // nothing when no stream has a set (sets[s] < 0 for all)
     int launch_resize(const RgbaLayout::Resize &rz, const std::vector<int8_t> &sets, uint8_t *const *d_dst, hipStream_t on);
     // a YUV resize `rz` of planes that go to d_planes: the DEVICE array of k_plane_resize's destinations -- stream s's planes at
     // d_planes + its offsets, null where sets[s] < 0 -- uploaded on `on`; *wide: word stores are possible

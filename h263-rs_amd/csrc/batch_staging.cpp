@@ -342,6 +342,8 @@ static int batch_decode_next_pictures(h263mi_batch *b, uint32_t decoder_options,
                                       bool from_header, uint8_t *d_rgba, uint8_t *d_deblocked)
 {
     if (!b || !data || !len) return H263MI_ERR_INVALID_ARGUMENT;
+    // (a tensor's base holds whole elements: refused before a bit is parsed)
+    if (d_rgba && (uintptr_t)d_rgba % b->layout.base_align()) return H263MI_ERR_INVALID_ARGUMENT;
     const uint32_t n = b->n;
     // data[i] == NULL: in the _ex form (stream_rc given) the stream has no picture in this call; in the plain form every
     // stream decodes, and NULL with length 0 is an empty reader (the parser answers with its end-of-stream error, as it does

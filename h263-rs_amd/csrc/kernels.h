@@ -7,6 +7,7 @@
 #include "digest_kernel.inl"
 #include "plane_resize_kernel.inl"
 #include "resize_kernel.inl"
+#include "tensor_resize_kernel.inl"
 
 namespace h263mi {
 
@@ -49,6 +50,9 @@ hipError_t launch_frame_yuv(const ReconArgs &rargs, const PostArgs &pargs, const
 // objects are also linked, in the CPU suite's ThreadSanitizer build (tests/tsan), against a stub runtime that has no resize
 // launcher.  The library always defines it (kernels.hip); h263mi_batch::launch_resize refuses to run without it.
 hipError_t launch_rgba_resize(const ResizeArgs &args, hipStream_t stream) __attribute__((weak));
+// k_tensor_resize over args.r.n_pictures pictures (tensor_resize_kernel.inl; bands and chunk are set here): k_rgba_resize's launch
+// shape, planar float stores.  Weak like launch_rgba_resize; h263mi_batch::launch_resize refuses to write a tensor without it.
+hipError_t launch_tensor_resize(const TensorArgs &args, hipStream_t stream) __attribute__((weak));
 // k_plane_resize over args.n_pictures pictures (plane_resize_kernel.inl; bands, chunk and segs_y are set here): the luma and
 // chroma planes of every picture in ONE launch.  Weak like launch_rgba_resize; h263mi_batch::launch_plane_resize refuses to run
 // without it.

@@ -7,6 +7,7 @@
 #include "recon_kernel.inl"
 #include "plane_resize_kernel.inl"
 #include "resize_kernel.inl"
+#include "tensor_resize_kernel.inl"
 #include "synth.inl"
 
 namespace h263mi {
@@ -770,6 +771,33 @@ hipError_t launch_rgba_resize(const ResizeArgs &args, hipStream_t stream)
     a.chunk = (a.bands + 7) / 8;
     const dim3 grid(a.chunk * 8, a.n_pictures, (a.ow + 63) / 64);
     hipLaunchKernelGGL(k_rgba_resize, grid, dim3(64), 0, stream, a);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
+// k_tensor_resize: the area average of k_rgba_resize, normalised and stored as three planes of binary32, binary16 or bfloat16
+// (tensor_resize_kernel.inl).  The launch shape is k_rgba_resize's: one wave per workgroup, no barrier, blockIdx.y = picture,
+// blockIdx.z = segment of 64 output columns, blockIdx.x = band of RESIZE_ROWS output rows in XCD order.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_tensor_resize(TensorArgs a)
+{
+    __shared__ __attribute__((aligned(16))) ResizeLds lds;
+    const uint32_t band = (blockIdx.x & 7u) * a.r.chunk + (blockIdx.x >> 3);
+    if (band >= a.r.bands) return;
+    const int lane = threadIdx.x & 63;
+    TensorLane t;
+    tensor_resize_item(a, lds, band, blockIdx.z, blockIdx.y, [&](auto f) { f(lane, t); });
+}
+
+hipError_t launch_tensor_resize(const TensorArgs &args, hipStream_t stream)
+{
+    if (!args.r.n_pictures) return hipSuccess;
+    if (args.r.n_pictures > 65535 || args.dtype > TENSOR_BF16) return hipErrorInvalidValue;
+    TensorArgs a = args;
+    a.r.bands = (a.r.oh + RESIZE_ROWS - 1) / RESIZE_ROWS;
+    a.r.chunk = (a.r.bands + 7) / 8;
+    const dim3 grid(a.r.chunk * 8, a.r.n_pictures, (a.r.ow + 63) / 64);
+    hipLaunchKernelGGL(k_tensor_resize, grid, dim3(64), 0, stream, a);
     return hipGetLastError();
 }
 

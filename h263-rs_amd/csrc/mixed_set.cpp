@@ -62,17 +62,32 @@ struct h263mi_mixed {
     // h263mi_mixed_set_rgba_resize: every stream rendered as W' x H' (offsets NULL), or full size (resized false)
     bool resized = false;
     h263mi_rgba_resize resize{};
+    // h263mi_mixed_set_tensor_output: every stream written as the 3 x H' x W' tensor (stride_n 0) -- in the place of a resize
+    bool tensored = false;
+    h263mi_tensor_out tensor{};
+    uint64_t tensor_bytes = 0;                  // h263mi_tensor_extent(1, &tensor)
     ~h263mi_mixed()
     {
         pool.reset();                           // the host threads first
         for (SizeClass &c : classes) delete c.b;
     }
-    // a class's frame store, and the scratch of its full-size pictures while a resize that is not a layout is in force
-    static uint64_t class_bytes(uint32_t w, uint32_t h, uint32_t slots, const h263mi_rgba_resize *rz)
+    // a class's frame store, and the scratch of its full-size pictures while a resize that is not a layout is in force, or a
+    // tensor (which always has one)
+    static uint64_t class_bytes(uint32_t w, uint32_t h, uint32_t slots, const h263mi_rgba_resize *rz, const h263mi_tensor_out *t = nullptr)
     {
-        return 2ull * slots * make_layout(w, h).frame_bytes + (rz ? resize_scratch_bytes(w, h, slots, *rz) : 0);
+        return 2ull * slots * make_layout(w, h).frame_bytes +
+               (t ? tensor_scratch_bytes(w, h, slots, *t) : (rz ? resize_scratch_bytes(w, h, slots, *rz) : 0));
     }
-    uint64_t slots_bytes(uint32_t w, uint32_t h, uint32_t slots) const { return class_bytes(w, h, slots, resized ? &resize : nullptr); }
+    uint64_t slots_bytes(uint32_t w, uint32_t h, uint32_t slots) const
+    {
+        return class_bytes(w, h, slots, resized ? &resize : nullptr, tensored ? &tensor : nullptr);
+    }
+    // the output shape in force for a class of `slots` slots of w x h (each slot placed by its own pointer)
+    int class_shape(uint32_t slots, uint32_t w, uint32_t h, h263mi_batch::RgbaLayout &out) const
+    {
+        if (tensored) return make_tensor_shape(cfg.device_id, slots, w, h, &tensor, out);
+        return make_output_shape(cfg.device_id, slots, w, h, resized ? &resize : nullptr, out);
+    }
     uint64_t store_bytes() const
     {
         uint64_t sum = 0;
@@ -83,6 +98,7 @@ struct h263mi_mixed {
     // what stream s's buffer must hold for a picture of w x h
     uint64_t rgba_need(uint32_t w, uint32_t h) const
     {
+        if (tensored) return tensor_bytes;
         if (!resized) return (uint64_t)w * h * 4;
         const uint64_t row = 4ull * resize.out_width, pitch = resize.row_pitch ? resize.row_pitch : row;
         return (uint64_t)(resize.out_height - 1) * pitch + row;
@@ -135,7 +151,7 @@ struct h263mi_mixed {
         h263mi_batch *nb = nullptr;
         RC_TRY(batch_create(slots, c.w, c.h, &cfg, &nb));
         {
-            const int rc = make_output_shape(cfg.device_id, slots, c.w, c.h, resized ? &resize : nullptr, nb->layout);
+            const int rc = class_shape(slots, c.w, c.h, nb->layout);
             if (rc != H263MI_OK) {
                 delete nb;
                 return rc;
@@ -262,6 +278,32 @@ int h263mi_mixed_set_rgba_resize(h263mi_mixed *m, const h263mi_rgba_resize *r)
         if (m->classes[k].b) m->classes[k].b->layout = std::move(shapes[k]);
     m->resized = r != nullptr;
     m->resize = r ? *r : h263mi_rgba_resize{};
+    m->tensored = false;
+    return H263MI_OK;
+}
+
+int h263mi_mixed_set_tensor_output(h263mi_mixed *m, const h263mi_tensor_out *t)
+{
+    if (!m || (t && t->stride_n)) return H263MI_ERR_INVALID_ARGUMENT;
+    uint64_t one = 0;
+    if (t) RC_TRY(tensor_extent(1, t, &one));
+    DeviceGuard g(m->cfg.device_id);
+    if (!g.ok) return H263MI_ERR_NO_DEVICE;
+    // every class's new shape first (the scratches they need count against the limit), then all of them at once
+    uint64_t total = 0;
+    for (const h263mi_mixed::SizeClass &c : m->classes)
+        if (c.b) total += h263mi_mixed::class_bytes(c.w, c.h, c.b->n, nullptr, t);
+    if (m->limit_bytes && total > m->limit_bytes) return H263MI_ERR_OUT_OF_MEMORY;
+    std::vector<h263mi_batch::RgbaLayout> shapes(m->classes.size());
+    for (size_t k = 0; k < m->classes.size(); k++)
+        if (m->classes[k].b) RC_TRY(make_tensor_shape(m->cfg.device_id, m->classes[k].b->n, m->classes[k].w, m->classes[k].h, t, shapes[k]));
+    for (size_t k = 0; k < m->classes.size(); k++)
+        if (m->classes[k].b) m->classes[k].b->layout = std::move(shapes[k]);
+    m->tensored = t != nullptr;
+    m->tensor = t ? *t : h263mi_tensor_out{};
+    m->tensor_bytes = one;
+    m->resized = false;
+    m->resize = h263mi_rgba_resize{};
     return H263MI_OK;
 }
 
@@ -320,6 +362,9 @@ int h263mi_mixed_decode_next_pictures_ps(h263mi_mixed *m, uint32_t decoder_optio
         if (rc == H263MI_OK && any_inter && !has_ref) rc = H263MI_ERR_UNCODED_IFRAME_BLOCKS;          // gather.rs:149
         if (rc == H263MI_OK && any_inter && !same) rc = H263MI_ERR_PICTURE_FORMAT_INVALID;           // (see the head of this section)
         if (rc == H263MI_OK && d_rgba && d_rgba[i] && rgba_capacity[i] < m->rgba_need(w, h)) rc = H263MI_ERR_INVALID_ARGUMENT;
+        // (a tensor's base holds whole elements)
+        if (rc == H263MI_OK && d_rgba && d_rgba[i] && m->tensored && (uintptr_t)d_rgba[i] % (m->tensor.dtype == H263MI_TENSOR_F32 ? 4u : 2u))
+            rc = H263MI_ERR_INVALID_ARGUMENT;
         if (rc == H263MI_OK) {
             want[i] = Want{w, h};
             target[i] = same ? c_old : -2;       // -2: joins a class of that size (existing or new), resolved below

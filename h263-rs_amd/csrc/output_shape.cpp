@@ -3,6 +3,7 @@
 #include "output_shape.h"
 
 #include <algorithm>
+#include <cmath>
 #include <new>
 
 namespace h263mi {
@@ -224,6 +225,46 @@ int yuv_resize_extent(uint32_t n_streams, const h263mi_yuv_resize *r, uint64_t *
     return yuv_layout_extent(n_streams, r->out_width, r->out_height, &lay, bytes, shape, offsets);
 }
 
+// h263mi_tensor_extent (include/h263mi.h has the rules); every sum in 128 bits, so nothing wraps
+int tensor_extent(uint32_t n_streams, const h263mi_tensor_out *t, uint64_t *bytes, RgbaLayout::Resize::Tensor *out, uint64_t *stride_n_out)
+{
+    typedef unsigned __int128 u128;
+    if (!t || !n_streams || !t->out_width || !t->out_height) return H263MI_ERR_INVALID_ARGUMENT;
+    if (t->dtype > H263MI_TENSOR_BF16 || t->bgr > 1 || t->reserved[0] || t->reserved[1]) return H263MI_ERR_INVALID_ARGUMENT;
+    for (int c = 0; c < 3; c++)
+        if (!std::isfinite(t->scale[c]) || !std::isfinite(t->bias[c])) return H263MI_ERR_INVALID_ARGUMENT;
+    const uint64_t elt = t->dtype == H263MI_TENSOR_F32 ? 4 : 2, W = t->out_width, H = t->out_height;
+    const uint64_t stride_h = t->stride_h ? t->stride_h : W;
+    if (stride_h < W) return H263MI_ERR_INVALID_ARGUMENT;
+    const u128 plane = (u128)(H - 1) * stride_h + W;          // elements from a plane's first to behind its last
+    const u128 stride_c = t->stride_c ? (u128)t->stride_c : (u128)H * stride_h;
+    if (stride_c < plane) return H263MI_ERR_INVALID_ARGUMENT;
+    const u128 picture = 2 * stride_c + plane;
+    if (picture * elt >= ((u128)1 << 32)) return H263MI_ERR_INVALID_ARGUMENT;
+    const u128 stride_n = t->stride_n ? (u128)t->stride_n : 3 * stride_c;
+    if (n_streams > 1 && stride_n < picture) return H263MI_ERR_INVALID_ARGUMENT;
+    const u128 total = ((u128)(n_streams - 1) * stride_n + picture) * elt;
+    // (the streams' byte offsets must fit too: they are below `total`)
+    if (total > UINT64_MAX) return H263MI_ERR_INVALID_ARGUMENT;
+    if (bytes) *bytes = (uint64_t)total;
+    if (out) {
+        out->on = true;
+        out->dtype = t->dtype;
+        out->bgr = t->bgr;
+        out->elt = (uint32_t)elt;
+        for (int c = 0; c < 3; c++) out->scale[c] = t->scale[c], out->bias[c] = t->bias[c];
+        out->stride_c = (uint64_t)stride_c;
+        out->stride_h = stride_h;
+    }
+    if (stride_n_out) *stride_n_out = n_streams > 1 ? (uint64_t)stride_n : 0;
+    return H263MI_OK;
+}
+
+uint64_t tensor_scratch_bytes(uint32_t w, uint32_t h, uint32_t slots, const h263mi_tensor_out &t)
+{
+    return (uint64_t)slots * w * h * 4 + ((uint64_t)t.out_width + t.out_height) * sizeof(ResizeSpan);
+}
+
 bool resize_as_layout(uint32_t w, uint32_t h, const h263mi_rgba_resize &r, h263mi_rgba_layout *lay)
 {
     for (int f = 0; f <= 2; f++) {
@@ -300,6 +341,21 @@ int make_output_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263
     return H263MI_OK;
 }
 
+int make_tensor_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_tensor_out *t, RgbaLayout &out)
+{
+    if (!t) return make_rgba_layout_shape(n, w, h, nullptr, out);
+    RgbaLayout shape;
+    uint64_t stride_n = 0;
+    RC_TRY(tensor_extent(n, t, &shape.bytes, &shape.resize.tensor, &stride_n));
+    RC_TRY(make_scratch(device, (size_t)n * w * h * 4, {{w, t->out_width}, {h, t->out_height}}, shape.resize.scratch));
+    shape.offsets.resize(n);
+    for (uint32_t i = 0; i < n; i++) shape.offsets[i] = (uint64_t)i * stride_n * shape.resize.tensor.elt;
+    shape.resize.ow = t->out_width;
+    shape.resize.oh = t->out_height;
+    out = std::move(shape);
+    return H263MI_OK;
+}
+
 int make_yuv_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_yuv_layout *lay, YuvLayout &out)
 {
     YuvLayout shape;
@@ -367,5 +423,6 @@ int h263mi_yuv_layout_extent(uint32_t n_streams, uint16_t width, uint16_t height
 }
 int h263mi_rgba_resize_extent(uint32_t n_streams, const h263mi_rgba_resize *r, uint64_t *bytes) { return h263mi::rgba_resize_extent(n_streams, r, bytes); }
 int h263mi_yuv_resize_extent(uint32_t n_streams, const h263mi_yuv_resize *r, uint64_t *bytes) { return h263mi::yuv_resize_extent(n_streams, r, bytes); }
+int h263mi_tensor_extent(uint32_t n_streams, const h263mi_tensor_out *t, uint64_t *bytes) { return h263mi::tensor_extent(n_streams, t, bytes); }
 
 }  // extern "C"

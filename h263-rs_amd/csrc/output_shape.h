@@ -1,5 +1,5 @@
 // output_shape.h -- the SHAPE a rendering writes its output in: the RGBA layouts and resizes (h263mi_rgba_layout,
-// h263mi_rgba_resize) and the plane layouts and resizes (h263mi_yuv_layout, h263mi_yuv_resize).  A caller's placement is
+// h263mi_rgba_resize), the float tensor that a resize may end in (h263mi_tensor_out) and the plane layouts and resizes (h263mi_yuv_layout, h263mi_yuv_resize).  A caller's placement is
 // validated here (the *_extent entry points), turned into what the kernels are told, and given the device memory it needs: the
 // plane offsets of a YUV layout, the scratch and the span tables of a resize.  Nothing here knows a frame store: a batch holds
 // one RgbaLayout and one YuvLayout (batch.h) and hands them to its renderings.
@@ -57,8 +57,18 @@ struct RgbaLayout {
     struct Resize {
         std::shared_ptr<ResizeScratch> scratch;
         uint32_t ow = 0, oh = 0, pitch = 0;
+        // ... or the resize ends in a tensor (h263mi_batch_set_tensor_output: k_tensor_resize instead of k_rgba_resize; `offsets`
+        // are then the BYTE offsets of the streams' tensors, pitch is not used): the whole description, copied
+        struct Tensor {
+            bool on = false;
+            uint32_t dtype = 0, bgr = 0, elt = 4;      // (elt: bytes per element)
+            float scale[3] = {1, 1, 1}, bias[3] = {0, 0, 0};
+            uint64_t stride_c = 0, stride_h = 0;       // in elements, defaults spelled out
+        } tensor;
         bool on() const { return scratch != nullptr; }
     } resize;
+    // what a pointer into the caller's buffer must be a multiple of (a tensor: its element size)
+    uint32_t base_align() const { return resize.on() && resize.tensor.on ? resize.tensor.elt : 1u; }
 };
 
 // The shape of the deblocked planes in d_deblocked (h263mi_batch_set_yuv_layout).  format 0: none -- tightly packed I420
@@ -112,6 +122,12 @@ int rgba_resize_extent(uint32_t n_streams, const h263mi_rgba_resize *r, uint64_t
 // h263mi_yuv_resize_extent; shape / offsets as yuv_layout_extent (of the W' x H' picture)
 int yuv_resize_extent(uint32_t n_streams, const h263mi_yuv_resize *r, uint64_t *bytes, YuvLayout *shape = nullptr,
                       std::vector<uint64_t> *offsets = nullptr);
+// h263mi_tensor_extent for n streams.  out (may be null): dtype, order, scale, bias and the strides with their defaults spelled
+// out; stride_n (may be null): the streams' distance in elements
+int tensor_extent(uint32_t n_streams, const h263mi_tensor_out *t, uint64_t *bytes, RgbaLayout::Resize::Tensor *out = nullptr,
+                  uint64_t *stride_n = nullptr);
+// device memory a tensor output of `slots` pictures of w x h holds: always a scratch, whatever W' x H'
+uint64_t tensor_scratch_bytes(uint32_t w, uint32_t h, uint32_t slots, const h263mi_tensor_out &t);
 // the layout that a resize of a w x h picture is by definition (full size, or 1/2 or 1/4 of sizes that 2 or 4 divide), into
 // *lay (offsets and pitch copied); false: none, the resize needs k_rgba_resize
 bool resize_as_layout(uint32_t w, uint32_t h, const h263mi_rgba_resize &r, h263mi_rgba_layout *lay);
@@ -123,6 +139,9 @@ uint64_t resize_scratch_bytes(uint32_t w, uint32_t h, uint32_t slots, const h263
 int make_rgba_layout_shape(uint32_t n, uint32_t w, uint32_t h, const h263mi_rgba_layout *layout, RgbaLayout &out);
 // the RGBA shape `r` (NULL: the default): the layout it is by definition, or the resize with a new scratch
 int make_output_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_rgba_resize *r, RgbaLayout &out);
+// the tensor shape `t` (NULL: the default): always the resize with a new scratch -- W' = w, H' = h too, where the area average is
+// the identity -- followed by k_tensor_resize
+int make_tensor_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_tensor_out *t, RgbaLayout &out);
 // the layout (NULL: none, format 0), its offsets uploaded
 int make_yuv_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_yuv_layout *layout, YuvLayout &out);
 // the YUV shape `r` (NULL: none): the full-size layout it is by definition when W' = w and H' = h, else the resize with a new

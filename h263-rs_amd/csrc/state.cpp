@@ -348,6 +348,36 @@ int h263mi_render_rgba_resize(const h263mi_state *cs, uint8_t strength, const h2
     return render_rgba_shaped(s, st, shape, r->out_width, r->out_height, r->row_pitch, rgba);
 }
 
+int h263mi_render_tensor(const h263mi_state *cs, uint8_t strength, const h263mi_tensor_out *t, void *out)
+{
+    h263mi_state *s = const_cast<h263mi_state *>(cs);
+    if (!s || !out || !t) return H263MI_ERR_INVALID_ARGUMENT;
+    if (!s->has_last || !s->b) return H263MI_ERR_NO_PICTURE;
+    h263mi_batch *b = s->b;
+    // the caller's shape: where its planes lie in `out`
+    h263mi_batch::RgbaLayout::Resize::Tensor host;
+    RC_TRY(tensor_extent(1, t, nullptr, &host));
+    h263mi_batch::Strengths st;
+    RC_TRY(state_strength(s, strength, st));
+    DeviceGuard g(s->cfg.device_id);
+    // written on the device as one contiguous 3 x H' x W' tensor into the state's scratch, then each plane copied out row by
+    // row into the caller's rectangle
+    h263mi_tensor_out tight = *t;
+    tight.stride_n = tight.stride_c = tight.stride_h = 0;
+    const size_t row = (size_t)t->out_width * host.elt, plane = row * t->out_height;
+    RC_TRY(s->rgba.reserve(s->cfg.device_id, 3 * plane));
+    h263mi_batch::RgbaLayout shape;            // (its scratch goes at the end, once the copies out have waited for it)
+    RC_TRY(make_tensor_shape(s->cfg.device_id, 1, b->L.width, b->L.height, &tight, shape));
+    const uint8_t *d = s->rgba.as<uint8_t>();
+    RC_TRY(b->render(st, s->rgba.as<uint8_t>(), nullptr, false, nullptr, &shape));
+    const hipStream_t on = b->stream;
+    for (size_t p = 0; p < 3; p++)
+        HIP_TRY(hipMemcpy2DAsync(static_cast<uint8_t *>(out) + p * host.stride_c * host.elt, host.stride_h * host.elt, d + p * plane, row,
+                                 row, t->out_height, hipMemcpyDeviceToHost, on));
+    HIP_TRY(hipStreamSynchronize(on));
+    return H263MI_OK;
+}
+
 int h263mi_render_yuv(const h263mi_state *cs, uint8_t strength, const h263mi_yuv_layout *layout, uint8_t *out)
 {
     h263mi_state *s = const_cast<h263mi_state *>(cs);

@@ -96,7 +96,11 @@ EXPORTS = [
     # ABI 7, additive: Adler-32 digests of decoded pictures and output buffers, made on the device
     "h263mi_adler32_spans_on", "h263mi_batch_adler32_spans", "h263mi_digest_yuv", "h263mi_batch_digest_yuv",
     "h263mi_mixed_digest_yuv",
+    # ABI 7, additive: the picture as a normalised planar float tensor (f32 / f16 / bf16) for inference
+    "h263mi_tensor_extent", "h263mi_batch_set_tensor_output", "h263mi_render_tensor", "h263mi_mixed_set_tensor_output",
 ]
+TENSOR_F32, TENSOR_F16, TENSOR_BF16 = 0, 1, 2
+TENSOR_NUMPY_DTYPE = {TENSOR_F32: np.float32, TENSOR_F16: np.float16, TENSOR_BF16: np.uint16}     # (bfloat16: bit patterns)
 YUV_I420, YUV_NV12 = 0, 1
 STRENGTH_FROM_HEADER = 0xFF
 CFG_OVERLAP_POST, CFG_PIPELINE_POST, CFG_TRUSTED_ARRAYS = 1, 2, 4
@@ -188,6 +192,31 @@ def rgba_resize_extent(n_streams, out_width, out_height, row_pitch=0, offsets=No
     nb = C.c_uint64()
     _check(lib().h263mi_rgba_resize_extent(n_streams, C.byref(resize), C.byref(nb)), "rgba_resize_extent")
     del keep
+    return nb.value
+
+
+class TensorOut(C.Structure):
+    """h263mi_tensor_out: the picture as 3 planes of out_height x out_width elements of `dtype`, element = u * scale[colour] +
+    bias[colour] (two binary32 roundings) of the area average u; strides in elements (0 = contiguous NCHW)."""
+    _fields_ = [("out_width", C.c_uint16), ("out_height", C.c_uint16), ("dtype", C.c_uint8), ("bgr", C.c_uint8),
+                ("reserved", C.c_uint8 * 2), ("scale", C.c_float * 3), ("bias", C.c_float * 3), ("stride_n", C.c_uint64),
+                ("stride_c", C.c_uint64), ("stride_h", C.c_uint64)]
+
+
+def make_tensor_out(out_width, out_height, dtype=TENSOR_F32, scale=(1.0, 1.0, 1.0), bias=(0.0, 0.0, 0.0), bgr=False, stride_n=0,
+                    stride_c=0, stride_h=0):
+    t = TensorOut()
+    t.out_width, t.out_height, t.dtype, t.bgr = out_width, out_height, dtype, 1 if bgr else 0
+    t.scale = (C.c_float * 3)(*[float(v) for v in scale])
+    t.bias = (C.c_float * 3)(*[float(v) for v in bias])
+    t.stride_n, t.stride_c, t.stride_h = stride_n, stride_c, stride_h
+    return t
+
+
+def tensor_extent(n_streams, tensor):
+    """h263mi_tensor_extent -> bytes the tensor's buffer must hold; H263Error when the description is refused"""
+    nb = C.c_uint64()
+    _check(lib().h263mi_tensor_extent(n_streams, C.byref(tensor) if tensor is not None else None, C.byref(nb)), "tensor_extent")
     return nb.value
 
 
@@ -491,6 +520,10 @@ def lib():
         L.h263mi_mixed_digest_yuv.argtypes = [vp, u32, vp, vp]
         L.h263mi_default_parser_threads.restype = u32
         L.h263mi_default_parser_threads.argtypes = [u32, C.POINTER(u32)]
+        L.h263mi_tensor_extent.argtypes = [u32, vp, C.POINTER(C.c_uint64)]
+        L.h263mi_batch_set_tensor_output.argtypes = [vp, vp]
+        L.h263mi_render_tensor.argtypes = [vp, u8, vp, vp]
+        L.h263mi_mixed_set_tensor_output.argtypes = [vp, vp]
         _lib = L
     return _lib
 
@@ -690,6 +723,23 @@ class H263State:
     def render_rgba_resize_into(self, strength, out, out_width, out_height, row_pitch=0):
         r, _ = make_rgba_resize(out_width, out_height, row_pitch)
         _check(lib().h263mi_render_rgba_resize(self._h, strength, C.byref(r), _p(out)), "render_rgba_resize")
+        return out
+
+    def render_tensor(self, strength, tensor):
+        """h263mi_render_tensor -> a (3, H', W') array of float32 / float16, or of uint16 bit patterns for bfloat16, cut out of a
+        buffer of the extent's size (what lies between rows and planes is zero there)"""
+        nb = tensor_extent(1, tensor)
+        dt = np.dtype(TENSOR_NUMPY_DTYPE[tensor.dtype])
+        out = np.zeros(nb // dt.itemsize, dt)
+        self.render_tensor_into(strength, tensor, out)
+        W, H = tensor.out_width, tensor.out_height
+        sh = tensor.stride_h or W
+        sc = tensor.stride_c or H * sh
+        return np.lib.stride_tricks.as_strided(out, (3, H, W), (sc * dt.itemsize, sh * dt.itemsize, dt.itemsize)).copy()
+
+    def render_tensor_into(self, strength, tensor, out):
+        """h263mi_render_tensor into `out` (an array whose first byte is the tensor's base); bytes outside the planes stay"""
+        _check(lib().h263mi_render_tensor(self._h, strength, C.byref(tensor), _p(out)), "render_tensor")
         return out
 
     def render_yuv(self, strength=0, format=YUV_I420, pitch_y=0, pitch_c=0):
@@ -1000,6 +1050,11 @@ class Batch:
         _check(lib().h263mi_batch_set_rgba_resize(self._h, C.byref(r)), "batch_set_rgba_resize")
         del keep
 
+    def set_tensor_output(self, tensor=None):
+        """h263mi_batch_set_tensor_output: d_rgba of the later calls is the base of the tensor `tensor` (a TensorOut; None: back
+        to today's output)"""
+        _check(lib().h263mi_batch_set_tensor_output(self._h, C.byref(tensor) if tensor is not None else None), "batch_set_tensor_output")
+
     def render_rgba(self, strength, d_rgba, d_deblocked=None, strengths=None):
         keep, ps = self._strengths(strengths)
         _check(lib().h263mi_batch_render_rgba_ps(self._h, strength, ps, d_rgba, d_deblocked), "batch_render_rgba")
@@ -1121,6 +1176,11 @@ class MixedBatch:
             return
         r, _ = make_rgba_resize(out_width, out_height, row_pitch)
         _check(lib().h263mi_mixed_set_rgba_resize(self._h, C.byref(r)), "mixed_set_rgba_resize")
+
+    def set_tensor_output(self, tensor=None):
+        """h263mi_mixed_set_tensor_output: every stream as the 3 x H' x W' tensor `tensor` (stride_n 0) at its own buffer (None:
+        full-size RGBA again)"""
+        _check(lib().h263mi_mixed_set_tensor_output(self._h, C.byref(tensor) if tensor is not None else None), "mixed_set_tensor_output")
 
     def set_memory_limit(self, n_bytes):
         """what the frame stores of all size classes together may take (0 = no limit; default: half of the device's memory)"""

@@ -160,6 +160,16 @@ public:
         check(h263mi_render_rgba_resize(s_, strength, &r, rgba.data()));
         return rgba;
     }
+    // the last picture as the normalised planar tensor `t` (h263mi_tensor_out, n = 1): the extent's bytes -- elements of
+    // float, or of IEEE binary16 / bfloat16 bit patterns --, the ones outside the 3 * H' rows zero
+    std::vector<uint8_t> render_tensor(uint8_t strength, const h263mi_tensor_out &t) const
+    {
+        uint64_t bytes = 0;
+        check(h263mi_tensor_extent(1, &t, &bytes));
+        std::vector<uint8_t> out((size_t)bytes);
+        check(h263mi_render_tensor(s_, strength, &t, out.data()));
+        return out;
+    }
     // the deblocked planes of the last picture as I420 or NV12 (h263mi_yuv_layout; nullptr: tightly packed I420), without
     // going through RGBA: the layout's extent in bytes, the ones outside the planes zero
     std::vector<uint8_t> render_yuv(uint8_t strength, const h263mi_yuv_layout *layout = nullptr) const
@@ -362,6 +372,8 @@ public:
     void set_memory_limit(uint64_t bytes) { check(h263mi_mixed_set_memory_limit(m_, bytes)); }
     // every stream rendered as W' x H' (offsets NULL); nullptr = full size again
     void set_rgba_resize(const h263mi_rgba_resize *r) { check(h263mi_mixed_set_rgba_resize(m_, r)); }
+    // every stream written as the 3 x H' x W' tensor `t` (stride_n 0) at its own buffer; nullptr = full-size RGBA again
+    void set_tensor_output(const h263mi_tensor_out *t) { check(h263mi_mixed_set_tensor_output(m_, t)); }
     uint64_t frame_store_bytes() const { return h263mi_mixed_frame_store_bytes(m_); }
     // per stream zlib's adler32(Y + Cb + Cr of its last picture, seed), nullopt for a stream without a picture; one launch pair
     // per picture size

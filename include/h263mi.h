@@ -427,6 +427,50 @@ int h263mi_batch_set_rgba_resize(h263mi_batch *b, const h263mi_rgba_resize *r);
 int h263mi_render_rgba_resize(const h263mi_state *s, uint8_t strength, const h263mi_rgba_resize *r, uint8_t *rgba);
 
 /*
+ * NORMALISED PLANAR FLOAT TENSOR OUTPUT (additive, ABI 7): the picture as the 3 x H' x W' input of a network -- resized,
+ * de-interleaved, converted and normalised in one pass behind the rendering.
+ * The value: let u (0..255) be the channel value of h263mi_rgba_resize for the same picture, strength and W' x H' (the area
+ * average of the full-size RGBA after deblock and BT.601, as documented there).  The element is
+ *     v = fl32( fl32( (float)u * scale[c] ) + bias[c] )
+ * -- two IEEE binary32 roundings to nearest even, NEVER a fused multiply-add; subnormals are kept.  For F16 and BF16 v is then
+ * converted with round-to-nearest-even: overflow gives +-inf, subnormal results are kept (BF16 bits of a finite v with binary32
+ * bits b: (b + 0x7fff + ((b >> 16) & 1)) >> 16).  It is what numpy.float32 arithmetic followed by .astype(float16) produces.
+ * Placement: element (n, p, Y, X) lies n*stride_n + p*stride_c + Y*stride_h + X ELEMENTS behind the pointer; plane p holds
+ * colour p (R, G, B) or, with bgr = 1, colour 2 - p.  scale and bias are per COLOUR.  No alpha plane.  Nothing outside the
+ * 3 * H' rows of W' elements per stream is written; a stream with nothing to render is not written at all.
+ */
+#define H263MI_TENSOR_F32  0
+#define H263MI_TENSOR_F16  1   /* IEEE binary16 */
+#define H263MI_TENSOR_BF16 2
+typedef struct h263mi_tensor_out {
+    uint16_t out_width, out_height;   /* W', H' >= 1 */
+    uint8_t  dtype;                   /* H263MI_TENSOR_* */
+    uint8_t  bgr;                     /* 0: planes R,G,B   1: planes B,G,R */
+    uint8_t  reserved[2];             /* zero */
+    float    scale[3], bias[3];       /* per COLOUR R,G,B (not per plane position); finite */
+    uint64_t stride_n, stride_c, stride_h;   /* in ELEMENTS; 0 = contiguous NCHW: W', H'*stride_h, 3*stride_c */
+} h263mi_tensor_out;
+
+/* Pure host function, no HIP call: validates and returns the bytes the tensor's buffer must hold,
+ *     elt * ((n-1)*stride_n + 2*stride_c + (H'-1)*stride_h + W')      (elt = 4, 2, 2 bytes).
+ * H263MI_ERR_INVALID_ARGUMENT: t NULL, n_streams 0, W' or H' 0; dtype unknown, bgr > 1, a reserved byte set; a scale or bias
+ * that is not finite; stride_h < W'; stride_c < (H'-1)*stride_h + W'; stride_n < 2*stride_c + (H'-1)*stride_h + W' while
+ * n_streams > 1; one picture's byte span >= 2^32; a sum that does not fit 64 bits. */
+int h263mi_tensor_extent(uint32_t n_streams, const h263mi_tensor_out *t, uint64_t *bytes);
+/* A batch has ONE shape in force for d_rgba: a layout, a resize or a tensor; each setter replaces the others, NULL restores the
+ * default; a refused setter leaves the shape in force untouched.  Every later call that writes d_rgba follows it
+ * (h263mi_batch_decode[_ps], _decode_events[_ps], _render_rgba[_ps], _decode_next_pictures[_ex|_ps]); a deferred rendering of
+ * H263MI_CFG_PIPELINE_POST keeps the whole description of its request (sizes, dtype, order, scale, bias, strides: copied).
+ * d_rgba is then the tensor's base: it must be a multiple of the element size (else H263MI_ERR_INVALID_ARGUMENT before
+ * anything is queued), and a checked batch holds it to h263mi_tensor_extent.  The batch keeps a device scratch of
+ * n_streams * w*h*4 bytes (the full-size RGBA) while a tensor is in force, whatever W' x H'.  d_deblocked and its shapes stay
+ * independent. */
+int h263mi_batch_set_tensor_output(h263mi_batch *b, const h263mi_tensor_out *t);
+/* One state, into HOST memory, n = 1 (stride_n is not used): `out` is the tensor's base.  strength as h263mi_render_rgba
+ * (H263MI_STRENGTH_FROM_HEADER included).  Bytes outside the 3 * H' rows are untouched. */
+int h263mi_render_tensor(const h263mi_state *s, uint8_t strength, const h263mi_tensor_out *t, void *out);
+
+/*
  * DEBLOCKED YUV 4:2:0 OUTPUT LAYOUT (additive, ABI 7): where the filtered planes go inside d_deblocked.  The planes are always
  * full size (w x h luma, cw x ch chroma, cw = ceil(w/2), ch = ceil(h/2)) under a layout -- h263mi_yuv_resize below resizes them --;
  * the RGBA layouts and resizes above apply to d_rgba only and the two shapes are independent.  I420: three planes Y, Cb, Cr.  NV12: a Y plane and one plane of ch rows of cw
@@ -716,6 +760,12 @@ uint64_t h263mi_mixed_frame_store_bytes(const h263mi_mixed *m);
  * h263mi_rgba_resize keeps a device scratch of its full-size pictures, slots * w*h*4 bytes: it counts against
  * h263mi_mixed_set_memory_limit and in h263mi_mixed_frame_store_bytes as its frame store does. */
 int h263mi_mixed_set_rgba_resize(h263mi_mixed *m, const h263mi_rgba_resize *r);
+/* Every stream of the set, whatever its size, written as the 3 x H' x W' tensor `t` (h263mi_tensor_out; stride_n must be 0) at
+ * its own d_rgba[s] -- streams of any sizes land in one tensor of one size when the caller passes base + s * stride; NULL =
+ * full-size RGBA again.  d_rgba[s] must be a multiple of the element size and rgba_capacity[s] at least
+ * h263mi_tensor_extent(1, t) (else that stream's H263MI_ERR_INVALID_ARGUMENT).  Replaces h263mi_mixed_set_rgba_resize and is
+ * replaced by it.  Every class keeps the scratch of its full-size pictures, slots * w*h*4 bytes, counted as the resize's. */
+int h263mi_mixed_set_tensor_output(h263mi_mixed *m, const h263mi_tensor_out *t);
 /* DecodedPicture::as_yuv of stream `stream`'s last picture: tightly packed planes to HOST memory */
 int h263mi_mixed_copy_yuv(h263mi_mixed *m, uint32_t stream, uint8_t *y, uint8_t *cb, uint8_t *cr);
 /* H263State::new for one stream: it forgets its pictures and its size */
