@@ -125,6 +125,19 @@ int h263mi_batch::launch_resize(const RgbaLayout::Resize &rz, const std::vector<
     a.d = L.width * L.height;
     a.inv_d = 1.0f / (float)a.d;
     a.n_pictures = n;
+    // a framing: the resize inside the destination rectangle (its span tables, its divisor), the W' x H' output around it
+    FrameRect fr{};
+    if (rz.framed.on) {
+        const h263mi_framing_rects &rc = rz.framed.rc;
+        a.rows = a.cols + rc.dst_w;
+        a.ow = rc.dst_w;
+        a.oh = rc.dst_h;
+        a.d = (uint32_t)rc.src_w * rc.src_h;
+        a.inv_d = 1.0f / (float)a.d;
+        fr.cw = rz.ow, fr.ch = rz.oh, fr.dx = rc.dst_x, fr.dy = rc.dst_y;
+        fr.pad = rz.framed.pad;
+        fr.keep = rz.framed.keep ? 1u : 0u;
+    }
     if (rz.tensor.on) {                        // the same resize, ending in planar float stores (k_tensor_resize)
         TensorArgs ta{};
         ta.r = a;
@@ -133,9 +146,21 @@ int h263mi_batch::launch_resize(const RgbaLayout::Resize &rz, const std::vector<
         ta.bgr = rz.tensor.bgr;
         ta.stride_c = rz.tensor.stride_c;
         ta.stride_h = rz.tensor.stride_h;
+        if (rz.framed.on) {
+            if (!launch_tensor_resize_framed) return H263MI_ERR_HIP;       // (kernels.h: only a stub runtime lacks it)
+            RC_TRY(time_begin(3, on));
+            HIP_TRY(launch_tensor_resize_framed(FramedTensorArgs{ta, fr}, on));
+            return H263MI_OK;
+        }
         if (!launch_tensor_resize) return H263MI_ERR_HIP;  // (kernels.h: only a stub runtime lacks it)
         RC_TRY(time_begin(3, on));
         HIP_TRY(launch_tensor_resize(ta, on));
+        return H263MI_OK;
+    }
+    if (rz.framed.on) {
+        if (!launch_rgba_resize_framed) return H263MI_ERR_HIP;             // (kernels.h: only a stub runtime lacks it)
+        RC_TRY(time_begin(3, on));
+        HIP_TRY(launch_rgba_resize_framed(FramedResizeArgs{a, fr}, on));
         return H263MI_OK;
     }
     if (!launch_rgba_resize) return H263MI_ERR_HIP;        // (kernels.h: only a stub runtime lacks it)
@@ -967,6 +992,26 @@ int h263mi_batch_set_tensor_output(h263mi_batch *b, const h263mi_tensor_out *t)
     h263mi_batch::RgbaLayout lay;
     RC_TRY(make_tensor_shape(b->device, b->n, b->L.width, b->L.height, t, lay));
     DeviceGuard g(b->device);                  // (a shape it replaces frees its scratch, unless a pending rendering holds it)
+    b->layout = std::move(lay);
+    return H263MI_OK;
+}
+
+int h263mi_batch_set_rgba_resize_framed(h263mi_batch *b, const h263mi_rgba_resize *r, const h263mi_framing *f)
+{
+    if (!b) return H263MI_ERR_INVALID_ARGUMENT;
+    h263mi_batch::RgbaLayout lay;
+    RC_TRY(make_output_shape(b->device, b->n, b->L.width, b->L.height, r, lay, f));
+    DeviceGuard g(b->device);                  // (a shape it replaces frees its scratch, unless a pending rendering holds it)
+    b->layout = std::move(lay);
+    return H263MI_OK;
+}
+
+int h263mi_batch_set_tensor_output_framed(h263mi_batch *b, const h263mi_tensor_out *t, const h263mi_framing *f)
+{
+    if (!b) return H263MI_ERR_INVALID_ARGUMENT;
+    h263mi_batch::RgbaLayout lay;
+    RC_TRY(make_tensor_shape(b->device, b->n, b->L.width, b->L.height, t, lay, f));
+    DeviceGuard g(b->device);
     b->layout = std::move(lay);
     return H263MI_OK;
 }

@@ -53,6 +53,11 @@ hipError_t launch_rgba_resize(const ResizeArgs &args, hipStream_t stream) __attr
 // k_tensor_resize over args.r.n_pictures pictures (tensor_resize_kernel.inl; bands and chunk are set here): k_rgba_resize's launch
 // shape, planar float stores.  Weak like launch_rgba_resize; h263mi_batch::launch_resize refuses to write a tensor without it.
 hipError_t launch_tensor_resize(const TensorArgs &args, hipStream_t stream) __attribute__((weak));
+// k_rgba_resize_framed / k_tensor_resize_framed (h263mi_framing): args.r describes the resize inside the destination rectangle,
+// args.f the W' x H' output around it, which is what the launch covers (bands and chunk are set here).  Weak like
+// launch_rgba_resize; the host refuses a framed shape without them.
+hipError_t launch_rgba_resize_framed(const FramedResizeArgs &args, hipStream_t stream) __attribute__((weak));
+hipError_t launch_tensor_resize_framed(const FramedTensorArgs &args, hipStream_t stream) __attribute__((weak));
 // k_plane_resize over args.n_pictures pictures (plane_resize_kernel.inl; bands, chunk and segs_y are set here): the luma and
 // chroma planes of every picture in ONE launch.  Weak like launch_rgba_resize; h263mi_batch::launch_plane_resize refuses to run
 // without it.

@@ -802,6 +802,62 @@ hipError_t launch_tensor_resize(const TensorArgs &args, hipStream_t stream)
 }
 
 // ---------------------------------------------------------------------------------------
+// k_rgba_resize_framed, k_tensor_resize_framed: a source window into a destination rectangle of the W' x H' output, the rest
+// padded or kept (h263mi_framing; resize_kernel.inl, tensor_resize_kernel.inl).  Instantiations of their own: k_rgba_resize and
+// k_tensor_resize above are not touched.  The launch shape is theirs over the W' x H' output: one wave per workgroup, no
+// barrier, blockIdx.y = picture, blockIdx.z = segment of 64 output columns, blockIdx.x = band in XCD order.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_rgba_resize_framed(FramedResizeArgs a)
+{
+    __shared__ __attribute__((aligned(16))) ResizeLds lds;
+    const uint32_t band = (blockIdx.x & 7u) * a.r.chunk + (blockIdx.x >> 3);
+    if (band >= a.r.bands) return;
+    const int lane = threadIdx.x & 63;
+    ResizeLane t;
+    framed_resize_item(a, lds, band, blockIdx.z, blockIdx.y, [&](auto f) { f(lane, t); });
+}
+
+__global__ __launch_bounds__(64) void k_tensor_resize_framed(FramedTensorArgs a)
+{
+    __shared__ __attribute__((aligned(16))) ResizeLds lds;
+    const uint32_t band = (blockIdx.x & 7u) * a.t.r.chunk + (blockIdx.x >> 3);
+    if (band >= a.t.r.bands) return;
+    const int lane = threadIdx.x & 63;
+    TensorLane t;
+    framed_tensor_item(a, lds, band, blockIdx.z, blockIdx.y, [&](auto f) { f(lane, t); });
+}
+
+// what a framed launch must hold before a wave runs: a rectangle that is not empty and lies inside the output
+static bool frame_rect_ok(const ResizeArgs &r, const FrameRect &f)
+{
+    return r.ow && r.oh && f.cw && f.ch && f.keep <= 1 && f.dx <= f.cw && r.ow <= f.cw - f.dx && f.dy <= f.ch && r.oh <= f.ch - f.dy;
+}
+
+hipError_t launch_rgba_resize_framed(const FramedResizeArgs &args, hipStream_t stream)
+{
+    if (!args.r.n_pictures) return hipSuccess;
+    if (args.r.n_pictures > 65535 || !frame_rect_ok(args.r, args.f)) return hipErrorInvalidValue;
+    FramedResizeArgs a = args;
+    a.r.bands = (a.f.ch + RESIZE_ROWS - 1) / RESIZE_ROWS;
+    a.r.chunk = (a.r.bands + 7) / 8;
+    const dim3 grid(a.r.chunk * 8, a.r.n_pictures, (a.f.cw + 63) / 64);
+    hipLaunchKernelGGL(k_rgba_resize_framed, grid, dim3(64), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_tensor_resize_framed(const FramedTensorArgs &args, hipStream_t stream)
+{
+    if (!args.t.r.n_pictures) return hipSuccess;
+    if (args.t.r.n_pictures > 65535 || args.t.dtype > TENSOR_BF16 || !frame_rect_ok(args.t.r, args.f)) return hipErrorInvalidValue;
+    FramedTensorArgs a = args;
+    a.t.r.bands = (a.f.ch + RESIZE_ROWS - 1) / RESIZE_ROWS;
+    a.t.r.chunk = (a.t.r.bands + 7) / 8;
+    const dim3 grid(a.t.r.chunk * 8, a.t.r.n_pictures, (a.f.cw + 63) / 64);
+    hipLaunchKernelGGL(k_tensor_resize_framed, grid, dim3(64), 0, stream, a);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
 // k_plane_resize: area-average resampling of the full-size deblocked planes into I420 or NV12 (plane_resize_kernel.inl).  One
 // wave per workgroup, no barrier; blockIdx.y = picture, blockIdx.z = segment of PLANE_OUT output columns (the luma segments,
 // then the chroma segments: one launch for all planes), blockIdx.x = band of PLANE_ROWS output rows in XCD order, as

@@ -66,6 +66,9 @@ struct h263mi_mixed {
     bool tensored = false;
     h263mi_tensor_out tensor{};
     uint64_t tensor_bytes = 0;                  // h263mi_tensor_extent(1, &tensor)
+    // h263mi_mixed_set_*_framed: the framing of the resize or tensor in force (never WINDOW), resolved per size class
+    bool framed = false;
+    h263mi_framing framing{};
     ~h263mi_mixed()
     {
         pool.reset();                           // the host threads first
@@ -73,20 +76,21 @@ struct h263mi_mixed {
     }
     // a class's frame store, and the scratch of its full-size pictures while a resize that is not a layout is in force, or a
     // tensor (which always has one)
-    static uint64_t class_bytes(uint32_t w, uint32_t h, uint32_t slots, const h263mi_rgba_resize *rz, const h263mi_tensor_out *t = nullptr)
+    static uint64_t class_bytes(uint32_t w, uint32_t h, uint32_t slots, const h263mi_rgba_resize *rz, const h263mi_tensor_out *t = nullptr,
+                                const h263mi_framing *f = nullptr)
     {
         return 2ull * slots * make_layout(w, h).frame_bytes +
-               (t ? tensor_scratch_bytes(w, h, slots, *t) : (rz ? resize_scratch_bytes(w, h, slots, *rz) : 0));
+               (t ? tensor_scratch_bytes(w, h, slots, *t, f) : (rz ? resize_scratch_bytes(w, h, slots, *rz, f) : 0));
     }
     uint64_t slots_bytes(uint32_t w, uint32_t h, uint32_t slots) const
     {
-        return class_bytes(w, h, slots, resized ? &resize : nullptr, tensored ? &tensor : nullptr);
+        return class_bytes(w, h, slots, resized ? &resize : nullptr, tensored ? &tensor : nullptr, framed ? &framing : nullptr);
     }
     // the output shape in force for a class of `slots` slots of w x h (each slot placed by its own pointer)
     int class_shape(uint32_t slots, uint32_t w, uint32_t h, h263mi_batch::RgbaLayout &out) const
     {
-        if (tensored) return make_tensor_shape(cfg.device_id, slots, w, h, &tensor, out);
-        return make_output_shape(cfg.device_id, slots, w, h, resized ? &resize : nullptr, out);
+        if (tensored) return make_tensor_shape(cfg.device_id, slots, w, h, &tensor, out, framed ? &framing : nullptr);
+        return make_output_shape(cfg.device_id, slots, w, h, resized ? &resize : nullptr, out, framed ? &framing : nullptr);
     }
     uint64_t store_bytes() const
     {
@@ -260,43 +264,63 @@ int h263mi_mixed_set_memory_limit(h263mi_mixed *m, uint64_t bytes)
 
 uint64_t h263mi_mixed_frame_store_bytes(const h263mi_mixed *m) { return m ? m->store_bytes() : 0; }
 
-int h263mi_mixed_set_rgba_resize(h263mi_mixed *m, const h263mi_rgba_resize *r)
+// what a framing of a mixed set must say whatever the sizes: valid, and not a WINDOW (f may be null; 1 x 1 -> ow x oh resolves
+// under the rules that do not depend on the picture)
+static int mixed_framing_ok(const h263mi_framing *f, uint32_t ow, uint32_t oh)
+{
+    if (!f) return H263MI_OK;
+    if (f->mode == H263MI_FRAME_WINDOW) return H263MI_ERR_INVALID_ARGUMENT;
+    h263mi_framing_rects rc;
+    return framing_resolve(1, 1, ow, oh, f, &rc);
+}
+
+int h263mi_mixed_set_rgba_resize(h263mi_mixed *m, const h263mi_rgba_resize *r) { return h263mi_mixed_set_rgba_resize_framed(m, r, nullptr); }
+
+int h263mi_mixed_set_rgba_resize_framed(h263mi_mixed *m, const h263mi_rgba_resize *r, const h263mi_framing *f)
 {
     if (!m || (r && r->offsets)) return H263MI_ERR_INVALID_ARGUMENT;
     if (r) RC_TRY(rgba_resize_extent(1, r, nullptr));
+    if (!r) f = nullptr;
+    if (r) RC_TRY(mixed_framing_ok(f, r->out_width, r->out_height));
     DeviceGuard g(m->cfg.device_id);
     if (!g.ok) return H263MI_ERR_NO_DEVICE;
     // every class's new shape first (the scratches they need count against the limit), then all of them at once
     uint64_t total = 0;
     for (const h263mi_mixed::SizeClass &c : m->classes)
-        if (c.b) total += h263mi_mixed::class_bytes(c.w, c.h, c.b->n, r);
+        if (c.b) total += h263mi_mixed::class_bytes(c.w, c.h, c.b->n, r, nullptr, f);
     if (m->limit_bytes && total > m->limit_bytes) return H263MI_ERR_OUT_OF_MEMORY;
     std::vector<h263mi_batch::RgbaLayout> shapes(m->classes.size());
     for (size_t k = 0; k < m->classes.size(); k++)
-        if (m->classes[k].b) RC_TRY(make_output_shape(m->cfg.device_id, m->classes[k].b->n, m->classes[k].w, m->classes[k].h, r, shapes[k]));
+        if (m->classes[k].b) RC_TRY(make_output_shape(m->cfg.device_id, m->classes[k].b->n, m->classes[k].w, m->classes[k].h, r, shapes[k], f));
     for (size_t k = 0; k < m->classes.size(); k++)
         if (m->classes[k].b) m->classes[k].b->layout = std::move(shapes[k]);
     m->resized = r != nullptr;
     m->resize = r ? *r : h263mi_rgba_resize{};
     m->tensored = false;
+    m->framed = f != nullptr;
+    m->framing = f ? *f : h263mi_framing{};
     return H263MI_OK;
 }
 
-int h263mi_mixed_set_tensor_output(h263mi_mixed *m, const h263mi_tensor_out *t)
+int h263mi_mixed_set_tensor_output(h263mi_mixed *m, const h263mi_tensor_out *t) { return h263mi_mixed_set_tensor_output_framed(m, t, nullptr); }
+
+int h263mi_mixed_set_tensor_output_framed(h263mi_mixed *m, const h263mi_tensor_out *t, const h263mi_framing *f)
 {
     if (!m || (t && t->stride_n)) return H263MI_ERR_INVALID_ARGUMENT;
     uint64_t one = 0;
     if (t) RC_TRY(tensor_extent(1, t, &one));
+    if (!t) f = nullptr;
+    if (t) RC_TRY(mixed_framing_ok(f, t->out_width, t->out_height));
     DeviceGuard g(m->cfg.device_id);
     if (!g.ok) return H263MI_ERR_NO_DEVICE;
     // every class's new shape first (the scratches they need count against the limit), then all of them at once
     uint64_t total = 0;
     for (const h263mi_mixed::SizeClass &c : m->classes)
-        if (c.b) total += h263mi_mixed::class_bytes(c.w, c.h, c.b->n, nullptr, t);
+        if (c.b) total += h263mi_mixed::class_bytes(c.w, c.h, c.b->n, nullptr, t, f);
     if (m->limit_bytes && total > m->limit_bytes) return H263MI_ERR_OUT_OF_MEMORY;
     std::vector<h263mi_batch::RgbaLayout> shapes(m->classes.size());
     for (size_t k = 0; k < m->classes.size(); k++)
-        if (m->classes[k].b) RC_TRY(make_tensor_shape(m->cfg.device_id, m->classes[k].b->n, m->classes[k].w, m->classes[k].h, t, shapes[k]));
+        if (m->classes[k].b) RC_TRY(make_tensor_shape(m->cfg.device_id, m->classes[k].b->n, m->classes[k].w, m->classes[k].h, t, shapes[k], f));
     for (size_t k = 0; k < m->classes.size(); k++)
         if (m->classes[k].b) m->classes[k].b->layout = std::move(shapes[k]);
     m->tensored = t != nullptr;
@@ -304,7 +328,20 @@ int h263mi_mixed_set_tensor_output(h263mi_mixed *m, const h263mi_tensor_out *t)
     m->tensor_bytes = one;
     m->resized = false;
     m->resize = h263mi_rgba_resize{};
+    m->framed = f != nullptr;
+    m->framing = f ? *f : h263mi_framing{};
     return H263MI_OK;
+}
+
+int h263mi_mixed_stream_framing(const h263mi_mixed *m, uint32_t stream, h263mi_framing_rects *out)
+{
+    if (!m || stream >= m->n || !out) return H263MI_ERR_INVALID_ARGUMENT;
+    const int c = m->cls[stream];
+    if (c < 0 || m->classes[c].b->ss[m->slot[stream]].cur < 0) return H263MI_ERR_NO_PICTURE;
+    const uint32_t w = m->classes[c].w, h = m->classes[c].h;
+    const uint32_t ow = m->tensored ? m->tensor.out_width : (m->resized ? m->resize.out_width : w);
+    const uint32_t oh = m->tensored ? m->tensor.out_height : (m->resized ? m->resize.out_height : h);
+    return framing_resolve(w, h, ow, oh, m->framed ? &m->framing : nullptr, out);
 }
 
 int h263mi_mixed_decode_next_pictures(h263mi_mixed *m, uint32_t decoder_options, const uint8_t *const *data, const size_t *len,

@@ -260,9 +260,56 @@ int tensor_extent(uint32_t n_streams, const h263mi_tensor_out *t, uint64_t *byte
     return H263MI_OK;
 }
 
-uint64_t tensor_scratch_bytes(uint32_t w, uint32_t h, uint32_t slots, const h263mi_tensor_out &t)
+// h263mi_framing_resolve (include/h263mi.h has the rules): exact integer arithmetic, every product below 2^32
+static uint32_t rnd_div(uint64_t a, uint64_t b) { return (uint32_t)((2 * a + b) / (2 * b)); }
+static uint32_t clamp_to(uint32_t v, uint32_t hi) { return v < 1 ? 1 : (v > hi ? hi : v); }
+
+int framing_resolve(uint32_t w, uint32_t h, uint32_t ow, uint32_t oh, const h263mi_framing *f, h263mi_framing_rects *out, bool *whole)
 {
-    return (uint64_t)slots * w * h * 4 + ((uint64_t)t.out_width + t.out_height) * sizeof(ResizeSpan);
+    if (!out || !w || !h || !ow || !oh || w > 65535 || h > 65535 || ow > 65535 || oh > 65535) return H263MI_ERR_INVALID_ARGUMENT;
+    const uint32_t mode = f ? f->mode : (uint32_t)H263MI_FRAME_STRETCH;
+    uint32_t sx = 0, sy = 0, sw = w, sh = h, dx = 0, dy = 0, dw = ow, dh = oh;
+    if (f) {
+        if (mode > H263MI_FRAME_WINDOW || f->keep_outside > 1) return H263MI_ERR_INVALID_ARGUMENT;
+        for (uint8_t r : f->reserved)
+            if (r) return H263MI_ERR_INVALID_ARGUMENT;
+        const bool any = f->src_x || f->src_y || f->src_w || f->src_h || f->dst_x || f->dst_y || f->dst_w || f->dst_h;
+        if (mode != H263MI_FRAME_WINDOW && any) return H263MI_ERR_INVALID_ARGUMENT;
+    }
+    const bool wide = (uint64_t)w * oh >= (uint64_t)h * ow;        // the picture's aspect is at least the output's
+    if (mode == H263MI_FRAME_LETTERBOX) {
+        if (wide) dh = clamp_to(rnd_div((uint64_t)h * ow, w), oh);
+        else dw = clamp_to(rnd_div((uint64_t)w * oh, h), ow);
+        dx = (ow - dw) / 2;
+        dy = (oh - dh) / 2;
+    } else if (mode == H263MI_FRAME_COVER) {
+        if (wide) sw = clamp_to(rnd_div((uint64_t)h * ow, oh), w);
+        else sh = clamp_to(rnd_div((uint64_t)w * oh, ow), h);
+        sx = (w - sw) / 2;
+        sy = (h - sh) / 2;
+    } else if (mode == H263MI_FRAME_WINDOW) {
+        sx = f->src_x, sy = f->src_y, sw = f->src_w, sh = f->src_h;
+        dx = f->dst_x, dy = f->dst_y, dw = f->dst_w, dh = f->dst_h;
+        if (!sw || !sh || !dw || !dh || sx + sw > w || sy + sh > h || dx + dw > ow || dy + dh > oh) return H263MI_ERR_INVALID_ARGUMENT;
+    }
+    *out = h263mi_framing_rects{(uint16_t)sx, (uint16_t)sy, (uint16_t)sw, (uint16_t)sh, (uint16_t)dx, (uint16_t)dy, (uint16_t)dw, (uint16_t)dh};
+    if (whole) *whole = sw == w && sh == h && dw == ow && dh == oh;
+    return H263MI_OK;
+}
+
+// the framing of `f` for w x h -> ow x oh where it is NOT the unframed shape (then true, *rc filled in); f must resolve
+static bool framed_rects(uint32_t w, uint32_t h, uint32_t ow, uint32_t oh, const h263mi_framing *f, h263mi_framing_rects *rc)
+{
+    bool whole = true;
+    return f && framing_resolve(w, h, ow, oh, f, rc, &whole) == H263MI_OK && !whole;
+}
+
+uint64_t tensor_scratch_bytes(uint32_t w, uint32_t h, uint32_t slots, const h263mi_tensor_out &t, const h263mi_framing *f)
+{
+    h263mi_framing_rects rc;
+    const uint64_t spans = framed_rects(w, h, t.out_width, t.out_height, f, &rc) ? (uint64_t)rc.dst_w + rc.dst_h
+                                                                                 : (uint64_t)t.out_width + t.out_height;
+    return (uint64_t)slots * w * h * 4 + spans * sizeof(ResizeSpan);
 }
 
 bool resize_as_layout(uint32_t w, uint32_t h, const h263mi_rgba_resize &r, h263mi_rgba_layout *lay)
@@ -277,9 +324,12 @@ bool resize_as_layout(uint32_t w, uint32_t h, const h263mi_rgba_resize &r, h263m
     return false;
 }
 
-uint64_t resize_scratch_bytes(uint32_t w, uint32_t h, uint32_t slots, const h263mi_rgba_resize &r)
+uint64_t resize_scratch_bytes(uint32_t w, uint32_t h, uint32_t slots, const h263mi_rgba_resize &r, const h263mi_framing *f)
 {
     h263mi_rgba_layout lay;
+    h263mi_framing_rects rc;
+    if (framed_rects(w, h, r.out_width, r.out_height, f, &rc))
+        return (uint64_t)slots * w * h * 4 + ((uint64_t)rc.dst_w + rc.dst_h) * sizeof(ResizeSpan);
     if (resize_as_layout(w, h, r, &lay)) return 0;
     return (uint64_t)slots * w * h * 4 + ((uint64_t)r.out_width + r.out_height) * sizeof(ResizeSpan);
 }
@@ -303,13 +353,14 @@ int make_rgba_layout_shape(uint32_t n, uint32_t w, uint32_t h, const h263mi_rgba
 
 // The scratch of a resize on `device`: `pixel_bytes` for the full-size pictures, and the span tables of the geometries
 // (source length -> output length, in the order the kernel's tables lie) uploaded.
-struct SpanGeometry { uint32_t in, out; };
+struct SpanGeometry { uint32_t in, out, at = 0; };      // (at: where the `in` source columns start -- a framing's source window)
 static int make_scratch(int device, size_t pixel_bytes, std::initializer_list<SpanGeometry> geometries, std::shared_ptr<ResizeScratch> &out)
 {
     std::vector<ResizeSpan> spans;
     for (const SpanGeometry &g : geometries) {
         spans.resize(spans.size() + g.out);
         resize_spans(g.in, g.out, spans.data() + spans.size() - g.out);
+        for (uint32_t k = 0; k < g.out; k++) spans[spans.size() - g.out + k].first += g.at;
     }
     DeviceGuard g(device);
     if (!g.ok) return H263MI_ERR_NO_DEVICE;
@@ -321,17 +372,42 @@ static int make_scratch(int device, size_t pixel_bytes, std::initializer_list<Sp
     return H263MI_OK;
 }
 
-int make_output_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_rgba_resize *r, RgbaLayout &out)
+// The framing `f` of a w x h picture in an ow x oh output, validated; where it is not the unframed shape: into `fr`, and the
+// geometries of its span tables into g[2] (else fr.on stays false and g is that of the plain resize)
+static int resolve_framed(uint32_t w, uint32_t h, uint32_t ow, uint32_t oh, const h263mi_framing *f, RgbaLayout::Resize::Framed &fr,
+                          SpanGeometry g[2])
+{
+    g[0] = SpanGeometry{w, ow};
+    g[1] = SpanGeometry{h, oh};
+    if (!f) return H263MI_OK;
+    h263mi_framing_rects rc;
+    bool whole = true;
+    RC_TRY(framing_resolve(w, h, ow, oh, f, &rc, &whole));
+    if (whole) return H263MI_OK;
+    // (kernels.h: only a stub runtime lacks the framed kernels)
+    if (!launch_rgba_resize_framed || !launch_tensor_resize_framed) return H263MI_ERR_HIP;
+    fr.on = true;
+    fr.rc = rc;
+    fr.pad = (uint32_t)f->pad[0] | (uint32_t)f->pad[1] << 8 | (uint32_t)f->pad[2] << 16;
+    fr.keep = f->keep_outside != 0;
+    g[0] = SpanGeometry{rc.src_w, rc.dst_w, rc.src_x};
+    g[1] = SpanGeometry{rc.src_h, rc.dst_h, rc.src_y};
+    return H263MI_OK;
+}
+
+int make_output_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_rgba_resize *r, RgbaLayout &out, const h263mi_framing *f)
 {
     if (!r) return make_rgba_layout_shape(n, w, h, nullptr, out);
     RgbaLayout shape;
     RC_TRY(rgba_resize_extent(n, r, &shape.bytes));
+    const uint32_t ow = r->out_width, oh = r->out_height;
+    SpanGeometry g[2];
+    RC_TRY(resolve_framed(w, h, ow, oh, f, shape.resize.framed, g));
     h263mi_rgba_layout lay;
     // identical by definition: the fused layout kernels, no scratch, no extra pass
-    if (resize_as_layout(w, h, *r, &lay)) return make_rgba_layout_shape(n, w, h, &lay, out);
-    const uint32_t ow = r->out_width, oh = r->out_height;
+    if (!shape.resize.framed.on && resize_as_layout(w, h, *r, &lay)) return make_rgba_layout_shape(n, w, h, &lay, out);
     const uint64_t row = 4ull * ow, pitch = r->row_pitch ? r->row_pitch : row;
-    RC_TRY(make_scratch(device, (size_t)n * w * h * 4, {{w, ow}, {h, oh}}, shape.resize.scratch));
+    RC_TRY(make_scratch(device, (size_t)n * w * h * 4, {g[0], g[1]}, shape.resize.scratch));
     shape.offsets.resize(n);
     for (uint32_t i = 0; i < n; i++) shape.offsets[i] = r->offsets ? r->offsets[i] : (uint64_t)i * oh * pitch;
     shape.resize.ow = ow;
@@ -341,13 +417,15 @@ int make_output_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263
     return H263MI_OK;
 }
 
-int make_tensor_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_tensor_out *t, RgbaLayout &out)
+int make_tensor_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_tensor_out *t, RgbaLayout &out, const h263mi_framing *f)
 {
     if (!t) return make_rgba_layout_shape(n, w, h, nullptr, out);
     RgbaLayout shape;
     uint64_t stride_n = 0;
     RC_TRY(tensor_extent(n, t, &shape.bytes, &shape.resize.tensor, &stride_n));
-    RC_TRY(make_scratch(device, (size_t)n * w * h * 4, {{w, t->out_width}, {h, t->out_height}}, shape.resize.scratch));
+    SpanGeometry g[2];
+    RC_TRY(resolve_framed(w, h, t->out_width, t->out_height, f, shape.resize.framed, g));
+    RC_TRY(make_scratch(device, (size_t)n * w * h * 4, {g[0], g[1]}, shape.resize.scratch));
     shape.offsets.resize(n);
     for (uint32_t i = 0; i < n; i++) shape.offsets[i] = (uint64_t)i * stride_n * shape.resize.tensor.elt;
     shape.resize.ow = t->out_width;
@@ -424,5 +502,9 @@ int h263mi_yuv_layout_extent(uint32_t n_streams, uint16_t width, uint16_t height
 int h263mi_rgba_resize_extent(uint32_t n_streams, const h263mi_rgba_resize *r, uint64_t *bytes) { return h263mi::rgba_resize_extent(n_streams, r, bytes); }
 int h263mi_yuv_resize_extent(uint32_t n_streams, const h263mi_yuv_resize *r, uint64_t *bytes) { return h263mi::yuv_resize_extent(n_streams, r, bytes); }
 int h263mi_tensor_extent(uint32_t n_streams, const h263mi_tensor_out *t, uint64_t *bytes) { return h263mi::tensor_extent(n_streams, t, bytes); }
+int h263mi_framing_resolve(uint16_t w, uint16_t h, uint16_t out_w, uint16_t out_h, const h263mi_framing *f, h263mi_framing_rects *out)
+{
+    return h263mi::framing_resolve(w, h, out_w, out_h, f, out);
+}
 
 }  // extern "C"

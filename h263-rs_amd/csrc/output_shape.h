@@ -65,6 +65,15 @@ struct RgbaLayout {
             float scale[3] = {1, 1, 1}, bias[3] = {0, 0, 0};
             uint64_t stride_c = 0, stride_h = 0;       // in elements, defaults spelled out
         } tensor;
+        // ... and it may be framed (h263mi_framing that is not the unframed shape: k_rgba_resize_framed / k_tensor_resize_framed):
+        // the resolved rectangles -- the scratch's span tables are then those of sw -> dw and sh -> dh, offset by sx / sy -- the
+        // pad colour and keep_outside, copied
+        struct Framed {
+            bool on = false;
+            h263mi_framing_rects rc{};
+            uint32_t pad = 0;                          // R | G << 8 | B << 16
+            bool keep = false;
+        } framed;
         bool on() const { return scratch != nullptr; }
     } resize;
     // what a pointer into the caller's buffer must be a multiple of (a tensor: its element size)
@@ -126,22 +135,30 @@ int yuv_resize_extent(uint32_t n_streams, const h263mi_yuv_resize *r, uint64_t *
 // out; stride_n (may be null): the streams' distance in elements
 int tensor_extent(uint32_t n_streams, const h263mi_tensor_out *t, uint64_t *bytes, RgbaLayout::Resize::Tensor *out = nullptr,
                   uint64_t *stride_n = nullptr);
-// device memory a tensor output of `slots` pictures of w x h holds: always a scratch, whatever W' x H'
-uint64_t tensor_scratch_bytes(uint32_t w, uint32_t h, uint32_t slots, const h263mi_tensor_out &t);
+// h263mi_framing_resolve (f NULL: STRETCH); *whole (may be null): source whole and destination whole -- the unframed shape
+int framing_resolve(uint32_t w, uint32_t h, uint32_t ow, uint32_t oh, const h263mi_framing *f, h263mi_framing_rects *out, bool *whole = nullptr);
+// device memory a tensor output of `slots` pictures of w x h holds: always a scratch, whatever W' x H' (f: a framing that
+// resolves for w x h -- its span tables are those of the destination rectangle)
+uint64_t tensor_scratch_bytes(uint32_t w, uint32_t h, uint32_t slots, const h263mi_tensor_out &t, const h263mi_framing *f = nullptr);
 // the layout that a resize of a w x h picture is by definition (full size, or 1/2 or 1/4 of sizes that 2 or 4 divide), into
 // *lay (offsets and pitch copied); false: none, the resize needs k_rgba_resize
 bool resize_as_layout(uint32_t w, uint32_t h, const h263mi_rgba_resize &r, h263mi_rgba_layout *lay);
 // device memory a resize of `slots` pictures of w x h holds (0: it is a layout)
-uint64_t resize_scratch_bytes(uint32_t w, uint32_t h, uint32_t slots, const h263mi_rgba_resize &r);
+uint64_t resize_scratch_bytes(uint32_t w, uint32_t h, uint32_t slots, const h263mi_rgba_resize &r, const h263mi_framing *f = nullptr);
 
 // ---- the shapes, with the device memory they need, for n streams of w x h on `device`
 // h263mi_batch_set_rgba_layout's (NULL: the default); no device memory
 int make_rgba_layout_shape(uint32_t n, uint32_t w, uint32_t h, const h263mi_rgba_layout *layout, RgbaLayout &out);
 // the RGBA shape `r` (NULL: the default): the layout it is by definition, or the resize with a new scratch
-int make_output_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_rgba_resize *r, RgbaLayout &out);
+// f (h263mi_framing, NULL: none): a framing that resolves to the whole source and the whole destination is the unframed shape;
+// every other one is the resize with a scratch, followed by k_rgba_resize_framed
+int make_output_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_rgba_resize *r, RgbaLayout &out,
+                      const h263mi_framing *f = nullptr);
 // the tensor shape `t` (NULL: the default): always the resize with a new scratch -- W' = w, H' = h too, where the area average is
 // the identity -- followed by k_tensor_resize
-int make_tensor_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_tensor_out *t, RgbaLayout &out);
+// (f as make_output_shape: k_tensor_resize_framed)
+int make_tensor_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_tensor_out *t, RgbaLayout &out,
+                      const h263mi_framing *f = nullptr);
 // the layout (NULL: none, format 0), its offsets uploaded
 int make_yuv_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_yuv_layout *layout, YuvLayout &out);
 // the YUV shape `r` (NULL: none): the full-size layout it is by definition when W' = w and H' = h, else the resize with a new

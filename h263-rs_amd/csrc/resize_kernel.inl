@@ -183,4 +183,90 @@ H263_HD void resize_item(const ResizeArgs &a, ResizeLds &s, uint32_t band, uint3
     }
 }
 
+// ---------------------------------------------------------------------------------------
+// k_rgba_resize_framed: a source window of the picture into a destination rectangle of the W' x H' output (h263mi_framing).
+//
+// FramedResizeArgs::r describes the resize INSIDE the rectangle: r.ow x r.oh is dw x dh, the span tables have dw and dh
+// entries made over sw -> dw and sh -> dh with `first` offset by sx / sy, and r.d is sw*sh -- so phases 1 and 2 above run
+// unchanged on the full-size scratch at its real row stride (r.w; the 16-byte load path stays keyed on it: c0 = first & ~3
+// may start left of the window, on columns that are read, inside the picture, and never weighted).  The launch shape is that
+// of the W' x H' output (cw x ch here): a wave still owns 64 output columns x RESIZE_ROWS rows of it.  A row or a segment
+// wholly outside the rectangle skips phases 1 and 2 and stores the pad colour, or nothing with `keep`; lanes outside the
+// rectangle in a mixed wave carry the pad colour.  Every byte is written once.
+// ---------------------------------------------------------------------------------------
+struct FrameRect {
+    uint32_t cw, ch;             // the W' x H' output that the launch covers
+    uint32_t dx, dy;             // where the r.ow x r.oh rectangle lies in it: dx + r.ow <= cw, dy + r.oh <= ch
+    uint32_t pad;                // R | G << 8 | B << 16: the colour outside the rectangle
+    uint32_t keep;               // 1: nothing outside the rectangle is written
+};
+
+struct FramedResizeArgs {
+    ResizeArgs r;                // pitch, dst, bands and chunk are the OUTPUT's (bands = ceil(ch / RESIZE_ROWS))
+    FrameRect f;
+};
+
+// the columns of the rectangle that segment [X0, X1] holds: [xa, xb], empty (false) when xa > xb
+H263_HD bool frame_columns(const FrameRect &f, uint32_t dw, uint32_t X0, uint32_t X1, uint32_t &xa, uint32_t &xb)
+{
+    xa = X0 > f.dx ? X0 : f.dx;
+    xb = X1 < f.dx + dw - 1u ? X1 : f.dx + dw - 1u;
+    return xa <= xb;
+}
+
+// phases 1 and 2 of output row Y (a row of the rectangle) for the rectangle's columns [xa, xb] of a segment that starts at X0
+template <class Lane, class EachLane, class Sums>
+H263_HD void framed_phases(const ResizeArgs &a, const FrameRect &f, ResizeLds &s, const uint8_t *pic_src, uint32_t Y, uint32_t X0,
+                           uint32_t xa, uint32_t xb, EachLane each, Sums sums)
+{
+    const ResizeSpan rs = a.rows[Y - f.dy];
+    const ResizeSpan &ca = a.cols[xa - f.dx], &cb = a.cols[xb - f.dx];
+    const uint32_t c0 = ca.first & ~3u, c_end = cb.first + cb.count;
+    for (uint32_t c = c0; c < c_end; c += RESIZE_CHUNK) {
+        each([&](int lane, Lane &) { resize_phase_vertical(a, s, lane, pic_src, rs, c, c_end); });
+        wave_fence();
+        each([&](int lane, Lane &t) {
+            const uint32_t X = X0 + (uint32_t)lane;
+            const bool valid = X >= xa && X <= xb;
+            resize_phase_horizontal(a, s, sums(t), valid ? a.cols[X - f.dx] : cb, valid, c);
+        });
+        wave_fence();                                         // (the next chunk's column sums overwrite these)
+    }
+}
+
+template <class EachLane>
+H263_HD void framed_resize_item(const FramedResizeArgs &fa, ResizeLds &s, uint32_t band, uint32_t seg, uint32_t pic, EachLane each)
+{
+    const ResizeArgs &a = fa.r;
+    const FrameRect &f = fa.f;
+    uint8_t *const pic_dst = a.dst[pic];
+    if (!pic_dst) return;                                     // a stream with nothing to render: untouched
+    const uint8_t *const pic_src = a.src + (size_t)pic * a.w * a.h * 4u;
+    const uint32_t X0 = seg * 64u, X1 = (X0 + 64u < f.cw ? X0 + 64u : f.cw) - 1u;
+    uint32_t xa, xb;
+    const bool cols_in = frame_columns(f, a.ow, X0, X1, xa, xb);
+    if (!cols_in && f.keep) return;
+    const uint32_t Y0 = band * RESIZE_ROWS, Y1 = Y0 + RESIZE_ROWS < f.ch ? Y0 + RESIZE_ROWS : f.ch;
+    const uint32_t half = a.d >> 1;
+    for (uint32_t Y = Y0; Y < Y1; Y++) {
+        const bool row_in = cols_in && Y >= f.dy && Y < f.dy + a.oh;
+        if (!row_in && f.keep) continue;
+        if (row_in) {
+            each([&](int lane, ResizeLane &t) { t.acc[0] = t.acc[1] = t.acc[2] = 0; });
+            framed_phases<ResizeLane>(a, f, s, pic_src, Y, X0, xa, xb, each, [](ResizeLane &t) -> ResizeLane & { return t; });
+        }
+        each([&](int lane, ResizeLane &t) {
+            const uint32_t X = X0 + (uint32_t)lane;
+            if (X > X1) return;
+            const bool inside = row_in && X >= xa && X <= xb;
+            if (!inside && f.keep) return;
+            uint32_t px = f.pad;
+            if (inside)
+                px = resize_div(t.acc[0] + half, a.d, a.inv_d) | (resize_div(t.acc[1] + half, a.d, a.inv_d) << 8) |
+                     (resize_div(t.acc[2] + half, a.d, a.inv_d) << 16);
+            *reinterpret_cast<uint32_t *>(pic_dst + (size_t)Y * a.pitch + (size_t)X * 4u) = px | 0xff000000u;
+        });
+    }
+}
+
 }  // namespace h263mi

@@ -265,6 +265,7 @@ static int state_strength(const h263mi_state *s, uint8_t strength, h263mi_batch:
 
 // The last picture as W' x H' RGBA in `shape`: rendered with tight rows into the state's scratch (which holds them), then copied out
 // at the caller's pitch -- row by row when that is wider -- and waited for.
+// A framing with keep_outside writes its destination rectangle alone: that rectangle alone is copied out.
 static int render_rgba_shaped(h263mi_state *s, const h263mi_batch::Strengths &st, const h263mi_batch::RgbaLayout &shape, uint32_t ow,
                               uint32_t oh, uint64_t row_pitch, uint8_t *rgba)
 {
@@ -272,7 +273,12 @@ static int render_rgba_shaped(h263mi_state *s, const h263mi_batch::Strengths &st
     uint8_t *d = s->rgba.as<uint8_t>();
     RC_TRY(s->b->render(st, d, nullptr, false, nullptr, &shape));
     const size_t row = (size_t)ow * 4, pitch = row_pitch ? (size_t)row_pitch : row;
-    if (pitch == row) HIP_TRY(hipMemcpyAsync(rgba, d, row * oh, hipMemcpyDeviceToHost, on));
+    const h263mi_batch::RgbaLayout::Resize::Framed &fr = shape.resize.framed;
+    if (fr.on && fr.keep) {
+        const size_t at = (size_t)fr.rc.dst_x * 4;
+        HIP_TRY(hipMemcpy2DAsync(rgba + fr.rc.dst_y * pitch + at, pitch, d + fr.rc.dst_y * row + at, row, (size_t)fr.rc.dst_w * 4, fr.rc.dst_h,
+                                 hipMemcpyDeviceToHost, on));
+    } else if (pitch == row) HIP_TRY(hipMemcpyAsync(rgba, d, row * oh, hipMemcpyDeviceToHost, on));
     else HIP_TRY(hipMemcpy2DAsync(rgba, pitch, d, row, row, oh, hipMemcpyDeviceToHost, on));
     HIP_TRY(hipStreamSynchronize(on));
     return H263MI_OK;
@@ -332,11 +338,19 @@ int h263mi_render_rgba_layout(const h263mi_state *cs, uint8_t strength, const h2
 
 int h263mi_render_rgba_resize(const h263mi_state *cs, uint8_t strength, const h263mi_rgba_resize *r, uint8_t *rgba)
 {
+    return h263mi_render_rgba_resize_framed(cs, strength, r, nullptr, rgba);
+}
+
+int h263mi_render_rgba_resize_framed(const h263mi_state *cs, uint8_t strength, const h263mi_rgba_resize *r, const h263mi_framing *f,
+                                     uint8_t *rgba)
+{
     h263mi_state *s = const_cast<h263mi_state *>(cs);
     if (!s || !rgba || !r || r->offsets) return H263MI_ERR_INVALID_ARGUMENT;
     if (!s->has_last || !s->b) return H263MI_ERR_NO_PICTURE;
     h263mi_batch *b = s->b;
     RC_TRY(rgba_resize_extent(1, r, nullptr));
+    h263mi_framing_rects rects;
+    RC_TRY(framing_resolve(b->L.width, b->L.height, r->out_width, r->out_height, f, &rects));
     h263mi_batch::Strengths st;
     RC_TRY(state_strength(s, strength, st));
     DeviceGuard g(s->cfg.device_id);
@@ -344,11 +358,16 @@ int h263mi_render_rgba_resize(const h263mi_state *cs, uint8_t strength, const h2
     h263mi_rgba_resize tight = *r;
     tight.row_pitch = 0;
     h263mi_batch::RgbaLayout shape;            // (its scratch, if any, goes at the end, once the copy out has waited for it)
-    RC_TRY(make_output_shape(s->cfg.device_id, 1, b->L.width, b->L.height, &tight, shape));
+    RC_TRY(make_output_shape(s->cfg.device_id, 1, b->L.width, b->L.height, &tight, shape, f));
     return render_rgba_shaped(s, st, shape, r->out_width, r->out_height, r->row_pitch, rgba);
 }
 
 int h263mi_render_tensor(const h263mi_state *cs, uint8_t strength, const h263mi_tensor_out *t, void *out)
+{
+    return h263mi_render_tensor_framed(cs, strength, t, nullptr, out);
+}
+
+int h263mi_render_tensor_framed(const h263mi_state *cs, uint8_t strength, const h263mi_tensor_out *t, const h263mi_framing *f, void *out)
 {
     h263mi_state *s = const_cast<h263mi_state *>(cs);
     if (!s || !out || !t) return H263MI_ERR_INVALID_ARGUMENT;
@@ -357,6 +376,8 @@ int h263mi_render_tensor(const h263mi_state *cs, uint8_t strength, const h263mi_
     // the caller's shape: where its planes lie in `out`
     h263mi_batch::RgbaLayout::Resize::Tensor host;
     RC_TRY(tensor_extent(1, t, nullptr, &host));
+    h263mi_framing_rects rects;
+    RC_TRY(framing_resolve(b->L.width, b->L.height, t->out_width, t->out_height, f, &rects));
     h263mi_batch::Strengths st;
     RC_TRY(state_strength(s, strength, st));
     DeviceGuard g(s->cfg.device_id);
@@ -367,13 +388,18 @@ int h263mi_render_tensor(const h263mi_state *cs, uint8_t strength, const h263mi_
     const size_t row = (size_t)t->out_width * host.elt, plane = row * t->out_height;
     RC_TRY(s->rgba.reserve(s->cfg.device_id, 3 * plane));
     h263mi_batch::RgbaLayout shape;            // (its scratch goes at the end, once the copies out have waited for it)
-    RC_TRY(make_tensor_shape(s->cfg.device_id, 1, b->L.width, b->L.height, &tight, shape));
+    RC_TRY(make_tensor_shape(s->cfg.device_id, 1, b->L.width, b->L.height, &tight, shape, f));
     const uint8_t *d = s->rgba.as<uint8_t>();
     RC_TRY(b->render(st, s->rgba.as<uint8_t>(), nullptr, false, nullptr, &shape));
     const hipStream_t on = b->stream;
+    // (a framing with keep_outside writes its destination rectangle alone: that rectangle alone is copied out)
+    const bool rect_only = shape.resize.framed.on && shape.resize.framed.keep;
+    const size_t x0 = rect_only ? rects.dst_x : 0, y0 = rect_only ? rects.dst_y : 0;
+    const size_t cols = rect_only ? rects.dst_w : t->out_width, rows_out = rect_only ? rects.dst_h : t->out_height;
     for (size_t p = 0; p < 3; p++)
-        HIP_TRY(hipMemcpy2DAsync(static_cast<uint8_t *>(out) + p * host.stride_c * host.elt, host.stride_h * host.elt, d + p * plane, row,
-                                 row, t->out_height, hipMemcpyDeviceToHost, on));
+        HIP_TRY(hipMemcpy2DAsync(static_cast<uint8_t *>(out) + (p * host.stride_c + y0 * host.stride_h + x0) * host.elt,
+                                 host.stride_h * host.elt, d + p * plane + y0 * row + x0 * host.elt, row, cols * host.elt, rows_out,
+                                 hipMemcpyDeviceToHost, on));
     HIP_TRY(hipStreamSynchronize(on));
     return H263MI_OK;
 }

@@ -199,4 +199,85 @@ H263_HD void tensor_resize_item(const TensorArgs &a, ResizeLds &s, uint32_t band
     }
 }
 
+// ---------------------------------------------------------------------------------------
+// k_tensor_resize_framed: k_rgba_resize_framed (resize_kernel.inl: FrameRect, the meaning of t.r) ending in the tensor's stores.
+// The pad colour is a `u` like any other: it is scaled, biased and converted by the same code, and for the 16-bit types it goes
+// through the same LDS hand-off as the picture's values, so a pair that straddles the rectangle's edge still leaves as one
+// 32-bit store.  With `keep` only the columns [wa, wb] of the rectangle may be written: a pair needs both elements in that
+// range, the first of the range at an odd address leaves alone -- an element outside is never written, whatever the base
+// alignment, stride_h, dx and dw are.
+// ---------------------------------------------------------------------------------------
+struct FramedTensorArgs {
+    TensorArgs t;
+    FrameRect f;
+};
+
+// tensor_phase_store16 for the columns [wa, wb] of a row: the lane at a dword address stores its element and its right
+// neighbour's as one word where the neighbour is in the range and in the wave
+H263_HD void framed_phase_store16(const TensorArgs &a, const ResizeLds &s, const TensorLane &t, int lane, uint8_t *pic_dst, uint32_t X,
+                                  uint32_t wa, uint32_t wb, uint32_t Y)
+{
+    if (X < wa || X > wb) return;
+    for (uint32_t p = 0; p < 3; p++) {
+        const uint32_t c = a.bgr ? 2u - p : p;
+        uint8_t *const at = tensor_at(a, pic_dst, p, Y, X, 2);
+        if (((uintptr_t)at & 2u) == 0) {
+            if (lane < 63 && X < wb) *reinterpret_cast<uint32_t *>(at) = tensor_pack16(a.dtype, t.v[c], s.v[c][lane + 1]);
+            else *reinterpret_cast<uint16_t *>(at) = (uint16_t)tensor_cvt16(a.dtype, t.v[c]);
+        } else if (lane == 0 || X == wa) {
+            *reinterpret_cast<uint16_t *>(at) = (uint16_t)tensor_cvt16(a.dtype, t.v[c]);
+        }
+        // (every other element at an odd address left with the lane to its left: that one is in the range and in the wave)
+    }
+}
+
+template <class EachLane>
+H263_HD void framed_tensor_item(const FramedTensorArgs &fa, ResizeLds &s, uint32_t band, uint32_t seg, uint32_t pic, EachLane each)
+{
+    const TensorArgs &a = fa.t;
+    const ResizeArgs &r = a.r;
+    const FrameRect &f = fa.f;
+    uint8_t *const pic_dst = r.dst[pic];
+    if (!pic_dst) return;                                     // a stream with nothing to render: untouched
+    const uint8_t *const pic_src = r.src + (size_t)pic * r.w * r.h * 4u;
+    const uint32_t X0 = seg * 64u, X1 = (X0 + 64u < f.cw ? X0 + 64u : f.cw) - 1u;
+    uint32_t xa, xb;
+    const bool cols_in = frame_columns(f, r.ow, X0, X1, xa, xb);
+    if (!cols_in && f.keep) return;
+    const uint32_t Y0 = band * RESIZE_ROWS, Y1 = Y0 + RESIZE_ROWS < f.ch ? Y0 + RESIZE_ROWS : f.ch;
+    for (uint32_t Y = Y0; Y < Y1; Y++) {
+        const bool row_in = cols_in && Y >= f.dy && Y < f.dy + r.oh;
+        if (!row_in && f.keep) continue;
+        if (row_in) {
+            each([&](int lane, TensorLane &t) { t.sums.acc[0] = t.sums.acc[1] = t.sums.acc[2] = 0; });
+            framed_phases<TensorLane>(r, f, s, pic_src, Y, X0, xa, xb, each, [](TensorLane &t) -> ResizeLane & { return t.sums; });
+        }
+        // the columns this row writes
+        const uint32_t wa = f.keep ? xa : X0, wb = f.keep ? xb : X1;
+        auto value = [&](int lane, TensorLane &t) {
+            const uint32_t X = X0 + (uint32_t)lane;
+            if (row_in && X >= xa && X <= xb) {
+                tensor_phase_value(a, t);
+            } else {
+                for (int c = 0; c < 3; c++) t.v[c] = tensor_bits_of(tensor_value((f.pad >> (8 * c)) & 0xffu, a.scale[c], a.bias[c]));
+            }
+        };
+        if (a.dtype == TENSOR_F32) {
+            each([&](int lane, TensorLane &t) {
+                const uint32_t X = X0 + (uint32_t)lane;
+                value(lane, t);
+                tensor_phase_store32(a, t, pic_dst, X, Y, X >= wa && X <= wb);
+            });
+        } else {
+            each([&](int lane, TensorLane &t) {
+                value(lane, t);
+                for (int c = 0; c < 3; c++) s.v[c][lane] = t.v[c];
+            });
+            wave_fence();
+            each([&](int lane, TensorLane &t) { framed_phase_store16(a, s, t, lane, pic_dst, X0 + (uint32_t)lane, wa, wb, Y); });
+            wave_fence();                                     // (the next row's column sums overwrite the values)
+        }
+    }
+}
+
 }  // namespace h263mi

@@ -98,7 +98,12 @@ EXPORTS = [
     "h263mi_mixed_digest_yuv",
     # ABI 7, additive: the picture as a normalised planar float tensor (f32 / f16 / bf16) for inference
     "h263mi_tensor_extent", "h263mi_batch_set_tensor_output", "h263mi_render_tensor", "h263mi_mixed_set_tensor_output",
+    # ABI 7, additive: aspect-preserving framing (letterbox, cover, window) of the resized RGBA and of the tensor
+    "h263mi_framing_resolve", "h263mi_batch_set_rgba_resize_framed", "h263mi_batch_set_tensor_output_framed",
+    "h263mi_render_rgba_resize_framed", "h263mi_render_tensor_framed", "h263mi_mixed_set_rgba_resize_framed",
+    "h263mi_mixed_set_tensor_output_framed", "h263mi_mixed_stream_framing",
 ]
+FRAME_STRETCH, FRAME_LETTERBOX, FRAME_COVER, FRAME_WINDOW = 0, 1, 2, 3
 TENSOR_F32, TENSOR_F16, TENSOR_BF16 = 0, 1, 2
 TENSOR_NUMPY_DTYPE = {TENSOR_F32: np.float32, TENSOR_F16: np.float16, TENSOR_BF16: np.uint16}     # (bfloat16: bit patterns)
 YUV_I420, YUV_NV12 = 0, 1
@@ -218,6 +223,50 @@ def tensor_extent(n_streams, tensor):
     nb = C.c_uint64()
     _check(lib().h263mi_tensor_extent(n_streams, C.byref(tensor) if tensor is not None else None, C.byref(nb)), "tensor_extent")
     return nb.value
+
+
+class Framing(C.Structure):
+    """h263mi_framing: which rectangle of the picture fills which rectangle of the W' x H' output (FRAME_*), the colour around
+    it (pad: R, G, B) or keep_outside; the rectangles are given under FRAME_WINDOW only."""
+    _fields_ = [("mode", C.c_uint8), ("keep_outside", C.c_uint8), ("pad", C.c_uint8 * 3), ("reserved", C.c_uint8 * 3),
+                ("src_x", C.c_uint16), ("src_y", C.c_uint16), ("src_w", C.c_uint16), ("src_h", C.c_uint16),
+                ("dst_x", C.c_uint16), ("dst_y", C.c_uint16), ("dst_w", C.c_uint16), ("dst_h", C.c_uint16)]
+
+
+class FramingRects(C.Structure):
+    """h263mi_framing_rects: the resolved source and destination rectangles"""
+    _fields_ = [(n, C.c_uint16) for n in ("src_x", "src_y", "src_w", "src_h", "dst_x", "dst_y", "dst_w", "dst_h")]
+
+    def src(self):
+        return (self.src_x, self.src_y, self.src_w, self.src_h)
+
+    def dst(self):
+        return (self.dst_x, self.dst_y, self.dst_w, self.dst_h)
+
+
+def make_framing(mode=FRAME_STRETCH, pad=(0, 0, 0), keep_outside=False, src=None, dst=None):
+    """-> Framing; src / dst: (x, y, w, h) of FRAME_WINDOW"""
+    f = Framing()
+    f.mode, f.keep_outside = mode, 1 if keep_outside else 0
+    f.pad = (C.c_uint8 * 3)(*[int(v) for v in pad])
+    if src is not None:
+        f.src_x, f.src_y, f.src_w, f.src_h = src
+    if dst is not None:
+        f.dst_x, f.dst_y, f.dst_w, f.dst_h = dst
+    return f
+
+
+def _opt(struct):
+    return C.byref(struct) if struct is not None else None
+
+
+def framing_resolve(width, height, out_width, out_height, framing=None):
+    """h263mi_framing_resolve -> FramingRects of a width x height picture in an out_width x out_height output (no device);
+    H263Error when the framing is refused.  A position of the output maps back to the source as
+    x = src_x + (X - dst_x) * src_w / dst_w, y = src_y + (Y - dst_y) * src_h / dst_h."""
+    rc = FramingRects()
+    _check(lib().h263mi_framing_resolve(width, height, out_width, out_height, _opt(framing), C.byref(rc)), "framing_resolve")
+    return rc
 
 
 class YuvLayout(C.Structure):
@@ -524,6 +573,15 @@ def lib():
         L.h263mi_batch_set_tensor_output.argtypes = [vp, vp]
         L.h263mi_render_tensor.argtypes = [vp, u8, vp, vp]
         L.h263mi_mixed_set_tensor_output.argtypes = [vp, vp]
+        u16 = C.c_uint16
+        L.h263mi_framing_resolve.argtypes = [u16, u16, u16, u16, vp, vp]
+        L.h263mi_batch_set_rgba_resize_framed.argtypes = [vp, vp, vp]
+        L.h263mi_batch_set_tensor_output_framed.argtypes = [vp, vp, vp]
+        L.h263mi_render_rgba_resize_framed.argtypes = [vp, u8, vp, vp, vp]
+        L.h263mi_render_tensor_framed.argtypes = [vp, u8, vp, vp, vp]
+        L.h263mi_mixed_set_rgba_resize_framed.argtypes = [vp, vp, vp]
+        L.h263mi_mixed_set_tensor_output_framed.argtypes = [vp, vp, vp]
+        L.h263mi_mixed_stream_framing.argtypes = [vp, u32, vp]
         _lib = L
     return _lib
 
@@ -723,6 +781,22 @@ class H263State:
     def render_rgba_resize_into(self, strength, out, out_width, out_height, row_pitch=0):
         r, _ = make_rgba_resize(out_width, out_height, row_pitch)
         _check(lib().h263mi_render_rgba_resize(self._h, strength, C.byref(r), _p(out)), "render_rgba_resize")
+        return out
+
+    def render_rgba_resize_framed_into(self, strength, out, framing, out_width, out_height, row_pitch=0):
+        """h263mi_render_rgba_resize_framed into `out`: with keep_outside its bytes outside the destination rectangle stay"""
+        r, _ = make_rgba_resize(out_width, out_height, row_pitch)
+        _check(lib().h263mi_render_rgba_resize_framed(self._h, strength, C.byref(r), _opt(framing), _p(out)), "render_rgba_resize_framed")
+        return out
+
+    def render_rgba_resize_framed(self, strength, framing, out_width, out_height, row_pitch=0):
+        """h263mi_render_rgba_resize_framed: H' * pitch bytes (what no store reaches is zero here)"""
+        out = np.zeros(rgba_resize_extent(1, out_width, out_height, row_pitch), np.uint8)
+        return self.render_rgba_resize_framed_into(strength, out, framing, out_width, out_height, row_pitch)
+
+    def render_tensor_framed_into(self, strength, tensor, framing, out):
+        """h263mi_render_tensor_framed into `out` (an array whose first byte is the tensor's base)"""
+        _check(lib().h263mi_render_tensor_framed(self._h, strength, C.byref(tensor), _opt(framing), _p(out)), "render_tensor_framed")
         return out
 
     def render_tensor(self, strength, tensor):
@@ -1050,6 +1124,16 @@ class Batch:
         _check(lib().h263mi_batch_set_rgba_resize(self._h, C.byref(r)), "batch_set_rgba_resize")
         del keep
 
+    def set_rgba_resize_framed(self, framing, out_width, out_height, row_pitch=0, offsets=None):
+        """h263mi_batch_set_rgba_resize_framed (framing: a Framing, None = the plain resize)"""
+        r, keep = make_rgba_resize(out_width, out_height, row_pitch, offsets)
+        _check(lib().h263mi_batch_set_rgba_resize_framed(self._h, C.byref(r), _opt(framing)), "batch_set_rgba_resize_framed")
+        del keep
+
+    def set_tensor_output_framed(self, tensor, framing):
+        """h263mi_batch_set_tensor_output_framed (tensor None: back to the default output; framing None: the plain tensor)"""
+        _check(lib().h263mi_batch_set_tensor_output_framed(self._h, _opt(tensor), _opt(framing)), "batch_set_tensor_output_framed")
+
     def set_tensor_output(self, tensor=None):
         """h263mi_batch_set_tensor_output: d_rgba of the later calls is the base of the tensor `tensor` (a TensorOut; None: back
         to today's output)"""
@@ -1176,6 +1260,21 @@ class MixedBatch:
             return
         r, _ = make_rgba_resize(out_width, out_height, row_pitch)
         _check(lib().h263mi_mixed_set_rgba_resize(self._h, C.byref(r)), "mixed_set_rgba_resize")
+
+    def set_rgba_resize_framed(self, framing, out_width, out_height, row_pitch=0):
+        """h263mi_mixed_set_rgba_resize_framed: LETTERBOX / COVER resolved per size class (FRAME_WINDOW is refused)"""
+        r, _ = make_rgba_resize(out_width, out_height, row_pitch)
+        _check(lib().h263mi_mixed_set_rgba_resize_framed(self._h, C.byref(r), _opt(framing)), "mixed_set_rgba_resize_framed")
+
+    def set_tensor_output_framed(self, tensor, framing):
+        """h263mi_mixed_set_tensor_output_framed (tensor None: full-size RGBA again)"""
+        _check(lib().h263mi_mixed_set_tensor_output_framed(self._h, _opt(tensor), _opt(framing)), "mixed_set_tensor_output_framed")
+
+    def stream_framing(self, stream):
+        """h263mi_mixed_stream_framing -> FramingRects of the stream's picture size under the shape in force"""
+        rc = FramingRects()
+        _check(lib().h263mi_mixed_stream_framing(self._h, stream, C.byref(rc)), "mixed_stream_framing")
+        return rc
 
     def set_tensor_output(self, tensor=None):
         """h263mi_mixed_set_tensor_output: every stream as the 3 x H' x W' tensor `tensor` (stride_n 0) at its own buffer (None:

@@ -170,6 +170,24 @@ public:
         check(h263mi_render_tensor(s_, strength, &t, out.data()));
         return out;
     }
+    // the same under a framing (h263mi_framing: letterbox, cover or window; nullptr: the plain call).  With keep_outside the
+    // bytes outside the destination rectangle are the zeros these vectors start with.
+    std::vector<uint8_t> render_rgba_resize_framed(uint8_t strength, const h263mi_rgba_resize &r, const h263mi_framing *f) const
+    {
+        uint64_t bytes = 0;
+        check(h263mi_rgba_resize_extent(1, &r, &bytes));
+        std::vector<uint8_t> rgba((size_t)bytes);
+        check(h263mi_render_rgba_resize_framed(s_, strength, &r, f, rgba.data()));
+        return rgba;
+    }
+    std::vector<uint8_t> render_tensor_framed(uint8_t strength, const h263mi_tensor_out &t, const h263mi_framing *f) const
+    {
+        uint64_t bytes = 0;
+        check(h263mi_tensor_extent(1, &t, &bytes));
+        std::vector<uint8_t> out((size_t)bytes);
+        check(h263mi_render_tensor_framed(s_, strength, &t, f, out.data()));
+        return out;
+    }
     // the deblocked planes of the last picture as I420 or NV12 (h263mi_yuv_layout; nullptr: tightly packed I420), without
     // going through RGBA: the layout's extent in bytes, the ones outside the planes zero
     std::vector<uint8_t> render_yuv(uint8_t strength, const h263mi_yuv_layout *layout = nullptr) const
@@ -374,6 +392,16 @@ public:
     void set_rgba_resize(const h263mi_rgba_resize *r) { check(h263mi_mixed_set_rgba_resize(m_, r)); }
     // every stream written as the 3 x H' x W' tensor `t` (stride_n 0) at its own buffer; nullptr = full-size RGBA again
     void set_tensor_output(const h263mi_tensor_out *t) { check(h263mi_mixed_set_tensor_output(m_, t)); }
+    // the same under a framing resolved per picture size (LETTERBOX, COVER; WINDOW is refused); nullptr framing: the plain call
+    void set_rgba_resize_framed(const h263mi_rgba_resize *r, const h263mi_framing *f) { check(h263mi_mixed_set_rgba_resize_framed(m_, r, f)); }
+    void set_tensor_output_framed(const h263mi_tensor_out *t, const h263mi_framing *f) { check(h263mi_mixed_set_tensor_output_framed(m_, t, f)); }
+    // the rectangles of the stream's picture size under the shape in force: maps a position of its output back to its source
+    h263mi_framing_rects stream_framing(uint32_t stream) const
+    {
+        h263mi_framing_rects rc{};
+        check(h263mi_mixed_stream_framing(m_, stream, &rc));
+        return rc;
+    }
     uint64_t frame_store_bytes() const { return h263mi_mixed_frame_store_bytes(m_); }
     // per stream zlib's adler32(Y + Cb + Cr of its last picture, seed), nullopt for a stream without a picture; one launch pair
     // per picture size

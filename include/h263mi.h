@@ -471,6 +471,56 @@ int h263mi_batch_set_tensor_output(h263mi_batch *b, const h263mi_tensor_out *t);
 int h263mi_render_tensor(const h263mi_state *s, uint8_t strength, const h263mi_tensor_out *t, void *out);
 
 /*
+ * ASPECT-PRESERVING FRAMING OF A RESIZED OUTPUT (additive, ABI 7): which rectangle of the picture goes into which rectangle of
+ * the W' x H' output of h263mi_rgba_resize or h263mi_tensor_out -- a letterbox, a centre crop ("cover") or any window.
+ * With F the full-size RGBA of the picture (h263mi_render_rgba at the same strength) and the resolved rectangles
+ * (sx, sy, sw, sh) of F and (dx, dy, dw, dh) of the output: inside the destination rectangle the output is the area average of
+ * h263mi_rgba_resize of the sw x sh picture F[sy : sy+sh, sx : sx+sw] to dw x dh (its formula with w, h, W', H' replaced by
+ * sw, sh, dw, dh: divisor sw*sh, one rounding), placed at (dx, dy).  Outside it every pixel is `pad` (RGBA: alpha 255), or is
+ * not written at all with keep_outside.  For a tensor every u, pad included, becomes fl32(fl32(u * scale[c]) + bias[c]) and is
+ * converted as h263mi_tensor_out documents.  Extents, placement and alignment are those of the unframed output: the framing
+ * changes what is written inside the W' x H' rectangle, not where that rectangle lies.
+ * The rules, exact integer arithmetic with rnd(a, b) = (2a + b) div 2b, for a w x h picture:
+ *   STRETCH    source whole, destination whole (the unframed output)
+ *   LETTERBOX  source whole; w*H' >= h*W': dw = W', dh = clamp(rnd(h*W', w), 1, H'); else dh = H', dw = clamp(rnd(w*H', h), 1, W');
+ *              dx = (W' - dw) div 2, dy = (H' - dh) div 2
+ *   COVER      destination whole; w*H' >= h*W': sh = h, sw = clamp(rnd(h*W', H'), 1, w); else sw = w, sh = clamp(rnd(w*H', W'), 1, h);
+ *              sx = (w - sw) div 2, sy = (h - sh) div 2
+ *   WINDOW     both rectangles as given
+ * A framing that resolves to the whole source and the whole destination IS the unframed shape (the same launches, the same
+ * bytes, the fused 1/2 and 1/4 layouts included); every other one renders the full-size pictures into the device scratch of the
+ * resize and resamples from there.
+ */
+#define H263MI_FRAME_STRETCH   0
+#define H263MI_FRAME_LETTERBOX 1
+#define H263MI_FRAME_COVER     2
+#define H263MI_FRAME_WINDOW    3
+typedef struct h263mi_framing {
+    uint8_t  mode;            /* H263MI_FRAME_* */
+    uint8_t  keep_outside;    /* 1: nothing outside the destination rectangle is written; 0: it is filled with pad */
+    uint8_t  pad[3];          /* R, G, B, 0..255: for a tensor a `u` that goes through scale / bias like any other */
+    uint8_t  reserved[3];     /* zero */
+    uint16_t src_x, src_y, src_w, src_h;   /* WINDOW only (else 0): the source rectangle, in pixels of the full-size RGBA */
+    uint16_t dst_x, dst_y, dst_w, dst_h;   /* WINDOW only (else 0): the rectangle of the W' x H' output that it fills */
+} h263mi_framing;
+typedef struct h263mi_framing_rects { uint16_t src_x, src_y, src_w, src_h, dst_x, dst_y, dst_w, dst_h; } h263mi_framing_rects;
+/* Pure host function, no HIP call: the rectangles that `f` (NULL: STRETCH) comes to for a w x h picture and a W' x H' output --
+ * the validation of a framing, and the mapping of a position in the output back to the source:
+ *     x_src = src_x + (x_out - dst_x) * src_w / dst_w,    y_src = src_y + (y_out - dst_y) * src_h / dst_h.
+ * H263MI_ERR_INVALID_ARGUMENT: out NULL; a size of 0; a mode above 3; keep_outside above 1; a reserved byte set; a rectangle
+ * field set outside WINDOW; under WINDOW an extent of 0 or a rectangle that does not lie inside its picture. */
+int h263mi_framing_resolve(uint16_t w, uint16_t h, uint16_t out_w, uint16_t out_h, const h263mi_framing *f, h263mi_framing_rects *out);
+/* The setters and renderings of h263mi_rgba_resize and h263mi_tensor_out with a framing (f NULL: the plain call; r or t NULL:
+ * the default shape, f is not looked at).  They replace, and are replaced by, every other shape of d_rgba; a refused setter
+ * leaves the shape in force untouched.  A deferred rendering of H263MI_CFG_PIPELINE_POST keeps the framing of its request
+ * (copied).  H263MI_ERR_INVALID_ARGUMENT as h263mi_framing_resolve for the batch's picture size. */
+int h263mi_batch_set_rgba_resize_framed(h263mi_batch *b, const h263mi_rgba_resize *r, const h263mi_framing *f);
+int h263mi_batch_set_tensor_output_framed(h263mi_batch *b, const h263mi_tensor_out *t, const h263mi_framing *f);
+/* One state, into HOST memory.  With keep_outside the caller's bytes outside the destination rectangle are untouched. */
+int h263mi_render_rgba_resize_framed(const h263mi_state *s, uint8_t strength, const h263mi_rgba_resize *r, const h263mi_framing *f, uint8_t *rgba);
+int h263mi_render_tensor_framed(const h263mi_state *s, uint8_t strength, const h263mi_tensor_out *t, const h263mi_framing *f, void *out);
+
+/*
  * DEBLOCKED YUV 4:2:0 OUTPUT LAYOUT (additive, ABI 7): where the filtered planes go inside d_deblocked.  The planes are always
  * full size (w x h luma, cw x ch chroma, cw = ceil(w/2), ch = ceil(h/2)) under a layout -- h263mi_yuv_resize below resizes them --;
  * the RGBA layouts and resizes above apply to d_rgba only and the two shapes are independent.  I420: three planes Y, Cb, Cr.  NV12: a Y plane and one plane of ch rows of cw
@@ -766,6 +816,15 @@ int h263mi_mixed_set_rgba_resize(h263mi_mixed *m, const h263mi_rgba_resize *r);
  * h263mi_tensor_extent(1, t) (else that stream's H263MI_ERR_INVALID_ARGUMENT).  Replaces h263mi_mixed_set_rgba_resize and is
  * replaced by it.  Every class keeps the scratch of its full-size pictures, slots * w*h*4 bytes, counted as the resize's. */
 int h263mi_mixed_set_tensor_output(h263mi_mixed *m, const h263mi_tensor_out *t);
+/* The same with a framing (h263mi_framing; f NULL: the plain call): LETTERBOX and COVER are resolved per size class when the
+ * class is made, so every size keeps its own aspect ratio inside the one W' x H'; WINDOW is H263MI_ERR_INVALID_ARGUMENT (a
+ * source rectangle has no meaning across sizes).  A class whose framing is not the unframed shape keeps the scratch of its
+ * full-size pictures, counted as above. */
+int h263mi_mixed_set_rgba_resize_framed(h263mi_mixed *m, const h263mi_rgba_resize *r, const h263mi_framing *f);
+int h263mi_mixed_set_tensor_output_framed(h263mi_mixed *m, const h263mi_tensor_out *t, const h263mi_framing *f);
+/* The rectangles of stream `stream`'s picture size under the shape in force (h263mi_framing_resolve of its w x h; without a
+ * resize or tensor: the whole picture onto itself).  H263MI_ERR_NO_PICTURE: the stream has no picture yet. */
+int h263mi_mixed_stream_framing(const h263mi_mixed *m, uint32_t stream, h263mi_framing_rects *out);
 /* DecodedPicture::as_yuv of stream `stream`'s last picture: tightly packed planes to HOST memory */
 int h263mi_mixed_copy_yuv(h263mi_mixed *m, uint32_t stream, uint8_t *y, uint8_t *cb, uint8_t *cr);
 /* H263State::new for one stream: it forgets its pictures and its size */
