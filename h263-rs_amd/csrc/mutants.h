@@ -20,6 +20,13 @@
 //                                            with shifts like its SIMD lanes
 //   -DH263MI_MUTATE_DEBLOCK_WRAP_COLUMNS     post_phase_hedges hands hfilter2 the strip column, not the picture column: the
 //                                            columns that ride in the last tile (post_tile_columns) miss the horizontal edges
+// ... and three of the reconstruction waves' bookkeeping (tests/test_gpu_mutation.py with tests/wave_mutation_probe.py):
+//   -DH263MI_MUTATE_KILL_IGNORED             recon_phase_mark takes `killed` as 0: a coded block whose run walked past position
+//                                            63 (rle.rs:125-127) goes through the IDCT with the LEVELs of its pool slot
+//   -DH263MI_MUTATE_STATIC_IGNORES_MOTION    recon_wave_is_static ignores any_moving: eight uncoded inter macroblocks are
+//                                            copied from the reference whatever their vectors are
+//   -DH263MI_MUTATE_UNCODED_INTRA_DC         recon_phase_mark takes dc_nonzero as 0: an uncoded block of an intra macroblock
+//                                            is never activated and stays at zero (the Dc class of rle.rs:151-160 is lost)
 // Two parts.  The switches need nothing and are included by post_kernel.inl and recon_kernel.inl; the IDCT helper is included
 // by recon_kernel.inl (which defines H263MI_MUTANTS_WITH_IDCT) behind the definitions it uses (f32x2, splat2, BasisPtr,
 // basis_pair).
@@ -68,6 +75,21 @@ constexpr bool kDeblockFloorEverywhere = false;
 constexpr bool kDeblockWrapColumns = true;
 #else
 constexpr bool kDeblockWrapColumns = false;
+#endif
+#if defined(H263MI_MUTATE_KILL_IGNORED)
+constexpr bool kKillIgnored = true;
+#else
+constexpr bool kKillIgnored = false;
+#endif
+#if defined(H263MI_MUTATE_STATIC_IGNORES_MOTION)
+constexpr bool kStaticIgnoresMotion = true;
+#else
+constexpr bool kStaticIgnoresMotion = false;
+#endif
+#if defined(H263MI_MUTATE_UNCODED_INTRA_DC)
+constexpr bool kUncodedIntraDc = true;
+#else
+constexpr bool kUncodedIntraDc = false;
 #endif
 
 }  // namespace mutants

@@ -521,9 +521,9 @@ H263_DEV TaskInfo recon_phase_mark(const ReconArgs &, ReconWave &s, int lane, co
     // never comes out of a parser and is refused by every host entry point.)
     const uint32_t intra = (0x18u >> (mb_type & 31u)) & 1u, inter_type = (0x27u >> (mb_type & 31u)) & 1u;
     const uint32_t ck = (w0 >> 16) >> blk;                                    // bit 0: coded, bit 8: killed
-    const uint32_t coded = ck & 1u, killed = (ck >> 8) & 1u;
+    const uint32_t coded = ck & 1u, killed = mutants::kKillIgnored ? 0u : (ck >> 8) & 1u;     // (mutants.h: false in the product)
     const uint32_t dcb = (uint32_t)((((uint64_t)w6 << 32) | w5) >> (8u * blk)) & 0xffu;
-    const uint32_t dc_nonzero = (dcb + 255u) >> 8, dc_is_ff = (dcb + 1u) >> 8;
+    const uint32_t dc_nonzero = mutants::kUncodedIntraDc ? 0u : (dcb + 255u) >> 8, dc_is_ff = (dcb + 1u) >> 8;     // (mutants.h)
     // number of this block among the macroblock's coded blocks -> its place in the pool
     const uint32_t idx = w7 + (uint32_t)popc32((w0 >> 16) & ((1u << blk) - 1u) & 0x3fu);
     const uint32_t worst = w7 > idx ? w7 : idx;                               // (idx may have wrapped)
@@ -1176,7 +1176,7 @@ H263_DEV void recon_phase_predict(const ReconArgs &a, ReconWave &s, WaveFetch &f
 // copy path of gather_block, gather.rs:63-79).
 H263_HD bool recon_wave_is_static(const ReconArgs &a, const WaveMasks &km, bool any_moving)
 {
-    return a.has_ref && km.act == 0 && km.valid == 0xffu && km.inter == 0xffu && !any_moving;
+    return a.has_ref && km.act == 0 && km.valid == 0xffu && km.inter == 0xffu && (mutants::kStaticIgnoresMotion || !any_moving);     // (mutants.h)
 }
 
 H263_DEV void recon_phase_copy(const ReconArgs &a, int lane, const WavePos &p)

@@ -7,6 +7,8 @@
 // measures nothing.
 #include <stdlib.h>
 
+#include <vector>
+
 #include "../../h263-rs_amd/csrc/post_kernel.inl"
 #include "../../h263-rs_amd/csrc/recon_kernel.inl"
 #include "../../h263-rs_amd/csrc/synth.inl"
@@ -78,6 +80,27 @@ void sim_no_integer_short_cut(int on) { no_integer_short_cut = on; }
 static uint64_t integer_waves[2] = {0, 0};
 void sim_integer_waves(uint64_t out[2]) { out[0] = integer_waves[0]; out[1] = integer_waves[1]; }
 
+// What the driver below decided for every wave of the last sim_recon[_ex] call (tests/test_sim_wave_sweep.py holds it against
+// the anatomy tests/wave_cases.py works out from the records alone).  Sixteen words per wave, in the order the waves ran.
+enum : uint32_t { ROUND_NONE = 0, ROUND_GENERAL = 1, ROUND_DENSE = 2, ROUND_WIDE = 3 };
+struct WaveStat {
+    uint32_t pic, mby, group;              // which wave: picture, macroblock row, group of 8 macroblocks
+    uint32_t valid, n_active;              // the valid mask; the number of block tasks that went through the IDCT
+    uint32_t is_static;                    // 1: the copy path (recon_wave_is_static), 2: ... taken from an empty group word alone
+    uint32_t mc, all_inter;                // the recon_tail<MC> instantiation; recon_phase_predict's all_inter (0 for a static wave)
+    uint32_t group_word;                   // the word of the sparse record index the wave used (0: dense records)
+    uint32_t n_rounds;
+    uint32_t form[6];                      // per round: ROUND_*
+};
+static std::vector<WaveStat> wave_stats;
+uint32_t sim_wave_stats(uint32_t *out, uint32_t cap_waves)
+{
+    const uint32_t n = (uint32_t)wave_stats.size();
+    for (uint32_t i = 0; i < n && i < cap_waves; i++) memcpy(out + 16 * i, &wave_stats[i], sizeof(WaveStat));
+    return n;
+}
+static_assert(sizeof(WaveStat) == 64, "sixteen words");
+
 void sim_layout(uint32_t w, uint32_t h, FrameLayout *out) { *out = make_layout(w, h); }
 
 // block_first_event / events: sparse coefficient transport consumed by the reconstruction wave itself (nullptr: dense)
@@ -123,6 +146,7 @@ int sim_recon_ex(uint32_t w, uint32_t h, uint32_t n_pictures, const MbRecord *mb
     // order of units does not matter)
     const uint32_t tpp = a.tiles_x * a.tiles_y, total = tpp * n_pictures, chunk = (total + 7) / 8;
     static WaveFetch f[64];
+    wave_stats.clear();
     for (uint32_t wg = 0; wg < chunk * 8; wg++) {
         const uint32_t xcd = wg & 7, t = wg >> 3, g = xcd * chunk + t;
         if (t >= chunk || g >= total) continue;
@@ -136,8 +160,14 @@ int sim_recon_ex(uint32_t w, uint32_t h, uint32_t n_pictures, const MbRecord *mb
             p.cbase = a.coeff_base ? a.coeff_base[p.pic] : 0ull;
             memset(s, 0xA5, sizeof *s);   // LDS is not zero-initialised on the device either
             const uint32_t group_word = recon_group_word(a, p);
+            WaveStat ws{};
+            ws.pic = (uint32_t)p.pic; ws.mby = (uint32_t)p.mby; ws.group = (uint32_t)(p.mbx0 >> 3);
+            ws.valid = recon_valid_mask(a, p);
+            ws.group_word = group_word;
             if (a.mb_group_index && (group_word & 0xffu) == 0 && a.has_ref && recon_valid_mask(a, p) == 0xffu) {   // as kernels.hip::recon_wave
                 for (int l = 0; l < 64; l++) recon_phase_copy(a, l, p);
+                ws.is_static = 2;
+                wave_stats.push_back(ws);
                 continue;
             }
             for (int l = 0; l < 64; l++) recon_phase_load(a, *s, l, p, group_word);
@@ -159,11 +189,16 @@ int sim_recon_ex(uint32_t w, uint32_t h, uint32_t n_pictures, const MbRecord *mb
             for (int l = 0; l < 64; l++) recon_phase_compact(*s, l, ti[l], km.act);
             bool any_moving = false;
             for (int l = 0; l < 64; l++) any_moving = any_moving || ti[l].moving;
+            ws.n_active = (uint32_t)recon_n_active(km);
             if (recon_wave_is_static(a, km, any_moving)) {  // as kernels.hip::recon_wave
                 for (int l = 0; l < 64; l++) recon_phase_copy(a, l, p);
+                ws.is_static = 1;
+                wave_stats.push_back(ws);
                 continue;
             }
             const bool mc = a.has_ref && km.inter;          // the dispatch of kernels.hip: recon_tail<MC>
+            ws.mc = mc;
+            ws.all_inter = mc && a.has_ref && km.inter == km.valid && km.valid == 0xffu;     // as recon_phase_predict<true>
             for (int l = 0; l < 64; l++) {
                 if (mc) recon_phase_fetch<true>(a, *s, f[l], l, p, km);
                 else recon_phase_fetch<false>(a, *s, f[l], l, p, km);
@@ -176,6 +211,7 @@ int sim_recon_ex(uint32_t w, uint32_t h, uint32_t n_pictures, const MbRecord *mb
                 uint32_t wm = 0, rm = 0;
                 uint64_t rows_any = 0, cols_any = 0;
                 bool any_special = false;
+                bool dense = false;
                 if (n_active > 0) {
                     // (sparse transport: the three steps of coeff_rows_from_events each over all lanes)
                     for (int stage = a.events ? 0 : 2; stage < 3; stage++)
@@ -189,11 +225,19 @@ int sim_recon_ex(uint32_t w, uint32_t h, uint32_t n_pictures, const MbRecord *mb
                     bool wide = false;                                      // as kernels.hip: recon_round_rows
                     for (int l = 0; l < 64; l++) wide = wide || ri[l].wide != 0;
                     if (force_wide_rounds) wide = true;
+                    // the dense round: not wide, and a non-zero LEVEL in columns 6..7 of EVERY lane's coefficient row (one
+                    // ballot on the device); it takes the <true> instantiations of both passes, with the arguments of
+                    // kernels.hip: recon_round_rows / recon_round_cols
+                    dense = !wide;
+                    for (int l = 0; l < 64; l++) dense = dense && ri[l].w[3] != 0;
                     for (int l = 0; l < 64; l++) {
-                        if (wide) recon_phase_idct_rows<false, true>(*s, ri[l], l, cols_from_mask(wm), cols_any);
+                        if (dense) recon_phase_idct_rows<true>(*s, ri[l], l, 8, ~0ull);
+                        else if (wide) recon_phase_idct_rows<false, true>(*s, ri[l], l, cols_from_mask(wm), cols_any);
                         else recon_phase_idct_rows(*s, ri[l], l, cols_from_mask(wm), cols_any);
                     }
                     for (int l = 0; l < 64; l++) any_special = any_special || recon_block_is_special(ri[l], l, rows_any, cols_any);
+                    if (ws.n_rounds < 6) ws.form[ws.n_rounds] = dense ? ROUND_DENSE : (wide ? ROUND_WIDE : ROUND_GENERAL);
+                    ws.n_rounds++;
                 }
                 if (round == 0) {
                     // the two reductions over the lanes' vectors that the device makes with ballots (recon_phase_predict)
@@ -210,8 +254,12 @@ int sim_recon_ex(uint32_t w, uint32_t h, uint32_t n_pictures, const MbRecord *mb
                     }
                 }
                 if (n_active > 0)
-                    for (int l = 0; l < 64; l++) recon_phase_idct_cols(*s, ri[l], l, rows_from_mask(rm), rows_any, cols_any, any_special, /*strip_is_zero=*/!mc);
+                    for (int l = 0; l < 64; l++) {
+                        if (dense) recon_phase_idct_cols<true>(*s, ri[l], l, 8, ~0ull, ~0ull, false, /*strip_is_zero=*/!mc);
+                        else recon_phase_idct_cols(*s, ri[l], l, rows_from_mask(rm), rows_any, cols_any, any_special, /*strip_is_zero=*/!mc);
+                    }
             }
+            wave_stats.push_back(ws);
             for (int l = 0; l < 64; l++) recon_phase_store(a, *s, l, p, km);
         }
     }

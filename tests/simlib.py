@@ -24,7 +24,8 @@ _libs = {}
 
 def lib(asan=False, variant=None):
     """variant: "blend" / "intborder" = the checker built with that motion-compensation mutation, "dbhalf" / "dbfloor" /
-    "dbwrap" = with that mutation of the post-filter (csrc/mutants.h)"""
+    "dbwrap" = with that mutation of the post-filter, "killkeep" / "staticmv" / "intradc" = with that mutation of the
+    reconstruction waves' bookkeeping (csrc/mutants.h)"""
     name = "libh263mi_sim_%s.so" % variant if variant else ("libh263mi_sim_asan.so" if asan else "libh263mi_sim.so")
     if name not in _libs:
         subprocess.check_call(["make", "-C", SIM_DIR, "-s", name])
@@ -37,8 +38,25 @@ def lib(asan=False, variant=None):
                                C.c_int]
         L.sim_synth_picture.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
                                         C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.sim_wave_stats.argtypes = [C.c_void_p, C.c_uint32]
+        L.sim_wave_stats.restype = C.c_uint32
         _libs[name] = L
     return _libs[name]
+
+
+ROUND_NONE, ROUND_GENERAL, ROUND_DENSE, ROUND_WIDE = range(4)
+WAVE_STAT_DTYPE = np.dtype([(n, "<u4") for n in ("pic", "mby", "group", "valid", "n_active", "is_static", "mc", "all_inter",
+                                                 "group_word", "n_rounds")] + [("form", "<u4", (6,))])
+
+
+def wave_stats(asan=False, variant=None):
+    """what the checker's driver decided for every wave of its last sim_recon[_ex] call (sim.cpp: WaveStat), in the order
+    the waves ran: is_static 1 = the copy path after the mark phase, 2 = taken from an empty group word; form = ROUND_*"""
+    L = lib(asan, variant)
+    n = L.sim_wave_stats(None, 0)
+    out = np.zeros(n, WAVE_STAT_DTYPE)
+    assert L.sim_wave_stats(_p(out), n) == n
+    return out
 
 
 def layout(w, h):

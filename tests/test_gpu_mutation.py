@@ -15,7 +15,13 @@ Three more are of the DEBLOCKING POST-FILTER (csrc/mutants.h; probe and models: 
   libh263mi_dbhalf.so     |d1 / 2| rounds toward zero where the reference shifts a negative d1
   libh263mi_dbfloor.so    the scalar tails of the reference divide with shifts like its SIMD lanes
   libh263mi_dbwrap.so     the columns that ride in the last post tile miss the horizontal block edges
-Likewise: each differs from the oracle and equals, on every byte, the numpy restatement with that mutation switched on."""
+Likewise: each differs from the oracle and equals, on every byte, the numpy restatement with that mutation switched on.
+
+Three more are of the BOOKKEEPING of the reconstruction waves (csrc/mutants.h; probe and models: tests/wave_mutation_probe.py):
+  libh263mi_killkeep.so   the mark phase ignores the kill bits
+  libh263mi_staticmv.so   eight uncoded inter macroblocks are copied from the reference whatever their vectors are
+  libh263mi_intradc.so    uncoded blocks of intra macroblocks are not activated
+Each has an exact model -- the oracle over edited records -- and must equal it on every byte, through k_recon and k_frame."""
 import json
 import os
 import subprocess
@@ -240,3 +246,53 @@ def test_post_probe_through_the_product_build_is_clean(tmp_path, post_probe_orac
     clean = _post_probe(os.path.join(PKG, "libh263mi.so"), tmp_path, "product")
     names, n = probe.compare(clean, post_probe_oracle)
     assert n == 0, "the product build: %d bytes differ, in %s" % (n, names[:5])
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the mutants of the reconstruction waves' bookkeeping
+# ---------------------------------------------------------------------------------------------------------------
+def _wave_probe(lib_path, tmp_path, name):
+    out = str(tmp_path / (name + ".npz"))
+    env = dict(os.environ, H263MI_LIB=lib_path)
+    subprocess.run([sys.executable, os.path.join(HERE, "wave_mutation_probe.py"), out], env=env, check=True, timeout=300)
+    return np.load(out)
+
+
+@pytest.fixture(scope="module")
+def wave_probe_oracle():
+    import wave_mutation_probe as probe
+    return probe.expectations()
+
+
+@pytest.mark.parametrize("mutant", ["killkeep", "staticmv", "intradc"])
+def test_wave_mutant_build_fails_exactly_as_its_model_predicts(mutant, tmp_path, wave_probe_oracle):
+    """the probe pictures of tests/wave_mutation_probe.py through a mutant build (child process), by k_recon and by k_frame: every
+    byte must be the one the mutation's model -- the oracle over edited records -- predicts, every picture must differ from the
+    oracle, and only in the blocks the anatomy names"""
+    import wave_cases as wc
+    import wave_mutation_probe as probe
+    lib = os.path.join(PKG, "mutants", "libh263mi_%s.so" % mutant)
+    if not os.path.exists(lib):                                  # normally built by __graft_entry__.build()
+        subprocess.check_call(["make", "-C", PKG, "-s", "mutants"])
+    got = _wave_probe(lib, tmp_path, mutant)
+    wrong = 0
+    for (name, pic, want), (_, _, predicted) in zip(wave_probe_oracle, probe.expectations(mutant)):
+        for path in ("state", "frame"):
+            planes = tuple(got["%s_%s_%d" % (path, name, i)] for i in range(3))
+            diff = wc.first_difference(pic, planes, predicted)
+            assert diff is None, "the %s mutant (got, %s) against its model (expected), picture %s: %s" % (mutant, path, name, diff)
+            where = wc.differing_blocks(pic, planes, want)
+            assert where, "the %s mutant went unnoticed on picture %s (%s)" % (mutant, name, path)
+            assert where <= probe.predicted_blocks(pic, mutant), (mutant, name, path, sorted(where - probe.predicted_blocks(pic, mutant))[:5])
+            wrong += len(where)
+    print("%s mutant: %d blocks differ from the oracle; all as its model predicts" % (mutant, wrong))
+
+
+def test_wave_probe_through_the_product_build_is_clean(tmp_path, wave_probe_oracle):
+    """the same child-process path with the product library: every byte is the oracle's"""
+    import wave_cases as wc
+    clean = _wave_probe(os.path.join(PKG, "libh263mi.so"), tmp_path, "product")
+    for name, pic, want in wave_probe_oracle:
+        for path in ("state", "frame"):
+            diff = wc.first_difference(pic, tuple(clean["%s_%s_%d" % (path, name, i)] for i in range(3)), want)
+            assert diff is None, "the product build (%s), picture %s: %s" % (path, name, diff)
