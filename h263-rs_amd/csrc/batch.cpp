@@ -112,6 +112,33 @@ int h263mi_batch::launch_resize(const RgbaLayout::Resize &rz, const std::vector<
     bool any = false;
     for (int8_t v : sets) any = any || v >= 0;
     if (!any) return H263MI_OK;
+    if (rz.filter.on) {                        // Pillow's bilinear / bicubic in the place of the area average (k_rgba_filter, k_tensor_filter)
+        const h263mi_framing_rects &rc = rz.framed.rc;
+        TensorFilterArgs fa{};
+        FilterArgs &a = fa.fl;
+        a.src = rz.scratch->pixels.as<uint8_t>();
+        a.dst = d_dst;
+        filter_axes(rz.scratch->spans.p, rc.dst_w, rc.dst_h, rz.filter.ksx, rz.filter.ksy, a.x, a.y);
+        a.w = L.width, a.h = L.height, a.dw = rc.dst_w, a.dh = rc.dst_h;
+        a.pitch = rz.pitch;
+        a.n_pictures = n;
+        a.f.cw = rz.ow, a.f.ch = rz.oh, a.f.dx = rc.dst_x, a.f.dy = rc.dst_y;
+        a.f.pad = rz.framed.pad;
+        a.f.keep = rz.framed.keep ? 1u : 0u;
+        if (!launch_rgba_filter || !launch_tensor_filter) return H263MI_ERR_HIP;       // (kernels.h: only a stub runtime lacks them)
+        RC_TRY(time_begin(3, on));
+        if (rz.tensor.on) {
+            for (int c = 0; c < 3; c++) fa.t.scale[c] = rz.tensor.scale[c], fa.t.bias[c] = rz.tensor.bias[c];
+            fa.t.dtype = rz.tensor.dtype;
+            fa.t.bgr = rz.tensor.bgr;
+            fa.t.stride_c = rz.tensor.stride_c;
+            fa.t.stride_h = rz.tensor.stride_h;
+            HIP_TRY(launch_tensor_filter(fa, on));
+        } else {
+            HIP_TRY(launch_rgba_filter(a, on));
+        }
+        return H263MI_OK;
+    }
     ResizeArgs a{};
     a.src = rz.scratch->pixels.as<uint8_t>();
     a.dst = d_dst;
@@ -1011,6 +1038,26 @@ int h263mi_batch_set_tensor_output_framed(h263mi_batch *b, const h263mi_tensor_o
     if (!b) return H263MI_ERR_INVALID_ARGUMENT;
     h263mi_batch::RgbaLayout lay;
     RC_TRY(make_tensor_shape(b->device, b->n, b->L.width, b->L.height, t, lay, f));
+    DeviceGuard g(b->device);
+    b->layout = std::move(lay);
+    return H263MI_OK;
+}
+
+int h263mi_batch_set_rgba_resize_filtered(h263mi_batch *b, const h263mi_rgba_resize *r, const h263mi_framing *f, const h263mi_filter *filter)
+{
+    if (!b) return H263MI_ERR_INVALID_ARGUMENT;
+    h263mi_batch::RgbaLayout lay;
+    RC_TRY(make_output_shape(b->device, b->n, b->L.width, b->L.height, r, lay, f, filter));
+    DeviceGuard g(b->device);                  // (a shape it replaces frees its scratch, unless a pending rendering holds it)
+    b->layout = std::move(lay);
+    return H263MI_OK;
+}
+
+int h263mi_batch_set_tensor_output_filtered(h263mi_batch *b, const h263mi_tensor_out *t, const h263mi_framing *f, const h263mi_filter *filter)
+{
+    if (!b) return H263MI_ERR_INVALID_ARGUMENT;
+    h263mi_batch::RgbaLayout lay;
+    RC_TRY(make_tensor_shape(b->device, b->n, b->L.width, b->L.height, t, lay, f, filter));
     DeviceGuard g(b->device);
     b->layout = std::move(lay);
     return H263MI_OK;

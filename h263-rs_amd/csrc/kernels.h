@@ -5,6 +5,7 @@
 
 #include "dev_common.h"
 #include "digest_kernel.inl"
+#include "filter_kernel.inl"
 #include "plane_resize_kernel.inl"
 #include "resize_kernel.inl"
 #include "tensor_resize_kernel.inl"
@@ -58,6 +59,11 @@ hipError_t launch_tensor_resize(const TensorArgs &args, hipStream_t stream) __at
 // launch_rgba_resize; the host refuses a framed shape without them.
 hipError_t launch_rgba_resize_framed(const FramedResizeArgs &args, hipStream_t stream) __attribute__((weak));
 hipError_t launch_tensor_resize_framed(const FramedTensorArgs &args, hipStream_t stream) __attribute__((weak));
+// k_rgba_filter / k_tensor_filter (h263mi_filter: bilinear, bicubic; filter_kernel.inl): args.f is the W' x H' output that the
+// launch covers and the place of the args.dw x args.dh rectangle in it (bands and chunk are set here).  Weak like
+// launch_rgba_resize; the host refuses a filtered shape without them.
+hipError_t launch_rgba_filter(const FilterArgs &args, hipStream_t stream) __attribute__((weak));
+hipError_t launch_tensor_filter(const TensorFilterArgs &args, hipStream_t stream) __attribute__((weak));
 // k_plane_resize over args.n_pictures pictures (plane_resize_kernel.inl; bands, chunk and segs_y are set here): the luma and
 // chroma planes of every picture in ONE launch.  Weak like launch_rgba_resize; h263mi_batch::launch_plane_resize refuses to run
 // without it.

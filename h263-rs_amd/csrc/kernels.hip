@@ -5,6 +5,7 @@
 #include "digest_kernel.inl"
 #include "post_kernel.inl"
 #include "recon_kernel.inl"
+#include "filter_kernel.inl"
 #include "plane_resize_kernel.inl"
 #include "resize_kernel.inl"
 #include "tensor_resize_kernel.inl"
@@ -854,6 +855,65 @@ hipError_t launch_tensor_resize_framed(const FramedTensorArgs &args, hipStream_t
     a.t.r.chunk = (a.t.r.bands + 7) / 8;
     const dim3 grid(a.t.r.chunk * 8, a.t.r.n_pictures, (a.f.cw + 63) / 64);
     hipLaunchKernelGGL(k_tensor_resize_framed, grid, dim3(64), 0, stream, a);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
+// k_rgba_filter, k_tensor_filter: Pillow's bilinear / bicubic resampling of a source window into a destination rectangle of the
+// W' x H' output, both passes in one kernel (h263mi_filter; filter_kernel.inl).  One instantiation each serves the framed and
+// the unframed shapes.  The launch shape is that of the framed resizes over the W' x H' output: one wave per workgroup, no
+// barrier, blockIdx.y = picture, blockIdx.z = segment of 64 output columns, blockIdx.x = band of FILTER_ROWS rows in XCD order.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_rgba_filter(FilterArgs a)
+{
+    __shared__ __attribute__((aligned(16))) FilterLds lds;
+    const uint32_t band = (blockIdx.x & 7u) * a.chunk + (blockIdx.x >> 3);
+    if (band >= a.bands) return;
+    const int lane = threadIdx.x & 63;
+    FilterLane t;
+    filter_rgba_item(a, lds, band, blockIdx.z, blockIdx.y, [&](auto f) { f(lane, t); });
+}
+
+__global__ __launch_bounds__(64) void k_tensor_filter(TensorFilterArgs a)
+{
+    __shared__ __attribute__((aligned(16))) FilterLds lds;
+    const uint32_t band = (blockIdx.x & 7u) * a.fl.chunk + (blockIdx.x >> 3);
+    if (band >= a.fl.bands) return;
+    const int lane = threadIdx.x & 63;
+    TensorFilterLane t;
+    filter_tensor_item(a, lds, band, blockIdx.z, blockIdx.y, [&](auto f) { f(lane, t); });
+}
+
+// what a filter launch must hold before a wave runs: tables, a rectangle that is not empty and lies inside the output, a source
+// picture
+static bool filter_args_ok(const FilterArgs &a)
+{
+    const FrameRect &f = a.f;
+    return a.src && a.dst && a.x.span && a.x.coeff && a.y.span && a.y.coeff && a.x.ksize && a.y.ksize && a.w && a.h && a.dw && a.dh &&
+           f.cw && f.ch && f.keep <= 1 && f.dx <= f.cw && a.dw <= f.cw - f.dx && f.dy <= f.ch && a.dh <= f.ch - f.dy && a.n_pictures <= 65535;
+}
+
+hipError_t launch_rgba_filter(const FilterArgs &args, hipStream_t stream)
+{
+    if (!args.n_pictures) return hipSuccess;
+    if (!filter_args_ok(args)) return hipErrorInvalidValue;
+    FilterArgs a = args;
+    a.bands = (a.f.ch + FILTER_ROWS - 1) / FILTER_ROWS;
+    a.chunk = (a.bands + 7) / 8;
+    const dim3 grid(a.chunk * 8, a.n_pictures, (a.f.cw + 63) / 64);
+    hipLaunchKernelGGL(k_rgba_filter, grid, dim3(64), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_tensor_filter(const TensorFilterArgs &args, hipStream_t stream)
+{
+    if (!args.fl.n_pictures) return hipSuccess;
+    if (!filter_args_ok(args.fl) || args.t.dtype > TENSOR_BF16) return hipErrorInvalidValue;
+    TensorFilterArgs a = args;
+    a.fl.bands = (a.fl.f.ch + FILTER_ROWS - 1) / FILTER_ROWS;
+    a.fl.chunk = (a.fl.bands + 7) / 8;
+    const dim3 grid(a.fl.chunk * 8, a.fl.n_pictures, (a.fl.f.cw + 63) / 64);
+    hipLaunchKernelGGL(k_tensor_filter, grid, dim3(64), 0, stream, a);
     return hipGetLastError();
 }
 

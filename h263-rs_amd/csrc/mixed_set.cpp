@@ -69,6 +69,8 @@ struct h263mi_mixed {
     // h263mi_mixed_set_*_framed: the framing of the resize or tensor in force (never WINDOW), resolved per size class
     bool framed = false;
     h263mi_framing framing{};
+    // h263mi_mixed_set_*_filtered: the filter of the resize or tensor in force (AREA: none); every class has its own tap tables
+    h263mi_filter filter{};
     ~h263mi_mixed()
     {
         pool.reset();                           // the host threads first
@@ -77,20 +79,20 @@ struct h263mi_mixed {
     // a class's frame store, and the scratch of its full-size pictures while a resize that is not a layout is in force, or a
     // tensor (which always has one)
     static uint64_t class_bytes(uint32_t w, uint32_t h, uint32_t slots, const h263mi_rgba_resize *rz, const h263mi_tensor_out *t = nullptr,
-                                const h263mi_framing *f = nullptr)
+                                const h263mi_framing *f = nullptr, const h263mi_filter *flt = nullptr)
     {
         return 2ull * slots * make_layout(w, h).frame_bytes +
-               (t ? tensor_scratch_bytes(w, h, slots, *t, f) : (rz ? resize_scratch_bytes(w, h, slots, *rz, f) : 0));
+               (t ? tensor_scratch_bytes(w, h, slots, *t, f, flt) : (rz ? resize_scratch_bytes(w, h, slots, *rz, f, flt) : 0));
     }
     uint64_t slots_bytes(uint32_t w, uint32_t h, uint32_t slots) const
     {
-        return class_bytes(w, h, slots, resized ? &resize : nullptr, tensored ? &tensor : nullptr, framed ? &framing : nullptr);
+        return class_bytes(w, h, slots, resized ? &resize : nullptr, tensored ? &tensor : nullptr, framed ? &framing : nullptr, &filter);
     }
     // the output shape in force for a class of `slots` slots of w x h (each slot placed by its own pointer)
     int class_shape(uint32_t slots, uint32_t w, uint32_t h, h263mi_batch::RgbaLayout &out) const
     {
-        if (tensored) return make_tensor_shape(cfg.device_id, slots, w, h, &tensor, out, framed ? &framing : nullptr);
-        return make_output_shape(cfg.device_id, slots, w, h, resized ? &resize : nullptr, out, framed ? &framing : nullptr);
+        if (tensored) return make_tensor_shape(cfg.device_id, slots, w, h, &tensor, out, framed ? &framing : nullptr, &filter);
+        return make_output_shape(cfg.device_id, slots, w, h, resized ? &resize : nullptr, out, framed ? &framing : nullptr, &filter);
     }
     uint64_t store_bytes() const
     {
@@ -278,20 +280,26 @@ int h263mi_mixed_set_rgba_resize(h263mi_mixed *m, const h263mi_rgba_resize *r) {
 
 int h263mi_mixed_set_rgba_resize_framed(h263mi_mixed *m, const h263mi_rgba_resize *r, const h263mi_framing *f)
 {
+    return h263mi_mixed_set_rgba_resize_filtered(m, r, f, nullptr);
+}
+
+int h263mi_mixed_set_rgba_resize_filtered(h263mi_mixed *m, const h263mi_rgba_resize *r, const h263mi_framing *f, const h263mi_filter *flt)
+{
     if (!m || (r && r->offsets)) return H263MI_ERR_INVALID_ARGUMENT;
     if (r) RC_TRY(rgba_resize_extent(1, r, nullptr));
-    if (!r) f = nullptr;
+    if (!r) f = nullptr, flt = nullptr;
+    RC_TRY(filter_kind(flt));
     if (r) RC_TRY(mixed_framing_ok(f, r->out_width, r->out_height));
     DeviceGuard g(m->cfg.device_id);
     if (!g.ok) return H263MI_ERR_NO_DEVICE;
     // every class's new shape first (the scratches they need count against the limit), then all of them at once
     uint64_t total = 0;
     for (const h263mi_mixed::SizeClass &c : m->classes)
-        if (c.b) total += h263mi_mixed::class_bytes(c.w, c.h, c.b->n, r, nullptr, f);
+        if (c.b) total += h263mi_mixed::class_bytes(c.w, c.h, c.b->n, r, nullptr, f, flt);
     if (m->limit_bytes && total > m->limit_bytes) return H263MI_ERR_OUT_OF_MEMORY;
     std::vector<h263mi_batch::RgbaLayout> shapes(m->classes.size());
     for (size_t k = 0; k < m->classes.size(); k++)
-        if (m->classes[k].b) RC_TRY(make_output_shape(m->cfg.device_id, m->classes[k].b->n, m->classes[k].w, m->classes[k].h, r, shapes[k], f));
+        if (m->classes[k].b) RC_TRY(make_output_shape(m->cfg.device_id, m->classes[k].b->n, m->classes[k].w, m->classes[k].h, r, shapes[k], f, flt));
     for (size_t k = 0; k < m->classes.size(); k++)
         if (m->classes[k].b) m->classes[k].b->layout = std::move(shapes[k]);
     m->resized = r != nullptr;
@@ -299,6 +307,7 @@ int h263mi_mixed_set_rgba_resize_framed(h263mi_mixed *m, const h263mi_rgba_resiz
     m->tensored = false;
     m->framed = f != nullptr;
     m->framing = f ? *f : h263mi_framing{};
+    m->filter = flt ? *flt : h263mi_filter{};
     return H263MI_OK;
 }
 
@@ -306,21 +315,27 @@ int h263mi_mixed_set_tensor_output(h263mi_mixed *m, const h263mi_tensor_out *t) 
 
 int h263mi_mixed_set_tensor_output_framed(h263mi_mixed *m, const h263mi_tensor_out *t, const h263mi_framing *f)
 {
+    return h263mi_mixed_set_tensor_output_filtered(m, t, f, nullptr);
+}
+
+int h263mi_mixed_set_tensor_output_filtered(h263mi_mixed *m, const h263mi_tensor_out *t, const h263mi_framing *f, const h263mi_filter *flt)
+{
     if (!m || (t && t->stride_n)) return H263MI_ERR_INVALID_ARGUMENT;
     uint64_t one = 0;
     if (t) RC_TRY(tensor_extent(1, t, &one));
-    if (!t) f = nullptr;
+    if (!t) f = nullptr, flt = nullptr;
+    RC_TRY(filter_kind(flt));
     if (t) RC_TRY(mixed_framing_ok(f, t->out_width, t->out_height));
     DeviceGuard g(m->cfg.device_id);
     if (!g.ok) return H263MI_ERR_NO_DEVICE;
     // every class's new shape first (the scratches they need count against the limit), then all of them at once
     uint64_t total = 0;
     for (const h263mi_mixed::SizeClass &c : m->classes)
-        if (c.b) total += h263mi_mixed::class_bytes(c.w, c.h, c.b->n, nullptr, t, f);
+        if (c.b) total += h263mi_mixed::class_bytes(c.w, c.h, c.b->n, nullptr, t, f, flt);
     if (m->limit_bytes && total > m->limit_bytes) return H263MI_ERR_OUT_OF_MEMORY;
     std::vector<h263mi_batch::RgbaLayout> shapes(m->classes.size());
     for (size_t k = 0; k < m->classes.size(); k++)
-        if (m->classes[k].b) RC_TRY(make_tensor_shape(m->cfg.device_id, m->classes[k].b->n, m->classes[k].w, m->classes[k].h, t, shapes[k], f));
+        if (m->classes[k].b) RC_TRY(make_tensor_shape(m->cfg.device_id, m->classes[k].b->n, m->classes[k].w, m->classes[k].h, t, shapes[k], f, flt));
     for (size_t k = 0; k < m->classes.size(); k++)
         if (m->classes[k].b) m->classes[k].b->layout = std::move(shapes[k]);
     m->tensored = t != nullptr;
@@ -330,6 +345,7 @@ int h263mi_mixed_set_tensor_output_framed(h263mi_mixed *m, const h263mi_tensor_o
     m->resize = h263mi_rgba_resize{};
     m->framed = f != nullptr;
     m->framing = f ? *f : h263mi_framing{};
+    m->filter = flt ? *flt : h263mi_filter{};
     return H263MI_OK;
 }
 

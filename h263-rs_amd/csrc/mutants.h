@@ -27,6 +27,11 @@
 //                                            copied from the reference whatever their vectors are
 //   -DH263MI_MUTATE_UNCODED_INTRA_DC         recon_phase_mark takes dc_nonzero as 0: an uncoded block of an intra macroblock
 //                                            is never activated and stays at zero (the Dc class of rle.rs:151-160 is lost)
+// ... and two of the bilinear / bicubic resampling (filter_kernel.inl), which the CPU checker alone is built with
+// (tests/test_sim_filter.py):
+//   -DH263MI_MUTATE_FILTER_SINGLE_ROUNDING   the horizontal pass hands on its unrounded sum: one weighted sum, one rounding
+//   -DH263MI_MUTATE_FILTER_NO_CLAMP          the horizontal pass keeps the low 8 bits of a value outside 0..255 instead of
+//                                            clamping it
 // Two parts.  The switches need nothing and are included by post_kernel.inl and recon_kernel.inl; the IDCT helper is included
 // by recon_kernel.inl (which defines H263MI_MUTANTS_WITH_IDCT) behind the definitions it uses (f32x2, splat2, BasisPtr,
 // basis_pair).
@@ -90,6 +95,16 @@ constexpr bool kStaticIgnoresMotion = false;
 constexpr bool kUncodedIntraDc = true;
 #else
 constexpr bool kUncodedIntraDc = false;
+#endif
+#if defined(H263MI_MUTATE_FILTER_SINGLE_ROUNDING)
+constexpr bool kFilterSingleRounding = true;
+#else
+constexpr bool kFilterSingleRounding = false;
+#endif
+#if defined(H263MI_MUTATE_FILTER_NO_CLAMP)
+constexpr bool kFilterNoClamp = true;
+#else
+constexpr bool kFilterNoClamp = false;
 #endif
 
 }  // namespace mutants

@@ -2,6 +2,8 @@
 // placement, and the device memory a shape needs.
 #include "output_shape.h"
 
+#include "filter_taps.h"
+
 #include <algorithm>
 #include <cmath>
 #include <new>
@@ -304,8 +306,31 @@ static bool framed_rects(uint32_t w, uint32_t h, uint32_t ow, uint32_t oh, const
     return f && framing_resolve(w, h, ow, oh, f, rc, &whole) == H263MI_OK && !whole;
 }
 
-uint64_t tensor_scratch_bytes(uint32_t w, uint32_t h, uint32_t slots, const h263mi_tensor_out &t, const h263mi_framing *f)
+int filter_kind(const h263mi_filter *flt, uint32_t *kind)
 {
+    if (kind) *kind = H263MI_FILTER_AREA;
+    if (!flt) return H263MI_OK;
+    if (flt->kind > H263MI_FILTER_BICUBIC) return H263MI_ERR_INVALID_ARGUMENT;
+    for (uint8_t r : flt->reserved)
+        if (r) return H263MI_ERR_INVALID_ARGUMENT;
+    if (kind) *kind = flt->kind;
+    return H263MI_OK;
+}
+
+// the bytes of the tap tables of `flt` (not AREA) for w x h -> ow x oh under `f` (NULL: none), which must resolve
+static uint64_t filter_table_bytes(uint32_t w, uint32_t h, uint32_t ow, uint32_t oh, const h263mi_framing *f, uint32_t kind)
+{
+    h263mi_framing_rects rc;
+    if (framing_resolve(w, h, ow, oh, f, &rc) != H263MI_OK) return 0;
+    return 4 * filter_table_words(kind, rc.src_w, rc.src_h, rc.dst_w, rc.dst_h);
+}
+
+uint64_t tensor_scratch_bytes(uint32_t w, uint32_t h, uint32_t slots, const h263mi_tensor_out &t, const h263mi_framing *f,
+                              const h263mi_filter *flt)
+{
+    uint32_t kind = H263MI_FILTER_AREA;
+    if (filter_kind(flt, &kind) == H263MI_OK && kind != H263MI_FILTER_AREA)
+        return (uint64_t)slots * w * h * 4 + filter_table_bytes(w, h, t.out_width, t.out_height, f, kind);
     h263mi_framing_rects rc;
     const uint64_t spans = framed_rects(w, h, t.out_width, t.out_height, f, &rc) ? (uint64_t)rc.dst_w + rc.dst_h
                                                                                  : (uint64_t)t.out_width + t.out_height;
@@ -324,8 +349,12 @@ bool resize_as_layout(uint32_t w, uint32_t h, const h263mi_rgba_resize &r, h263m
     return false;
 }
 
-uint64_t resize_scratch_bytes(uint32_t w, uint32_t h, uint32_t slots, const h263mi_rgba_resize &r, const h263mi_framing *f)
+uint64_t resize_scratch_bytes(uint32_t w, uint32_t h, uint32_t slots, const h263mi_rgba_resize &r, const h263mi_framing *f,
+                              const h263mi_filter *flt)
 {
+    uint32_t kind = H263MI_FILTER_AREA;
+    if (filter_kind(flt, &kind) == H263MI_OK && kind != H263MI_FILTER_AREA)
+        return (uint64_t)slots * w * h * 4 + filter_table_bytes(w, h, r.out_width, r.out_height, f, kind);
     h263mi_rgba_layout lay;
     h263mi_framing_rects rc;
     if (framed_rects(w, h, r.out_width, r.out_height, f, &rc))
@@ -395,12 +424,58 @@ static int resolve_framed(uint32_t w, uint32_t h, uint32_t ow, uint32_t oh, cons
     return H263MI_OK;
 }
 
-int make_output_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_rgba_resize *r, RgbaLayout &out, const h263mi_framing *f)
+// The resize of `shape` under the filter `kind` (not AREA): the framing resolved (whole onto whole without one), the scratch
+// with the full-size pictures and the tap tables of the rectangles
+static int make_filtered(int device, uint32_t n, uint32_t w, uint32_t h, uint32_t ow, uint32_t oh, const h263mi_framing *f, uint32_t kind,
+                         RgbaLayout &shape)
+{
+    h263mi_framing_rects rc;
+    bool whole = true;
+    RC_TRY(framing_resolve(w, h, ow, oh, f, &rc, &whole));
+    // (kernels.h: only a stub runtime lacks the filter kernels)
+    if (!launch_rgba_filter || !launch_tensor_filter) return H263MI_ERR_HIP;
+    RgbaLayout::Resize &rz = shape.resize;
+    rz.framed.on = !whole;
+    rz.framed.rc = rc;
+    if (f) {
+        rz.framed.pad = (uint32_t)f->pad[0] | (uint32_t)f->pad[1] << 8 | (uint32_t)f->pad[2] << 16;
+        rz.framed.keep = f->keep_outside != 0;
+    }
+    const FilterTable table = filter_table(kind, rc.src_x, rc.src_y, rc.src_w, rc.src_h, rc.dst_w, rc.dst_h);
+    DeviceGuard g(device);
+    if (!g.ok) return H263MI_ERR_NO_DEVICE;
+    std::shared_ptr<ResizeScratch> sc(new (std::nothrow) ResizeScratch());
+    if (!sc) return H263MI_ERR_OUT_OF_MEMORY;
+    RC_TRY(sc->pixels.make(device, (size_t)n * w * h * 4));
+    RC_TRY(sc->spans.make(device, table.words.size() * sizeof(uint32_t), table.words.data()));
+    rz.scratch = std::move(sc);
+    rz.filter.on = true;
+    rz.filter.kind = kind;
+    rz.filter.ksx = table.ksx;
+    rz.filter.ksy = table.ksy;
+    rz.ow = ow;
+    rz.oh = oh;
+    return H263MI_OK;
+}
+
+int make_output_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_rgba_resize *r, RgbaLayout &out, const h263mi_framing *f,
+                      const h263mi_filter *flt)
 {
     if (!r) return make_rgba_layout_shape(n, w, h, nullptr, out);
     RgbaLayout shape;
     RC_TRY(rgba_resize_extent(n, r, &shape.bytes));
     const uint32_t ow = r->out_width, oh = r->out_height;
+    uint32_t kind = H263MI_FILTER_AREA;
+    RC_TRY(filter_kind(flt, &kind));
+    if (kind != H263MI_FILTER_AREA) {
+        const uint64_t row = 4ull * ow, pitch = r->row_pitch ? r->row_pitch : row;
+        RC_TRY(make_filtered(device, n, w, h, ow, oh, f, kind, shape));
+        shape.offsets.resize(n);
+        for (uint32_t i = 0; i < n; i++) shape.offsets[i] = r->offsets ? r->offsets[i] : (uint64_t)i * oh * pitch;
+        shape.resize.pitch = kernel_pitch(pitch, row, oh);
+        out = std::move(shape);
+        return H263MI_OK;
+    }
     SpanGeometry g[2];
     RC_TRY(resolve_framed(w, h, ow, oh, f, shape.resize.framed, g));
     h263mi_rgba_layout lay;
@@ -417,12 +492,22 @@ int make_output_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263
     return H263MI_OK;
 }
 
-int make_tensor_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_tensor_out *t, RgbaLayout &out, const h263mi_framing *f)
+int make_tensor_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_tensor_out *t, RgbaLayout &out, const h263mi_framing *f,
+                      const h263mi_filter *flt)
 {
     if (!t) return make_rgba_layout_shape(n, w, h, nullptr, out);
     RgbaLayout shape;
     uint64_t stride_n = 0;
     RC_TRY(tensor_extent(n, t, &shape.bytes, &shape.resize.tensor, &stride_n));
+    uint32_t kind = H263MI_FILTER_AREA;
+    RC_TRY(filter_kind(flt, &kind));
+    if (kind != H263MI_FILTER_AREA) {
+        RC_TRY(make_filtered(device, n, w, h, t->out_width, t->out_height, f, kind, shape));
+        shape.offsets.resize(n);
+        for (uint32_t i = 0; i < n; i++) shape.offsets[i] = (uint64_t)i * stride_n * shape.resize.tensor.elt;
+        out = std::move(shape);
+        return H263MI_OK;
+    }
     SpanGeometry g[2];
     RC_TRY(resolve_framed(w, h, t->out_width, t->out_height, f, shape.resize.framed, g));
     RC_TRY(make_scratch(device, (size_t)n * w * h * 4, {g[0], g[1]}, shape.resize.scratch));
@@ -505,6 +590,19 @@ int h263mi_tensor_extent(uint32_t n_streams, const h263mi_tensor_out *t, uint64_
 int h263mi_framing_resolve(uint16_t w, uint16_t h, uint16_t out_w, uint16_t out_h, const h263mi_framing *f, h263mi_framing_rects *out)
 {
     return h263mi::framing_resolve(w, h, out_w, out_h, f, out);
+}
+int h263mi_filter_taps(uint8_t kind, uint32_t in_size, uint32_t out_size, uint32_t *ksize, uint32_t *first, uint32_t *count,
+                       int32_t *coeffs, size_t coeff_capacity)
+{
+    if (!ksize || (kind != H263MI_FILTER_BILINEAR && kind != H263MI_FILTER_BICUBIC)) return H263MI_ERR_INVALID_ARGUMENT;
+    if (!in_size || !out_size || in_size > 65535 || out_size > 65535) return H263MI_ERR_INVALID_ARGUMENT;
+    const uint32_t ks = h263mi::filter_ksize(kind, in_size, out_size);
+    if (coeffs) {
+        if (!first || !count || coeff_capacity < (size_t)out_size * ks) return H263MI_ERR_INVALID_ARGUMENT;
+        h263mi::filter_taps(kind, in_size, out_size, ks, first, count, coeffs);
+    }
+    *ksize = ks;
+    return H263MI_OK;
 }
 
 }  // extern "C"

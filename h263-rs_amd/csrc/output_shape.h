@@ -35,6 +35,7 @@ struct DeviceBlock {
 // What a resize kernel reads (k_rgba_resize, k_plane_resize): the full-size pictures that the rendering kernels write for it --
 // RGBA, n * w*h*4 bytes, or planes, tightly packed I420 per stream, n * (w*h + 2*cw*ch) bytes -- and the spans of its geometry:
 // W' column spans then H' row spans, for planes followed by the cW' and cH' spans of the chroma planes.
+// Under a filter (h263mi_filter: k_rgba_filter, k_tensor_filter) `spans` holds the tap tables instead (filter_taps.h: filter_table).
 struct ResizeScratch {
     DeviceBlock pixels, spans;             // (two allocations: resize_scratch_bytes counts both)
 };
@@ -74,6 +75,13 @@ struct RgbaLayout {
             uint32_t pad = 0;                          // R | G << 8 | B << 16
             bool keep = false;
         } framed;
+        // ... or resampled with Pillow's bilinear or bicubic filter (h263mi_filter other than AREA: k_rgba_filter / k_tensor_filter
+        // in the place of all four kernels above).  framed.rc is then always filled in (an unframed shape: the whole picture onto
+        // the whole output), the scratch holds the tap tables of sw -> dw and sh -> dh, ksx / ksy entries per position
+        struct Filter {
+            bool on = false;
+            uint32_t kind = 0, ksx = 0, ksy = 0;
+        } filter;
         bool on() const { return scratch != nullptr; }
     } resize;
     // what a pointer into the caller's buffer must be a multiple of (a tensor: its element size)
@@ -139,12 +147,17 @@ int tensor_extent(uint32_t n_streams, const h263mi_tensor_out *t, uint64_t *byte
 int framing_resolve(uint32_t w, uint32_t h, uint32_t ow, uint32_t oh, const h263mi_framing *f, h263mi_framing_rects *out, bool *whole = nullptr);
 // device memory a tensor output of `slots` pictures of w x h holds: always a scratch, whatever W' x H' (f: a framing that
 // resolves for w x h -- its span tables are those of the destination rectangle)
-uint64_t tensor_scratch_bytes(uint32_t w, uint32_t h, uint32_t slots, const h263mi_tensor_out &t, const h263mi_framing *f = nullptr);
+// (flt: a filter that filter_kind accepts -- other than AREA the tap tables take the place of the span tables)
+uint64_t tensor_scratch_bytes(uint32_t w, uint32_t h, uint32_t slots, const h263mi_tensor_out &t, const h263mi_framing *f = nullptr,
+                              const h263mi_filter *flt = nullptr);
+// the validation of an h263mi_filter (NULL: AREA); *kind (may be null): H263MI_FILTER_*
+int filter_kind(const h263mi_filter *flt, uint32_t *kind = nullptr);
 // the layout that a resize of a w x h picture is by definition (full size, or 1/2 or 1/4 of sizes that 2 or 4 divide), into
 // *lay (offsets and pitch copied); false: none, the resize needs k_rgba_resize
 bool resize_as_layout(uint32_t w, uint32_t h, const h263mi_rgba_resize &r, h263mi_rgba_layout *lay);
 // device memory a resize of `slots` pictures of w x h holds (0: it is a layout)
-uint64_t resize_scratch_bytes(uint32_t w, uint32_t h, uint32_t slots, const h263mi_rgba_resize &r, const h263mi_framing *f = nullptr);
+uint64_t resize_scratch_bytes(uint32_t w, uint32_t h, uint32_t slots, const h263mi_rgba_resize &r, const h263mi_framing *f = nullptr,
+                              const h263mi_filter *flt = nullptr);
 
 // ---- the shapes, with the device memory they need, for n streams of w x h on `device`
 // h263mi_batch_set_rgba_layout's (NULL: the default); no device memory
@@ -152,13 +165,16 @@ int make_rgba_layout_shape(uint32_t n, uint32_t w, uint32_t h, const h263mi_rgba
 // the RGBA shape `r` (NULL: the default): the layout it is by definition, or the resize with a new scratch
 // f (h263mi_framing, NULL: none): a framing that resolves to the whole source and the whole destination is the unframed shape;
 // every other one is the resize with a scratch, followed by k_rgba_resize_framed
+// flt (h263mi_filter, NULL or AREA: none): always the resize with a scratch -- the full-size pictures and the tap tables --,
+// followed by k_rgba_filter, whatever the sizes and the framing are
 int make_output_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_rgba_resize *r, RgbaLayout &out,
-                      const h263mi_framing *f = nullptr);
+                      const h263mi_framing *f = nullptr, const h263mi_filter *flt = nullptr);
 // the tensor shape `t` (NULL: the default): always the resize with a new scratch -- W' = w, H' = h too, where the area average is
 // the identity -- followed by k_tensor_resize
 // (f as make_output_shape: k_tensor_resize_framed)
+// (flt as make_output_shape: k_tensor_filter)
 int make_tensor_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_tensor_out *t, RgbaLayout &out,
-                      const h263mi_framing *f = nullptr);
+                      const h263mi_framing *f = nullptr, const h263mi_filter *flt = nullptr);
 // the layout (NULL: none, format 0), its offsets uploaded
 int make_yuv_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_yuv_layout *layout, YuvLayout &out);
 // the YUV shape `r` (NULL: none): the full-size layout it is by definition when W' = w and H' = h, else the resize with a new

@@ -344,8 +344,15 @@ int h263mi_render_rgba_resize(const h263mi_state *cs, uint8_t strength, const h2
 int h263mi_render_rgba_resize_framed(const h263mi_state *cs, uint8_t strength, const h263mi_rgba_resize *r, const h263mi_framing *f,
                                      uint8_t *rgba)
 {
+    return h263mi_render_rgba_resize_filtered(cs, strength, r, f, nullptr, rgba);
+}
+
+int h263mi_render_rgba_resize_filtered(const h263mi_state *cs, uint8_t strength, const h263mi_rgba_resize *r, const h263mi_framing *f,
+                                       const h263mi_filter *flt, uint8_t *rgba)
+{
     h263mi_state *s = const_cast<h263mi_state *>(cs);
     if (!s || !rgba || !r || r->offsets) return H263MI_ERR_INVALID_ARGUMENT;
+    RC_TRY(filter_kind(flt));
     if (!s->has_last || !s->b) return H263MI_ERR_NO_PICTURE;
     h263mi_batch *b = s->b;
     RC_TRY(rgba_resize_extent(1, r, nullptr));
@@ -358,7 +365,7 @@ int h263mi_render_rgba_resize_framed(const h263mi_state *cs, uint8_t strength, c
     h263mi_rgba_resize tight = *r;
     tight.row_pitch = 0;
     h263mi_batch::RgbaLayout shape;            // (its scratch, if any, goes at the end, once the copy out has waited for it)
-    RC_TRY(make_output_shape(s->cfg.device_id, 1, b->L.width, b->L.height, &tight, shape, f));
+    RC_TRY(make_output_shape(s->cfg.device_id, 1, b->L.width, b->L.height, &tight, shape, f, flt));
     return render_rgba_shaped(s, st, shape, r->out_width, r->out_height, r->row_pitch, rgba);
 }
 
@@ -369,8 +376,15 @@ int h263mi_render_tensor(const h263mi_state *cs, uint8_t strength, const h263mi_
 
 int h263mi_render_tensor_framed(const h263mi_state *cs, uint8_t strength, const h263mi_tensor_out *t, const h263mi_framing *f, void *out)
 {
+    return h263mi_render_tensor_filtered(cs, strength, t, f, nullptr, out);
+}
+
+int h263mi_render_tensor_filtered(const h263mi_state *cs, uint8_t strength, const h263mi_tensor_out *t, const h263mi_framing *f,
+                                  const h263mi_filter *flt, void *out)
+{
     h263mi_state *s = const_cast<h263mi_state *>(cs);
     if (!s || !out || !t) return H263MI_ERR_INVALID_ARGUMENT;
+    RC_TRY(filter_kind(flt));
     if (!s->has_last || !s->b) return H263MI_ERR_NO_PICTURE;
     h263mi_batch *b = s->b;
     // the caller's shape: where its planes lie in `out`
@@ -388,7 +402,7 @@ int h263mi_render_tensor_framed(const h263mi_state *cs, uint8_t strength, const 
     const size_t row = (size_t)t->out_width * host.elt, plane = row * t->out_height;
     RC_TRY(s->rgba.reserve(s->cfg.device_id, 3 * plane));
     h263mi_batch::RgbaLayout shape;            // (its scratch goes at the end, once the copies out have waited for it)
-    RC_TRY(make_tensor_shape(s->cfg.device_id, 1, b->L.width, b->L.height, &tight, shape, f));
+    RC_TRY(make_tensor_shape(s->cfg.device_id, 1, b->L.width, b->L.height, &tight, shape, f, flt));
     const uint8_t *d = s->rgba.as<uint8_t>();
     RC_TRY(b->render(st, s->rgba.as<uint8_t>(), nullptr, false, nullptr, &shape));
     const hipStream_t on = b->stream;

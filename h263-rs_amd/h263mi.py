@@ -102,7 +102,12 @@ EXPORTS = [
     "h263mi_framing_resolve", "h263mi_batch_set_rgba_resize_framed", "h263mi_batch_set_tensor_output_framed",
     "h263mi_render_rgba_resize_framed", "h263mi_render_tensor_framed", "h263mi_mixed_set_rgba_resize_framed",
     "h263mi_mixed_set_tensor_output_framed", "h263mi_mixed_stream_framing",
+    # ABI 7, additive: bilinear and bicubic resampling (Pillow-exact) of the resized RGBA and of the tensor
+    "h263mi_filter_taps", "h263mi_batch_set_rgba_resize_filtered", "h263mi_batch_set_tensor_output_filtered",
+    "h263mi_render_rgba_resize_filtered", "h263mi_render_tensor_filtered", "h263mi_mixed_set_rgba_resize_filtered",
+    "h263mi_mixed_set_tensor_output_filtered",
 ]
+FILTER_AREA, FILTER_BILINEAR, FILTER_BICUBIC = 0, 1, 2
 FRAME_STRETCH, FRAME_LETTERBOX, FRAME_COVER, FRAME_WINDOW = 0, 1, 2, 3
 TENSOR_F32, TENSOR_F16, TENSOR_BF16 = 0, 1, 2
 TENSOR_NUMPY_DTYPE = {TENSOR_F32: np.float32, TENSOR_F16: np.float16, TENSOR_BF16: np.uint16}     # (bfloat16: bit patterns)
@@ -258,6 +263,30 @@ def make_framing(mode=FRAME_STRETCH, pad=(0, 0, 0), keep_outside=False, src=None
 
 def _opt(struct):
     return C.byref(struct) if struct is not None else None
+
+
+class Filter(C.Structure):
+    """h263mi_filter: the resampling filter of a resized output (FILTER_AREA, FILTER_BILINEAR, FILTER_BICUBIC)"""
+    _fields_ = [("kind", C.c_uint8), ("reserved", C.c_uint8 * 7)]
+
+
+def make_filter(kind=FILTER_AREA):
+    """-> Filter"""
+    f = Filter()
+    f.kind = kind
+    return f
+
+
+def filter_taps(kind, in_size, out_size):
+    """h263mi_filter_taps -> (ksize, first[out_size], count[out_size], coeffs[out_size, ksize]): the source positions
+    [first, first + count) that each output position reads and their weights in units of 2^-22 (no device); H263Error when the
+    kind or a size is refused"""
+    ks = C.c_uint32()
+    _check(lib().h263mi_filter_taps(kind, in_size, out_size, C.byref(ks), None, None, None, 0), "filter_taps")
+    first, count = np.zeros(out_size, np.uint32), np.zeros(out_size, np.uint32)
+    coeffs = np.zeros((out_size, ks.value), np.int32)
+    _check(lib().h263mi_filter_taps(kind, in_size, out_size, C.byref(ks), _p(first), _p(count), _p(coeffs), coeffs.size), "filter_taps")
+    return ks.value, first, count, coeffs
 
 
 def framing_resolve(width, height, out_width, out_height, framing=None):
@@ -582,6 +611,13 @@ def lib():
         L.h263mi_mixed_set_rgba_resize_framed.argtypes = [vp, vp, vp]
         L.h263mi_mixed_set_tensor_output_framed.argtypes = [vp, vp, vp]
         L.h263mi_mixed_stream_framing.argtypes = [vp, u32, vp]
+        L.h263mi_filter_taps.argtypes = [u8, u32, u32, vp, vp, vp, vp, C.c_size_t]
+        L.h263mi_batch_set_rgba_resize_filtered.argtypes = [vp, vp, vp, vp]
+        L.h263mi_batch_set_tensor_output_filtered.argtypes = [vp, vp, vp, vp]
+        L.h263mi_render_rgba_resize_filtered.argtypes = [vp, u8, vp, vp, vp, vp]
+        L.h263mi_render_tensor_filtered.argtypes = [vp, u8, vp, vp, vp, vp]
+        L.h263mi_mixed_set_rgba_resize_filtered.argtypes = [vp, vp, vp, vp]
+        L.h263mi_mixed_set_tensor_output_filtered.argtypes = [vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -797,6 +833,24 @@ class H263State:
     def render_tensor_framed_into(self, strength, tensor, framing, out):
         """h263mi_render_tensor_framed into `out` (an array whose first byte is the tensor's base)"""
         _check(lib().h263mi_render_tensor_framed(self._h, strength, C.byref(tensor), _opt(framing), _p(out)), "render_tensor_framed")
+        return out
+
+    def render_rgba_resize_filtered_into(self, strength, out, framing, filter, out_width, out_height, row_pitch=0):
+        """h263mi_render_rgba_resize_filtered into `out` (framing, filter: None = none / the area average)"""
+        r, _ = make_rgba_resize(out_width, out_height, row_pitch)
+        _check(lib().h263mi_render_rgba_resize_filtered(self._h, strength, C.byref(r), _opt(framing), _opt(filter), _p(out)),
+               "render_rgba_resize_filtered")
+        return out
+
+    def render_rgba_resize_filtered(self, strength, framing, filter, out_width, out_height, row_pitch=0):
+        """h263mi_render_rgba_resize_filtered: H' * pitch bytes (what no store reaches is zero here)"""
+        out = np.zeros(rgba_resize_extent(1, out_width, out_height, row_pitch), np.uint8)
+        return self.render_rgba_resize_filtered_into(strength, out, framing, filter, out_width, out_height, row_pitch)
+
+    def render_tensor_filtered_into(self, strength, tensor, framing, filter, out):
+        """h263mi_render_tensor_filtered into `out` (an array whose first byte is the tensor's base)"""
+        _check(lib().h263mi_render_tensor_filtered(self._h, strength, C.byref(tensor), _opt(framing), _opt(filter), _p(out)),
+               "render_tensor_filtered")
         return out
 
     def render_tensor(self, strength, tensor):
@@ -1134,6 +1188,18 @@ class Batch:
         """h263mi_batch_set_tensor_output_framed (tensor None: back to the default output; framing None: the plain tensor)"""
         _check(lib().h263mi_batch_set_tensor_output_framed(self._h, _opt(tensor), _opt(framing)), "batch_set_tensor_output_framed")
 
+    def set_rgba_resize_filtered(self, framing, filter, out_width, out_height, row_pitch=0, offsets=None):
+        """h263mi_batch_set_rgba_resize_filtered (framing None: none; filter: a Filter, None = the area average)"""
+        r, keep = make_rgba_resize(out_width, out_height, row_pitch, offsets)
+        _check(lib().h263mi_batch_set_rgba_resize_filtered(self._h, C.byref(r), _opt(framing), _opt(filter)),
+               "batch_set_rgba_resize_filtered")
+        del keep
+
+    def set_tensor_output_filtered(self, tensor, framing, filter):
+        """h263mi_batch_set_tensor_output_filtered (tensor None: back to the default output)"""
+        _check(lib().h263mi_batch_set_tensor_output_filtered(self._h, _opt(tensor), _opt(framing), _opt(filter)),
+               "batch_set_tensor_output_filtered")
+
     def set_tensor_output(self, tensor=None):
         """h263mi_batch_set_tensor_output: d_rgba of the later calls is the base of the tensor `tensor` (a TensorOut; None: back
         to today's output)"""
@@ -1269,6 +1335,17 @@ class MixedBatch:
     def set_tensor_output_framed(self, tensor, framing):
         """h263mi_mixed_set_tensor_output_framed (tensor None: full-size RGBA again)"""
         _check(lib().h263mi_mixed_set_tensor_output_framed(self._h, _opt(tensor), _opt(framing)), "mixed_set_tensor_output_framed")
+
+    def set_rgba_resize_filtered(self, framing, filter, out_width, out_height, row_pitch=0):
+        """h263mi_mixed_set_rgba_resize_filtered: every size class with its own rectangle and its own tap tables"""
+        r, _ = make_rgba_resize(out_width, out_height, row_pitch)
+        _check(lib().h263mi_mixed_set_rgba_resize_filtered(self._h, C.byref(r), _opt(framing), _opt(filter)),
+               "mixed_set_rgba_resize_filtered")
+
+    def set_tensor_output_filtered(self, tensor, framing, filter):
+        """h263mi_mixed_set_tensor_output_filtered (tensor None: full-size RGBA again)"""
+        _check(lib().h263mi_mixed_set_tensor_output_filtered(self._h, _opt(tensor), _opt(framing), _opt(filter)),
+               "mixed_set_tensor_output_filtered")
 
     def stream_framing(self, stream):
         """h263mi_mixed_stream_framing -> FramingRects of the stream's picture size under the shape in force"""

@@ -188,6 +188,25 @@ public:
         check(h263mi_render_tensor_framed(s_, strength, &t, f, out.data()));
         return out;
     }
+    // ... and resampled with Pillow's bilinear or bicubic filter (h263mi_filter; nullptr or AREA: the framed call)
+    std::vector<uint8_t> render_rgba_resize_filtered(uint8_t strength, const h263mi_rgba_resize &r, const h263mi_framing *f,
+                                                     const h263mi_filter *filter) const
+    {
+        uint64_t bytes = 0;
+        check(h263mi_rgba_resize_extent(1, &r, &bytes));
+        std::vector<uint8_t> rgba((size_t)bytes);
+        check(h263mi_render_rgba_resize_filtered(s_, strength, &r, f, filter, rgba.data()));
+        return rgba;
+    }
+    std::vector<uint8_t> render_tensor_filtered(uint8_t strength, const h263mi_tensor_out &t, const h263mi_framing *f,
+                                                const h263mi_filter *filter) const
+    {
+        uint64_t bytes = 0;
+        check(h263mi_tensor_extent(1, &t, &bytes));
+        std::vector<uint8_t> out((size_t)bytes);
+        check(h263mi_render_tensor_filtered(s_, strength, &t, f, filter, out.data()));
+        return out;
+    }
     // the deblocked planes of the last picture as I420 or NV12 (h263mi_yuv_layout; nullptr: tightly packed I420), without
     // going through RGBA: the layout's extent in bytes, the ones outside the planes zero
     std::vector<uint8_t> render_yuv(uint8_t strength, const h263mi_yuv_layout *layout = nullptr) const
@@ -395,6 +414,15 @@ public:
     // the same under a framing resolved per picture size (LETTERBOX, COVER; WINDOW is refused); nullptr framing: the plain call
     void set_rgba_resize_framed(const h263mi_rgba_resize *r, const h263mi_framing *f) { check(h263mi_mixed_set_rgba_resize_framed(m_, r, f)); }
     void set_tensor_output_framed(const h263mi_tensor_out *t, const h263mi_framing *f) { check(h263mi_mixed_set_tensor_output_framed(m_, t, f)); }
+    // ... and with a filter (h263mi_filter: every size class gets its own tap tables; nullptr or AREA: the framed call)
+    void set_rgba_resize_filtered(const h263mi_rgba_resize *r, const h263mi_framing *f, const h263mi_filter *filter)
+    {
+        check(h263mi_mixed_set_rgba_resize_filtered(m_, r, f, filter));
+    }
+    void set_tensor_output_filtered(const h263mi_tensor_out *t, const h263mi_framing *f, const h263mi_filter *filter)
+    {
+        check(h263mi_mixed_set_tensor_output_filtered(m_, t, f, filter));
+    }
     // the rectangles of the stream's picture size under the shape in force: maps a position of its output back to its source
     h263mi_framing_rects stream_framing(uint32_t stream) const
     {

@@ -521,6 +521,61 @@ int h263mi_render_rgba_resize_framed(const h263mi_state *s, uint8_t strength, co
 int h263mi_render_tensor_framed(const h263mi_state *s, uint8_t strength, const h263mi_tensor_out *t, const h263mi_framing *f, void *out);
 
 /*
+ * BILINEAR AND BICUBIC RESAMPLING OF A RESIZED OUTPUT (additive, ABI 7): the filter of h263mi_rgba_resize, h263mi_tensor_out and
+ * their framed forms, chosen per shape.  AREA is the area average documented above, the right filter for shrinking 1080p; BILINEAR
+ * and BICUBIC are, bit for bit, PIL.Image.resize of Pillow on a mode-RGB image (the resampling behind torchvision.transforms.Resize
+ * on a PIL image): what a network whose training data went through it has seen.  Every comparison stays an equality.
+ * The taps of one axis, in_size -> out_size.  All arithmetic is IEEE binary64, no fused multiply-add, in the order written:
+ *     scale = in_size / out_size;  fs = max(scale, 1.0);  support = S * fs  (S = 1.0 bilinear, 2.0 bicubic);
+ *     ksize = 2 * ceil(support) + 1;
+ *   for output position X:
+ *     center = (X + 0.5) * scale;
+ *     xmin = max(0, trunc(center - support + 0.5));  xmax = min(in_size, trunc(center + support + 0.5));  count = xmax - xmin;
+ *     k[i] = f((i + xmin - center + 0.5) * (1.0 / fs))  for i < count;
+ *     ww = the sum of the k[i] in order of i;  each k[i] is divided by ww when ww != 0;
+ *     the integer weight is trunc(k * 4194304 + 0.5) for k >= 0 and trunc(k * 4194304 - 0.5) otherwise  (units of 2^-22);
+ *   bilinear: f(x) = 1 - |x| for |x| < 1, else 0;
+ *   bicubic (Keys, a = -0.5), x = |x|: ((a + 2) * x - (a + 3)) * x * x + 1 below 1;  (((x - 5) * x + 8) * x - 4) * a below 2;  else 0.
+ * One pass along an axis computes, per channel,
+ *     out = clamp((2^21 + sum_i coeff[i] * P[first + i]) >> 22, 0, 255)            (the shift is arithmetic)
+ * and a w x h picture becomes W' x H' in two: the horizontal pass makes W' x h 8-bit values (the first rounding), the vertical
+ * pass over those makes the result (the second rounding).  A pass whose two sizes agree is skipped: that axis is copied.  Alpha
+ * is 255.  For every row of every table 255 * sum |coeff| + 2^21 < 2^31: 32-bit signed integers hold every sum.
+ * Under a framing the rectangles (sx, sy, sw, sh) and (dx, dy, dw, dh) are those of h263mi_framing_resolve (none: the whole picture
+ * and the whole output): inside the destination rectangle the output is the two-pass resample of the sw x sh picture
+ * F[sy : sy+sh, sx : sx+sw] to dw x dh -- the taps are those of sw -> dw and sh -> dh and end at the WINDOW's own edges: it is
+ * im.crop(box).resize(size), not im.resize(size, box=box) --, placed at (dx, dy); outside it `pad` or keep_outside as the framing
+ * documents.  For a tensor u is the resampled channel value or the pad colour, and the element is fl32(fl32(u * scale[c]) + bias[c])
+ * converted as h263mi_tensor_out documents; placement, extents, alignment, strides and bgr are those of the unfiltered shape.
+ * Not offered: h263mi_yuv_resize stays area-only; Lanczos and Hamming, whose weights go through sin and cos and so depend on the
+ * C library; a mode without antialiasing.
+ */
+#define H263MI_FILTER_AREA     0   /* the area average of h263mi_rgba_resize */
+#define H263MI_FILTER_BILINEAR 1
+#define H263MI_FILTER_BICUBIC  2   /* Keys, a = -0.5 */
+typedef struct h263mi_filter { uint8_t kind; uint8_t reserved[7]; } h263mi_filter;   /* reserved: zero */
+
+/* Pure host function, no HIP call: the taps of one axis, in_size -> out_size.  *ksize: entries per output position;
+ * first[X], count[X] (count <= ksize): the source positions [first, first + count) that output position X reads;
+ * coeffs[X * ksize + k]: their weights in units of 2^-22, zero beyond count.  coeffs NULL: only *ksize is returned.
+ * H263MI_ERR_INVALID_ARGUMENT: ksize NULL; a kind other than BILINEAR or BICUBIC (AREA has no taps); a size outside 1..65535;
+ * with coeffs given: first or count NULL, or coeff_capacity below out_size * ksize. */
+int h263mi_filter_taps(uint8_t kind, uint32_t in_size, uint32_t out_size, uint32_t *ksize,
+                       uint32_t *first, uint32_t *count, int32_t *coeffs, size_t coeff_capacity);
+/* The setters and renderings of the framed forms with a filter.  filter NULL or H263MI_FILTER_AREA: the _framed call -- the same
+ * launches, the same bytes.  An unknown kind or a reserved byte set is H263MI_ERR_INVALID_ARGUMENT; a refused setter leaves the
+ * shape in force untouched.  Any other filter: the full-size pictures are rendered into the device scratch of the resize, which
+ * also holds the tap tables (made once when the shape is set, shared with a pending rendering), and k_rgba_filter /
+ * k_tensor_filter resample from there; the filter replaces, and is replaced by, every other shape of d_rgba; a deferred
+ * rendering of H263MI_CFG_PIPELINE_POST keeps the filter of its request (copied). */
+int h263mi_batch_set_rgba_resize_filtered(h263mi_batch *b, const h263mi_rgba_resize *r, const h263mi_framing *f, const h263mi_filter *filter);
+int h263mi_batch_set_tensor_output_filtered(h263mi_batch *b, const h263mi_tensor_out *t, const h263mi_framing *f, const h263mi_filter *filter);
+int h263mi_render_rgba_resize_filtered(const h263mi_state *s, uint8_t strength, const h263mi_rgba_resize *r, const h263mi_framing *f,
+                                       const h263mi_filter *filter, uint8_t *rgba);
+int h263mi_render_tensor_filtered(const h263mi_state *s, uint8_t strength, const h263mi_tensor_out *t, const h263mi_framing *f,
+                                  const h263mi_filter *filter, void *out);
+
+/*
  * DEBLOCKED YUV 4:2:0 OUTPUT LAYOUT (additive, ABI 7): where the filtered planes go inside d_deblocked.  The planes are always
  * full size (w x h luma, cw x ch chroma, cw = ceil(w/2), ch = ceil(h/2)) under a layout -- h263mi_yuv_resize below resizes them --;
  * the RGBA layouts and resizes above apply to d_rgba only and the two shapes are independent.  I420: three planes Y, Cb, Cr.  NV12: a Y plane and one plane of ch rows of cw
@@ -822,6 +877,12 @@ int h263mi_mixed_set_tensor_output(h263mi_mixed *m, const h263mi_tensor_out *t);
  * full-size pictures, counted as above. */
 int h263mi_mixed_set_rgba_resize_framed(h263mi_mixed *m, const h263mi_rgba_resize *r, const h263mi_framing *f);
 int h263mi_mixed_set_tensor_output_framed(h263mi_mixed *m, const h263mi_tensor_out *t, const h263mi_framing *f);
+/* ... and with a filter (h263mi_filter; NULL or AREA: the _framed call): LETTERBOX and COVER are resolved per size class when the
+ * class is made, together with its tap tables -- every size gets its own rectangle and its own taps --; WINDOW stays
+ * H263MI_ERR_INVALID_ARGUMENT.  Under BILINEAR or BICUBIC every class keeps the scratch of its full-size pictures and its tap
+ * tables (4 bytes per weight, 8 per output column and row), counted as above. */
+int h263mi_mixed_set_rgba_resize_filtered(h263mi_mixed *m, const h263mi_rgba_resize *r, const h263mi_framing *f, const h263mi_filter *filter);
+int h263mi_mixed_set_tensor_output_filtered(h263mi_mixed *m, const h263mi_tensor_out *t, const h263mi_framing *f, const h263mi_filter *filter);
 /* The rectangles of stream `stream`'s picture size under the shape in force (h263mi_framing_resolve of its w x h; without a
  * resize or tensor: the whole picture onto itself).  H263MI_ERR_NO_PICTURE: the stream has no picture yet. */
 int h263mi_mixed_stream_framing(const h263mi_mixed *m, uint32_t stream, h263mi_framing_rects *out);
