@@ -74,6 +74,25 @@ int h263mi_batch::launch_plane_resize(const YuvLayout::Resize &rz, const std::ve
     bool any = false;
     for (int8_t v : sets) any = any || v >= 0;
     if (!any) return H263MI_OK;
+    if (rz.filter.on) {                        // Pillow's bilinear / bicubic in the place of the area average (k_plane_filter)
+        PlaneFilterArgs a{};
+        a.src = rz.scratch->pixels.as<uint8_t>();
+        a.dst = d_dst;
+        a.w = L.width, a.h = L.height, a.cw = L.cwidth, a.ch = L.cheight;
+        a.ow = rz.ow, a.oh = rz.oh, a.cow = (rz.ow + 1) / 2, a.coh = (rz.oh + 1) / 2;
+        plane_filter_axes(rz.scratch->spans.p, a, rz.filter.ksx_y, rz.filter.ksy_y, rz.filter.ksx_c, rz.filter.ksy_c);
+        a.pitch_y = rz.pitch_y;
+        a.pitch_c = rz.pitch_c;
+        a.nv12 = rz.format == YUV_OUT_NV12 ? 1u : 0u;
+        a.wide = wide ? 1u : 0u;
+        a.d_y = L.width * L.height;
+        a.d_c = L.cwidth * L.cheight;
+        a.n_pictures = n;
+        if (!launch_plane_filter) return H263MI_ERR_HIP;            // (kernels.h: only a stub runtime lacks it)
+        RC_TRY(time_begin(5, on));
+        HIP_TRY(launch_plane_filter(a, on));
+        return H263MI_OK;
+    }
     PlaneResizeArgs a{};
     a.src = rz.scratch->pixels.as<uint8_t>();
     a.dst = d_dst;
@@ -1003,6 +1022,16 @@ int h263mi_batch_set_yuv_resize(h263mi_batch *b, const h263mi_yuv_resize *r)
     return H263MI_OK;
 }
 
+int h263mi_batch_set_yuv_resize_filtered(h263mi_batch *b, const h263mi_yuv_resize *r, const h263mi_filter *filter)
+{
+    if (!b) return H263MI_ERR_INVALID_ARGUMENT;
+    h263mi_batch::YuvLayout shape;
+    RC_TRY(make_yuv_resize_shape(b->device, b->n, b->L.width, b->L.height, r, shape, filter));
+    DeviceGuard g(b->device);                  // (the shape it replaces frees its memory, unless a pending rendering holds it)
+    b->yuv = std::move(shape);
+    return H263MI_OK;
+}
+
 int h263mi_batch_set_rgba_resize(h263mi_batch *b, const h263mi_rgba_resize *r)
 {
     if (!b) return H263MI_ERR_INVALID_ARGUMENT;
@@ -1198,7 +1227,7 @@ int h263mi_batch_timing_end(h263mi_batch *b, h263mi_kernel_times *out)
         } else if (r.kernel == 1 || r.kernel == 3) {       // (3: k_rgba_resize, the second half of a resized rendering)
             out->post_ms += ms;
             out->post_launches += r.launches;
-        } else if (r.kernel == 4) {                        // (k_plane_resize: post-processing time of the renderings counted above)
+        } else if (r.kernel == 4 || r.kernel == 5) {       // (k_plane_resize, k_plane_filter: post-processing time of the renderings counted above)
             out->post_ms += ms;
         } else {
             out->frame_ms += ms;

@@ -195,7 +195,8 @@ struct h263mi_batch {
     hipStream_t stream_of(int kernel_id) const { return (kernel_id == 1 && overlap_post) ? post_stream : stream; }
     int time_close();
     // (kernel id 3: k_rgba_resize, queued on `on` behind the rendering it resizes; its time counts as post-processing.
-    // id 4: k_plane_resize, likewise -- its time is post-processing time, and post_launches goes on counting renderings)
+    // id 4: k_plane_resize, likewise -- its time is post-processing time, and post_launches goes on counting renderings;
+    // id 5: k_plane_filter, in the place of id 4 under a filtered YUV resize)
     int time_begin(int kernel_id, hipStream_t on = nullptr);
 
     // ---- the work
@@ -224,7 +225,8 @@ struct h263mi_batch {
     // d_planes + its offsets, null where sets[s] < 0 -- uploaded on `on`; *wide: word stores are possible
     int plane_resize_dst(const YuvLayout::Resize &rz, const std::vector<int8_t> &sets, uint8_t *d_planes, hipStream_t on,
                          const h263mi::PlaneDst **d_out, bool *wide);
-    // k_plane_resize of `rz` into `d_dst` (plane_resize_dst), on `on`; nothing when no stream has a set
+    // k_plane_resize of `rz` -- or, under a filter (rz.filter), k_plane_filter -- into `d_dst` (plane_resize_dst), on `on`; nothing
+    // when no stream has a set
     int launch_plane_resize(const YuvLayout::Resize &rz, const std::vector<int8_t> &sets, const h263mi::PlaneDst *d_dst, bool wide,
                             hipStream_t on);
     // pipeline mode: the post-processing of the pictures just submitted is deferred to the next launch.

@@ -6,6 +6,7 @@
 #include "dev_common.h"
 #include "digest_kernel.inl"
 #include "filter_kernel.inl"
+#include "plane_filter_kernel.inl"
 #include "plane_resize_kernel.inl"
 #include "resize_kernel.inl"
 #include "tensor_resize_kernel.inl"
@@ -68,6 +69,10 @@ hipError_t launch_tensor_filter(const TensorFilterArgs &args, hipStream_t stream
 // chroma planes of every picture in ONE launch.  Weak like launch_rgba_resize; h263mi_batch::launch_plane_resize refuses to run
 // without it.
 hipError_t launch_plane_resize(const PlaneResizeArgs &args, hipStream_t stream) __attribute__((weak));
+// k_plane_filter over args.n_pictures pictures (plane_filter_kernel.inl; bands, chunk and segs_y are set here): k_plane_resize's
+// launch shape, Pillow's bilinear / bicubic taps in the place of the area average.  Weak like launch_rgba_resize; the host
+// refuses a filtered YUV shape without it.
+hipError_t launch_plane_filter(const PlaneFilterArgs &args, hipStream_t stream) __attribute__((weak));
 // k_digest over args.n_items work items, then k_digest_final over fin.n_digests digests (digest_kernel.inl): the launch pair of one
 // digest call, whatever it covers.  Weak like launch_rgba_resize; the digest entry points refuse to run without it.
 hipError_t launch_digest(const DigestArgs &args, const DigestFinalArgs &fin, hipStream_t stream) __attribute__((weak));

@@ -6,6 +6,7 @@
 #include "post_kernel.inl"
 #include "recon_kernel.inl"
 #include "filter_kernel.inl"
+#include "plane_filter_kernel.inl"
 #include "plane_resize_kernel.inl"
 #include "resize_kernel.inl"
 #include "tensor_resize_kernel.inl"
@@ -943,6 +944,40 @@ hipError_t launch_plane_resize(const PlaneResizeArgs &args, hipStream_t stream)
     a.segs_y = (a.ow + PLANE_OUT - 1) / PLANE_OUT;
     const dim3 grid(a.chunk * 8, a.n_pictures, a.segs_y + (a.cow + PLANE_OUT - 1) / PLANE_OUT);
     hipLaunchKernelGGL(k_plane_resize, grid, dim3(64), 0, stream, a);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
+// k_plane_filter: Pillow's bilinear / bicubic resampling of the full-size deblocked planes into I420 or NV12, both passes in one
+// kernel (plane_filter_kernel.inl).  The launch shape is k_plane_resize's: one wave per workgroup, no barrier; blockIdx.y =
+// picture, blockIdx.z = segment of PLANE_OUT output columns (luma, then chroma), blockIdx.x = band of PFILTER_ROWS output rows in
+// XCD order.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_plane_filter(PlaneFilterArgs a)
+{
+    __shared__ __attribute__((aligned(16))) PlaneFilterLds lds;
+    const uint32_t band = (blockIdx.x & 7u) * a.chunk + (blockIdx.x >> 3);
+    if (band >= a.bands) return;
+    const int lane = threadIdx.x & 63;
+    PlaneFilterLane t;
+    plane_filter_item(a, lds, band, blockIdx.z, blockIdx.y, [&](auto f) { f(lane, t); });
+}
+
+hipError_t launch_plane_filter(const PlaneFilterArgs &args, hipStream_t stream)
+{
+    if (!args.n_pictures) return hipSuccess;
+    const FilterAxis *const ax[4] = {&args.xy, &args.yy, &args.xc, &args.yc};
+    for (const FilterAxis *x : ax)
+        if (!x->span || !x->coeff || !x->ksize) return hipErrorInvalidValue;
+    if (!args.src || !args.dst || !args.w || !args.h || !args.ow || !args.oh || args.cw != (args.w + 1) / 2 || args.ch != (args.h + 1) / 2 ||
+        args.cow != (args.ow + 1) / 2 || args.coh != (args.oh + 1) / 2 || args.n_pictures > 65535)
+        return hipErrorInvalidValue;
+    PlaneFilterArgs a = args;
+    a.bands = (a.oh + PFILTER_ROWS - 1) / PFILTER_ROWS;
+    a.chunk = (a.bands + 7) / 8;
+    a.segs_y = (a.ow + PLANE_OUT - 1) / PLANE_OUT;
+    const dim3 grid(a.chunk * 8, a.n_pictures, a.segs_y + (a.cow + PLANE_OUT - 1) / PLANE_OUT);
+    hipLaunchKernelGGL(k_plane_filter, grid, dim3(64), 0, stream, a);
     return hipGetLastError();
 }
 

@@ -538,8 +538,10 @@ int make_yuv_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_
     return H263MI_OK;
 }
 
-int make_yuv_resize_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_yuv_resize *r, YuvLayout &out)
+int make_yuv_resize_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_yuv_resize *r, YuvLayout &out, const h263mi_filter *flt)
 {
+    uint32_t kind = H263MI_FILTER_AREA;
+    RC_TRY(filter_kind(flt, &kind));
     if (!r) {
         out = YuvLayout();
         return H263MI_OK;
@@ -552,7 +554,27 @@ int make_yuv_resize_shape(int device, uint32_t n, uint32_t w, uint32_t h, const 
         return make_yuv_shape(device, n, w, h, &lay, out);
     }
     const uint32_t cw = (w + 1) / 2, ch = (h + 1) / 2, cow = (ow + 1) / 2, coh = (oh + 1) / 2;
-    RC_TRY(make_scratch(device, (size_t)n * ((size_t)w * h + 2 * (size_t)cw * ch), {{w, ow}, {h, oh}, {cw, cow}, {ch, coh}}, shape.resize.scratch));
+    const size_t pixel_bytes = (size_t)n * ((size_t)w * h + 2 * (size_t)cw * ch);
+    if (kind != H263MI_FILTER_AREA) {
+        // the tap tables of luma and chroma back to back, made once (plane_filter_kernel.inl: plane_filter_axes)
+        if (!launch_plane_filter) return H263MI_ERR_HIP;       // (kernels.h: only a stub runtime lacks it)
+        const FilterTable ty = filter_table(kind, 0, 0, w, h, ow, oh), tc = filter_table(kind, 0, 0, cw, ch, cow, coh);
+        std::vector<uint32_t> words(ty.words);
+        words.insert(words.end(), tc.words.begin(), tc.words.end());
+        DeviceGuard g(device);
+        if (!g.ok) return H263MI_ERR_NO_DEVICE;
+        std::shared_ptr<ResizeScratch> sc(new (std::nothrow) ResizeScratch());
+        if (!sc) return H263MI_ERR_OUT_OF_MEMORY;
+        RC_TRY(sc->pixels.make(device, pixel_bytes));
+        RC_TRY(sc->spans.make(device, words.size() * sizeof(uint32_t), words.data()));
+        shape.resize.scratch = std::move(sc);
+        shape.resize.filter.on = true;
+        shape.resize.filter.kind = kind;
+        shape.resize.filter.ksx_y = ty.ksx, shape.resize.filter.ksy_y = ty.ksy;
+        shape.resize.filter.ksx_c = tc.ksx, shape.resize.filter.ksy_c = tc.ksy;
+    } else {
+        RC_TRY(make_scratch(device, pixel_bytes, {{w, ow}, {h, oh}, {cw, cow}, {ch, coh}}, shape.resize.scratch));
+    }
     shape.bytes = placed.bytes;
     shape.resize.format = placed.format;
     shape.resize.ow = ow;

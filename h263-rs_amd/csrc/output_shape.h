@@ -35,7 +35,8 @@ struct DeviceBlock {
 // What a resize kernel reads (k_rgba_resize, k_plane_resize): the full-size pictures that the rendering kernels write for it --
 // RGBA, n * w*h*4 bytes, or planes, tightly packed I420 per stream, n * (w*h + 2*cw*ch) bytes -- and the spans of its geometry:
 // W' column spans then H' row spans, for planes followed by the cW' and cH' spans of the chroma planes.
-// Under a filter (h263mi_filter: k_rgba_filter, k_tensor_filter) `spans` holds the tap tables instead (filter_taps.h: filter_table).
+// Under a filter (h263mi_filter: k_rgba_filter, k_tensor_filter, k_plane_filter) `spans` holds the tap tables instead
+// (filter_taps.h: filter_table; for planes the luma table, then the chroma table).
 struct ResizeScratch {
     DeviceBlock pixels, spans;             // (two allocations: resize_scratch_bytes counts both)
 };
@@ -118,6 +119,13 @@ struct YuvLayout {
         uint32_t ow = 0, oh = 0, pitch_y = 0, pitch_c = 0;
         bool wide = false;                 // pitches and offsets are all multiples of 4
         std::vector<uint64_t> offsets;     // 3 per stream: Y, Cb or CbCr, Cr
+        // ... resampled with Pillow's bilinear or bicubic filter (h263mi_batch_set_yuv_resize_filtered, a kind other than AREA:
+        // k_plane_filter in the place of k_plane_resize).  The scratch's `spans` then holds the luma and the chroma tap table
+        // back to back (filter_taps.h: filter_table), ks* entries per position of each axis
+        struct Filter {
+            bool on = false;
+            uint32_t kind = 0, ksx_y = 0, ksy_y = 0, ksx_c = 0, ksy_c = 0;
+        } filter;
         bool on() const { return scratch != nullptr; }
     } resize;
     bool shaped() const { return on() || resize.on(); }      // (then `bytes` is what d_deblocked must hold)
@@ -179,6 +187,9 @@ int make_tensor_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263
 int make_yuv_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_yuv_layout *layout, YuvLayout &out);
 // the YUV shape `r` (NULL: none): the full-size layout it is by definition when W' = w and H' = h, else the resize with a new
 // scratch
-int make_yuv_resize_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_yuv_resize *r, YuvLayout &out);
+// flt (h263mi_filter, NULL or AREA: none): the resize with a scratch whose `spans` holds the four tap tables, followed by
+// k_plane_filter; W' = w and H' = h stays the full-size layout under any filter
+int make_yuv_resize_shape(int device, uint32_t n, uint32_t w, uint32_t h, const h263mi_yuv_resize *r, YuvLayout &out,
+                          const h263mi_filter *flt = nullptr);
 
 }  // namespace h263mi

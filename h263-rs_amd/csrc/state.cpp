@@ -453,8 +453,15 @@ int h263mi_render_yuv(const h263mi_state *cs, uint8_t strength, const h263mi_yuv
 
 int h263mi_render_yuv_resize(const h263mi_state *cs, uint8_t strength, const h263mi_yuv_resize *r, uint8_t *out)
 {
+    return h263mi_render_yuv_resize_filtered(cs, strength, r, nullptr, out);
+}
+
+int h263mi_render_yuv_resize_filtered(const h263mi_state *cs, uint8_t strength, const h263mi_yuv_resize *r, const h263mi_filter *flt,
+                                      uint8_t *out)
+{
     h263mi_state *s = const_cast<h263mi_state *>(cs);
     if (!s || !out || !r) return H263MI_ERR_INVALID_ARGUMENT;
+    RC_TRY(filter_kind(flt));
     if (!s->has_last || !s->b) return H263MI_ERR_NO_PICTURE;
     h263mi_batch *b = s->b;
     // the caller's shape: where its planes lie in `out`
@@ -478,7 +485,7 @@ int h263mi_render_yuv_resize(const h263mi_state *cs, uint8_t strength, const h26
     dev.pitch_c = dpc;
     dev.offsets_y = dev.offsets_cb = dev.offsets_cr = nullptr;
     h263mi_batch::YuvLayout shape;              // (its scratch goes at the end, once the copies out have waited for it)
-    RC_TRY(make_yuv_resize_shape(s->cfg.device_id, 1, b->L.width, b->L.height, &dev, shape));
+    RC_TRY(make_yuv_resize_shape(s->cfg.device_id, 1, b->L.width, b->L.height, &dev, shape, flt));
     return render_planes_shaped(s, st, shape, out, host, off, ow, oh, row_c, coh, dpy, dpc);
 }
 

@@ -105,7 +105,7 @@ EXPORTS = [
     # ABI 7, additive: bilinear and bicubic resampling (Pillow-exact) of the resized RGBA and of the tensor
     "h263mi_filter_taps", "h263mi_batch_set_rgba_resize_filtered", "h263mi_batch_set_tensor_output_filtered",
     "h263mi_render_rgba_resize_filtered", "h263mi_render_tensor_filtered", "h263mi_mixed_set_rgba_resize_filtered",
-    "h263mi_mixed_set_tensor_output_filtered",
+    "h263mi_mixed_set_tensor_output_filtered", "h263mi_batch_set_yuv_resize_filtered", "h263mi_render_yuv_resize_filtered",
 ]
 FILTER_AREA, FILTER_BILINEAR, FILTER_BICUBIC = 0, 1, 2
 FRAME_STRETCH, FRAME_LETTERBOX, FRAME_COVER, FRAME_WINDOW = 0, 1, 2, 3
@@ -618,6 +618,8 @@ def lib():
         L.h263mi_render_tensor_filtered.argtypes = [vp, u8, vp, vp, vp, vp]
         L.h263mi_mixed_set_rgba_resize_filtered.argtypes = [vp, vp, vp, vp]
         L.h263mi_mixed_set_tensor_output_filtered.argtypes = [vp, vp, vp, vp]
+        L.h263mi_batch_set_yuv_resize_filtered.argtypes = [vp, vp, vp]
+        L.h263mi_render_yuv_resize_filtered.argtypes = [vp, u8, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -892,6 +894,22 @@ class H263State:
         """h263mi_render_yuv_resize with default placement: the extent's bytes (what lies between rows is zero here)"""
         out = np.zeros(yuv_resize_extent(1, out_width, out_height, format, pitch_y, pitch_c), np.uint8)
         return self.render_yuv_resize_into(strength, out, out_width, out_height, format, pitch_y, pitch_c)
+
+    def render_yuv_resize_filtered(self, strength, filter, out_width, out_height, format=YUV_I420, pitch_y=0, pitch_c=0):
+        """h263mi_render_yuv_resize_filtered with default placement: the extent's bytes (what lies between rows is zero here)"""
+        out = np.zeros(yuv_resize_extent(1, out_width, out_height, format, pitch_y, pitch_c), np.uint8)
+        return self.render_yuv_resize_filtered_into(strength, out, filter, out_width, out_height, format, pitch_y, pitch_c)
+
+    def render_yuv_resize_filtered_into(self, strength, out, filter, out_width, out_height, format=YUV_I420, pitch_y=0, pitch_c=0,
+                                        offsets_y=None, offsets_cb=None, offsets_cr=None, resize=None):
+        """h263mi_render_yuv_resize_filtered into `out` (filter: a Filter, None = the area average); bytes outside the planes stay"""
+        keep = None
+        if resize is None:
+            resize, keep = make_yuv_resize(out_width, out_height, format, pitch_y, pitch_c, offsets_y, offsets_cb, offsets_cr)
+        _check(lib().h263mi_render_yuv_resize_filtered(self._h, strength, C.byref(resize), _opt(filter), _p(out)),
+               "render_yuv_resize_filtered")
+        del keep
+        return out
 
     def render_yuv_resize_into(self, strength, out, out_width, out_height, format=YUV_I420, pitch_y=0, pitch_c=0, offsets_y=None,
                                offsets_cb=None, offsets_cr=None, resize=None):
@@ -1168,6 +1186,11 @@ class Batch:
             resize, keep = make_yuv_resize(out_width, out_height, format, pitch_y, pitch_c, offsets_y, offsets_cb, offsets_cr)
         _check(lib().h263mi_batch_set_yuv_resize(self._h, C.byref(resize)), "batch_set_yuv_resize")
         del keep
+
+    def set_yuv_resize_filtered(self, resize, filter):
+        """h263mi_batch_set_yuv_resize_filtered (resize: a YuvResize of make_yuv_resize, whose keep-alive the caller holds; None:
+        back to tightly packed full-size I420.  filter: a Filter, None = the area average)"""
+        _check(lib().h263mi_batch_set_yuv_resize_filtered(self._h, _opt(resize), _opt(filter)), "batch_set_yuv_resize_filtered")
 
     def set_rgba_resize(self, out_width=0, out_height=0, row_pitch=0, offsets=None, default=False):
         """h263mi_batch_set_rgba_resize (default=True: back to today's output)"""

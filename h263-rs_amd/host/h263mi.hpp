@@ -229,6 +229,16 @@ public:
         return out;
     }
 
+    // ... resampled with Pillow's bilinear or bicubic filter (h263mi_filter; nullptr or AREA: the call above)
+    std::vector<uint8_t> render_yuv_filtered(uint8_t strength, const h263mi_yuv_resize &r, const h263mi_filter *filter) const
+    {
+        uint64_t bytes = 0;
+        check(h263mi_yuv_resize_extent(1, &r, &bytes));
+        std::vector<uint8_t> out((size_t)bytes);
+        check(h263mi_render_yuv_resize_filtered(s_, strength, &r, filter, out.data()));
+        return out;
+    }
+
     // the same straight into page-locked memory of the caller (h263mi_host_alloc / h263mi_host_register): the buffer a
     // renderer reuses for every picture instead of the fresh Vec<u8> of bt601.rs:128; `rgba` holds width * height * 4 bytes
     void render_rgba_into_pinned(uint8_t strength, uint8_t *rgba) const { check(h263mi_render_rgba_pinned(s_, strength, rgba)); }

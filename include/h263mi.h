@@ -547,8 +547,9 @@ int h263mi_render_tensor_framed(const h263mi_state *s, uint8_t strength, const h
  * im.crop(box).resize(size), not im.resize(size, box=box) --, placed at (dx, dy); outside it `pad` or keep_outside as the framing
  * documents.  For a tensor u is the resampled channel value or the pad colour, and the element is fl32(fl32(u * scale[c]) + bias[c])
  * converted as h263mi_tensor_out documents; placement, extents, alignment, strides and bgr are those of the unfiltered shape.
- * Not offered: h263mi_yuv_resize stays area-only; Lanczos and Hamming, whose weights go through sin and cos and so depend on the
- * C library; a mode without antialiasing.
+ * The planes of h263mi_yuv_resize take the same two filters, each plane as one 8-bit channel (h263mi_batch_set_yuv_resize_filtered
+ * below).  Not offered: Lanczos and Hamming, whose weights go through sin and cos and so depend on the C library; a mode without
+ * antialiasing.
  */
 #define H263MI_FILTER_AREA     0   /* the area average of h263mi_rgba_resize */
 #define H263MI_FILTER_BILINEAR 1
@@ -656,6 +657,35 @@ int h263mi_batch_set_yuv_resize(h263mi_batch *b, const h263mi_yuv_resize *r);
  * stream (the offset arrays may be given, one entry each, as in h263mi_render_yuv).  Bytes outside the planes' rectangles are
  * untouched. */
 int h263mi_render_yuv_resize(const h263mi_state *s, uint8_t strength, const h263mi_yuv_resize *r, uint8_t *out);
+
+/*
+ * BILINEAR AND BICUBIC RESAMPLING OF THE RESIZED YUV OUTPUT (additive, ABI 7): h263mi_yuv_resize with the filter of h263mi_filter.
+ * Both structs are unchanged; h263mi_yuv_resize_extent and the placement -- format, pitches, offset arrays, default placement, the
+ * extent a checked batch holds d_deblocked to, word or byte stores -- are those of the unfiltered resize.
+ * Each plane is resampled on its own: luma w x h -> W' x H', Cb and Cr cw x ch -> cW' x cH' (c* = ceil(* / 2) as above).  The taps of
+ * an axis are h263mi_filter_taps(kind, in, out) for that plane's own sizes -- four tables: luma x, luma y, chroma x, chroma y --, and
+ * the arithmetic is the two-pass formula that h263mi_filter documents, applied to one 8-bit channel: the horizontal pass makes
+ * 8-bit values (the first rounding, clamped), the vertical pass over those makes the result (the second rounding, clamped); a pass
+ * whose two sizes agree is skipped, per plane and per axis.  Each plane is, bit for bit,
+ *     Image.fromarray(plane, "L").resize((pw', ph'), BILINEAR | BICUBIC)
+ * of Pillow; NV12 is the same Cb and Cr, interleaved.  The source planes are the picture's planes after deblock(strength), as for
+ * the area form.  Each chroma grid is treated as covering the picture area, as in the area form -- Pillow's
+ * center = (X + 0.5) * scale does exactly that --: no phase shift between luma and chroma is introduced.
+ * filter NULL or H263MI_FILTER_AREA: the unfiltered call -- the same launches, the same bytes.  An unknown kind or a reserved byte
+ * set is H263MI_ERR_INVALID_ARGUMENT; a refused setter leaves the YUV shape in force untouched.  W' = w and H' = h under any filter
+ * is the full-size layout byte for byte (the same kernels as h263mi_yuv_resize takes there: no scratch).  Any other filtered
+ * resize keeps the device scratch of the unfiltered one, with the four tap tables (made once when the shape is set) in the place of
+ * its span tables; k_plane_filter behind the rendering reads it.
+ * A batch still has ONE YUV shape in force: the filtered resize replaces a layout or a resize and is replaced by either; it is
+ * independent of the shape of d_rgba -- one call may write filtered planes and RGBA in any of its shapes.  A deferred rendering of
+ * H263MI_CFG_PIPELINE_POST keeps the filter of its request (copied; scratch and tables are shared with it).  Streams with nothing
+ * to render are not written, nor is any byte outside the planes' rectangles.
+ * Not offered: a framing of YUV output; YUV output from mixed-size sets (they have none); Lanczos and Hamming.
+ */
+int h263mi_batch_set_yuv_resize_filtered(h263mi_batch *b, const h263mi_yuv_resize *r, const h263mi_filter *filter);
+/* One state, into HOST memory, as h263mi_render_yuv_resize. */
+int h263mi_render_yuv_resize_filtered(const h263mi_state *s, uint8_t strength, const h263mi_yuv_resize *r,
+                                      const h263mi_filter *filter, uint8_t *out);
 
 /* deblock (strength 0 = off) + BT.601 of every stream's last picture into d_rgba
  * (DEVICE, n_streams * w*h*4 bytes, stream-major); d_deblocked (DEVICE, may be NULL)
