@@ -318,3 +318,12 @@ def vfull_residual(coeffs):
     out = vidct_1d(inter)                                                      # [n, x_offset, y_offset]
     res = vclip(out)
     return np.swapaxes(res, 1, 2).copy(), np.swapaxes(out, 1, 2).copy()
+
+
+def vline_residual(vals):
+    """vals: int array [n, 8] -- the first coefficient row of Horiz blocks or the first coefficient column of Vert blocks
+    (idct.rs:134-169: ONE idct_1d, then `* BASIS_TABLE[0][0]`) -> residual int array [n, 8] along the transformed
+    direction (every pixel of a Horiz block's column x / a Vert block's row y takes element x / y) and the binary32 bits of
+    the idct_1d output (for near-tie searches)"""
+    out = vidct_1d(vf32_from_int(np.asarray(vals, I64).reshape(-1, 8)))
+    return vclip(out, BASIS_BITS[0][0]), out

@@ -100,6 +100,21 @@ uint32_t sim_wave_stats(uint32_t *out, uint32_t cap_waves)
     return n;
 }
 static_assert(sizeof(WaveStat) == 64, "sixteen words");
+// ... and the arguments every round's two passes were given (tests/test_sim_idct_forms.py holds them against the declaration of
+// tests/idct_form_cases.py): eighteen words per wave, the waves in the order of sim_wave_stats.  A dense round reports what
+// its instantiations assume (8, 8, no class fix-up).
+struct RoundStat {
+    uint32_t n_cols[6], n_rows[6];         // the extent of the truncated sums: cols_from_mask / rows_from_mask over the round
+    uint32_t any_special[6];               // the column pass applied the class fix-up (some block is Horiz, Vert, Dc or Zero)
+};
+static std::vector<RoundStat> round_stats;
+uint32_t sim_round_stats(uint32_t *out, uint32_t cap_waves)
+{
+    const uint32_t n = (uint32_t)round_stats.size();
+    for (uint32_t i = 0; i < n && i < cap_waves; i++) memcpy(out + 18 * i, &round_stats[i], sizeof(RoundStat));
+    return n;
+}
+static_assert(sizeof(RoundStat) == 72, "eighteen words");
 
 void sim_layout(uint32_t w, uint32_t h, FrameLayout *out) { *out = make_layout(w, h); }
 
@@ -147,6 +162,7 @@ int sim_recon_ex(uint32_t w, uint32_t h, uint32_t n_pictures, const MbRecord *mb
     const uint32_t tpp = a.tiles_x * a.tiles_y, total = tpp * n_pictures, chunk = (total + 7) / 8;
     static WaveFetch f[64];
     wave_stats.clear();
+    round_stats.clear();
     for (uint32_t wg = 0; wg < chunk * 8; wg++) {
         const uint32_t xcd = wg & 7, t = wg >> 3, g = xcd * chunk + t;
         if (t >= chunk || g >= total) continue;
@@ -161,6 +177,7 @@ int sim_recon_ex(uint32_t w, uint32_t h, uint32_t n_pictures, const MbRecord *mb
             memset(s, 0xA5, sizeof *s);   // LDS is not zero-initialised on the device either
             const uint32_t group_word = recon_group_word(a, p);
             WaveStat ws{};
+            RoundStat rs{};
             ws.pic = (uint32_t)p.pic; ws.mby = (uint32_t)p.mby; ws.group = (uint32_t)(p.mbx0 >> 3);
             ws.valid = recon_valid_mask(a, p);
             ws.group_word = group_word;
@@ -168,6 +185,7 @@ int sim_recon_ex(uint32_t w, uint32_t h, uint32_t n_pictures, const MbRecord *mb
                 for (int l = 0; l < 64; l++) recon_phase_copy(a, l, p);
                 ws.is_static = 2;
                 wave_stats.push_back(ws);
+                round_stats.push_back(rs);
                 continue;
             }
             for (int l = 0; l < 64; l++) recon_phase_load(a, *s, l, p, group_word);
@@ -194,6 +212,7 @@ int sim_recon_ex(uint32_t w, uint32_t h, uint32_t n_pictures, const MbRecord *mb
                 for (int l = 0; l < 64; l++) recon_phase_copy(a, l, p);
                 ws.is_static = 1;
                 wave_stats.push_back(ws);
+                round_stats.push_back(rs);
                 continue;
             }
             const bool mc = a.has_ref && km.inter;          // the dispatch of kernels.hip: recon_tail<MC>
@@ -236,7 +255,12 @@ int sim_recon_ex(uint32_t w, uint32_t h, uint32_t n_pictures, const MbRecord *mb
                         else recon_phase_idct_rows(*s, ri[l], l, cols_from_mask(wm), cols_any);
                     }
                     for (int l = 0; l < 64; l++) any_special = any_special || recon_block_is_special(ri[l], l, rows_any, cols_any);
-                    if (ws.n_rounds < 6) ws.form[ws.n_rounds] = dense ? ROUND_DENSE : (wide ? ROUND_WIDE : ROUND_GENERAL);
+                    if (ws.n_rounds < 6) {
+                        ws.form[ws.n_rounds] = dense ? ROUND_DENSE : (wide ? ROUND_WIDE : ROUND_GENERAL);
+                        rs.n_cols[ws.n_rounds] = dense ? 8u : (uint32_t)cols_from_mask(wm);
+                        rs.n_rows[ws.n_rounds] = dense ? 8u : (uint32_t)rows_from_mask(rm);
+                        rs.any_special[ws.n_rounds] = !dense && any_special;
+                    }
                     ws.n_rounds++;
                 }
                 if (round == 0) {
@@ -260,6 +284,7 @@ int sim_recon_ex(uint32_t w, uint32_t h, uint32_t n_pictures, const MbRecord *mb
                     }
             }
             wave_stats.push_back(ws);
+            round_stats.push_back(rs);
             for (int l = 0; l < 64; l++) recon_phase_store(a, *s, l, p, km);
         }
     }

@@ -25,7 +25,7 @@ _libs = {}
 def lib(asan=False, variant=None):
     """variant: "blend" / "intborder" = the checker built with that motion-compensation mutation, "dbhalf" / "dbfloor" /
     "dbwrap" = with that mutation of the post-filter, "killkeep" / "staticmv" / "intradc" = with that mutation of the
-    reconstruction waves' bookkeeping (csrc/mutants.h)"""
+    reconstruction waves' bookkeeping, "pairwise" = with the IDCT's sums as balanced trees (csrc/mutants.h)"""
     name = "libh263mi_sim_%s.so" % variant if variant else ("libh263mi_sim_asan.so" if asan else "libh263mi_sim.so")
     if name not in _libs:
         subprocess.check_call(["make", "-C", SIM_DIR, "-s", name])
@@ -40,6 +40,8 @@ def lib(asan=False, variant=None):
                                         C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         L.sim_wave_stats.argtypes = [C.c_void_p, C.c_uint32]
         L.sim_wave_stats.restype = C.c_uint32
+        L.sim_round_stats.argtypes = [C.c_void_p, C.c_uint32]
+        L.sim_round_stats.restype = C.c_uint32
         _libs[name] = L
     return _libs[name]
 
@@ -56,6 +58,19 @@ def wave_stats(asan=False, variant=None):
     n = L.sim_wave_stats(None, 0)
     out = np.zeros(n, WAVE_STAT_DTYPE)
     assert L.sim_wave_stats(_p(out), n) == n
+    return out
+
+
+ROUND_STAT_DTYPE = np.dtype([(n, "<u4", (6,)) for n in ("n_cols", "n_rows", "any_special")])
+
+
+def round_stats(asan=False, variant=None):
+    """the arguments the two passes of every round were given in the checker's last sim_recon[_ex] call (sim.cpp: RoundStat),
+    one entry per wave in the order of wave_stats()"""
+    L = lib(asan, variant)
+    n = L.sim_round_stats(None, 0)
+    out = np.zeros(n, ROUND_STAT_DTYPE)
+    assert L.sim_round_stats(_p(out), n) == n
     return out
 
 

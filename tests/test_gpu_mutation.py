@@ -21,7 +21,10 @@ Three more are of the BOOKKEEPING of the reconstruction waves (csrc/mutants.h; p
   libh263mi_killkeep.so   the mark phase ignores the kill bits
   libh263mi_staticmv.so   eight uncoded inter macroblocks are copied from the reference whatever their vectors are
   libh263mi_intradc.so    uncoded blocks of intra macroblocks are not activated
-Each has an exact model -- the oracle over edited records -- and must equal it on every byte, through k_recon and k_frame."""
+Each has an exact model -- the oracle over edited records -- and must equal it on every byte, through k_recon and k_frame.
+
+The first two, fma and pairwise, are asked again PER FORM of a reconstruction round (tests/idct_form_cases.py; probe:
+tests/idct_form_probe.py): the first general round, the later ones, dense rounds and wide rounds, through k_recon and k_frame."""
 import json
 import os
 import subprocess
@@ -296,3 +299,84 @@ def test_wave_probe_through_the_product_build_is_clean(tmp_path, wave_probe_orac
         for path in ("state", "frame"):
             diff = wc.first_difference(pic, tuple(clean["%s_%s_%d" % (path, name, i)] for i in range(3)), want)
             assert diff is None, "the product build (%s), picture %s: %s" % (path, name, diff)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the arithmetic mutants again, in every form a reconstruction round is compiled in
+# ---------------------------------------------------------------------------------------------------------------
+def _form_probe(lib_path, tmp_path, name):
+    out = str(tmp_path / (name + ".npz"))
+    env = dict(os.environ, H263MI_LIB=lib_path)
+    subprocess.run([sys.executable, os.path.join(HERE, "idct_form_probe.py"), out], env=env, check=True, timeout=300)
+    return np.load(out)
+
+
+@pytest.fixture(scope="module")
+def form_probe_oracle():
+    import idct_form_probe as probe
+    return probe.expectations()
+
+
+def _form_detections(got, oracle, mutant):
+    """{k_recon / k_frame path: {form name: [listed, differing from the oracle, equal to the model's prediction]}}"""
+    import idct_form_probe as probe
+    import test_sim_idct_forms as cpu
+    return {path: cpu.detections([(pic, want, tuple(got["%s_%s_%d" % (path, name, i)] for i in range(3))) for name, pic, want in oracle], mutant)
+            for path in probe.PATHS}
+
+
+def test_form_probe_through_the_product_build_is_clean(tmp_path, form_probe_oracle):
+    """the designed tables of tests/idct_form_cases.py through the child-process path with the product library: every byte is
+    the oracle's, through k_recon and k_frame, and every fixture block is its soft-float residual"""
+    import idct_form_probe as probe
+    import test_sim_idct_forms as cpu
+    import wave_cases as wc
+    clean = _form_probe(os.path.join(PKG, "libh263mi.so"), tmp_path, "product")
+    for name, pic, want in form_probe_oracle:
+        for path in probe.PATHS:
+            planes = tuple(clean["%s_%s_%d" % (path, name, i)] for i in range(3))
+            diff = wc.first_difference(pic, planes, want)
+            assert diff is None, "the product build (%s), picture %s: %s" % (path, name, diff)
+            cpu.check_fixture_blocks(pic, planes, "the product build (%s)" % path)
+
+
+def test_pairwise_mutant_is_caught_in_every_form(tmp_path, form_probe_oracle):
+    """the pairwise mutation is in the source of idct_1d_pairs, hence in every instantiation: in the first general round, the
+    later general rounds, dense rounds and wide rounds, through k_recon and through k_frame, some block the model lists differs
+    from the oracle, and at least half of the listed blocks are exactly what the model predicts (the criterion of
+    test_mutant_build_is_caught; the CPU checker built with the mutation meets the model on all of them)"""
+    import idct_form_cases as fc
+    lib = os.path.join(PKG, "mutants", "libh263mi_pairwise.so")
+    if not os.path.exists(lib):                                  # normally built by __graft_entry__.build()
+        subprocess.check_call(["make", "-C", PKG, "-s", "mutants"])
+    counts = _form_detections(_form_probe(lib, tmp_path, "pairwise"), form_probe_oracle, "pairwise")
+    for path, forms in counts.items():
+        for form in fc.FORM_NAMES:
+            listed, differ, agree = forms[form]
+            print("pairwise mutant, %s, %s: %d listed placements, %d differ from the oracle, %d equal the model's prediction"
+                  % (path, form, listed, differ, agree))
+    for path, forms in counts.items():
+        for form in fc.FORM_NAMES:
+            listed, differ, agree = forms[form]
+            assert listed >= 8 and differ >= 1, "the pairwise mutant went unnoticed in %s rounds (%s)" % (form, path)
+            assert 2 * agree >= listed, (path, form, listed, agree)
+
+
+def test_fma_mutant_is_caught_in_the_new_forms(tmp_path, form_probe_oracle):
+    """-ffp-contract=fast: WHERE the compiler fuses is its choice, so the counts per form are reported (DESIGN.md section 0, row
+    a3) and the assertion is over the union of the forms the designed tables add (later general rounds, dense rounds, wide
+    rounds; the first general round has test_mutant_build_is_caught); a form with zero detections says that the
+    compiler did not contract there"""
+    import idct_form_cases as fc
+    lib = os.path.join(PKG, "mutants", "libh263mi_fma.so")
+    if not os.path.exists(lib):                                  # normally built by __graft_entry__.build()
+        subprocess.check_call(["make", "-C", PKG, "-s", "mutants"])
+    counts = _form_detections(_form_probe(lib, tmp_path, "fma"), form_probe_oracle, "fma")
+    total = 0
+    for path, forms in counts.items():
+        for form in fc.FORM_NAMES:
+            listed, differ, agree = forms[form]
+            print("fma mutant, %s, %s: %d listed placements, %d differ from the oracle, %d equal the model's prediction"
+                  % (path, form, listed, differ, agree))
+            total += differ if form != "general-first" else 0
+    assert total >= 1, "the fma mutant went unnoticed in the later general rounds, the dense rounds and the wide rounds alike"

@@ -181,6 +181,36 @@ def test_scalar_and_vectorised_softfloat_agree_on_whole_blocks():
         assert sf.block_residual([int(v) for v in co[b]], force_full=True) == res[b].tolist()
 
 
+def _random_lines(seed, n):
+    rng = np.random.default_rng(seed)
+    vals = np.zeros((n, 8), np.int64)
+    for b in range(n):
+        k = int(rng.integers(1, 9))
+        pos = rng.choice(8, k, replace=False)
+        vals[b, pos] = rng.integers(-2048, 2048, k) if b % 10 == 0 else rng.integers(-600, 601, k)
+        if not vals[b, 1:].any():
+            vals[b, 1 + int(rng.integers(0, 7))] = 1 + int(rng.integers(0, 600))
+    return vals
+
+
+def test_10000_random_vert_and_10000_random_horiz_blocks():
+    """the vectorised one-transform form (softfloat_idct.vline_residual: idct.rs:134-169) against the C oracle's Vert and Horiz
+    classes, and against the scalar specification on a few"""
+    for kind, seed in (("vert", 31), ("horiz", 32)):
+        vals = _random_lines(seed, 10000)
+        res, _ = sf.vline_residual(vals)
+        v = np.zeros((len(vals), 64), np.float32)
+        v[:, :8] = vals
+        got_c = c_residual(np.full(len(vals), TAG[kind]), v)
+        want = np.repeat(res[:, :, None], 8, axis=2) if kind == "vert" else np.repeat(res[:, None, :], 8, axis=1)
+        assert (clip255(want) == got_c).all()
+        for b in range(0, len(vals), 500):
+            co = [0] * 64
+            for j, x in enumerate(vals[b]):
+                co[8 * j if kind == "vert" else j] = int(x)
+            assert sf.classify(co)[0] == kind and sf.block_residual(co) == want[b].tolist()
+
+
 def test_mutation_fixture_is_consistent():
     """tests/golden/idct_sensitive_blocks.json (tools/find_sensitive_blocks.py): the C oracle gives `residual`, the
     mutated soft-float arithmetic gives the listed differing pixels -- so an implementation that fuses or
