@@ -1186,6 +1186,78 @@ int h263mi_batch_adler32_spans(h263mi_batch *b, const uint8_t *d_base, uint64_t 
     return digest_rc(digest_spans(b->digest_words, b->placement, d_base, buffer_bytes, spans, n_spans, seed, digests, n_digests, b->stream));
 }
 
+// h263mi_roi_tensor_on's arguments, decided on the host in the order include/h263mi.h lists; *out: the launch they come to.
+// The table itself is never read here: a wave validates its own record (roi_kernel.inl).
+static int roi_tensor_args(const uint8_t *d_rgba, uint64_t rgba_bytes, uint32_t n_pictures, uint32_t width, uint32_t height,
+                           const h263mi_roi *d_rois, uint32_t n_rois, const h263mi_tensor_out *t, void *d_out, uint64_t out_bytes,
+                           uint32_t *d_status, RoiArgs *out)
+{
+    static_assert(sizeof(h263mi_roi) == 16 && sizeof(RoiRecord) == 16, "a wave reads its record as four words");
+    h263mi_batch::RgbaLayout::Resize::Tensor tn;
+    uint64_t extent = 0, stride_n = 0;
+    RC_TRY(tensor_extent(n_rois ? n_rois : 1, t, &extent, &tn, &stride_n));
+    if (!n_pictures || !width || !height || width > 65535 || height > 65535) return H263MI_ERR_INVALID_ARGUMENT;
+    if ((uint64_t)width * height >= (1ull << 30)) return H263MI_ERR_INVALID_ARGUMENT;
+    if (n_rois > 65535) return H263MI_ERR_INVALID_ARGUMENT;
+    if (n_rois && (!d_rgba || !d_rois || !d_out)) return H263MI_ERR_INVALID_ARGUMENT;
+    if ((uintptr_t)d_rgba % 16 || (uintptr_t)d_out % tn.elt) return H263MI_ERR_INVALID_ARGUMENT;
+    if (rgba_bytes / ((uint64_t)width * height * 4) < n_pictures) return H263MI_ERR_INVALID_ARGUMENT;     // (the product may not fit)
+    if (n_rois && out_bytes < extent) return H263MI_ERR_INVALID_ARGUMENT;
+    RoiArgs a{};
+    a.t.r.src = d_rgba;
+    a.t.r.w = width, a.t.r.h = height;
+    a.t.r.ow = t->out_width, a.t.r.oh = t->out_height;
+    a.t.r.n_pictures = n_pictures;
+    for (int c = 0; c < 3; c++) a.t.scale[c] = tn.scale[c], a.t.bias[c] = tn.bias[c];
+    a.t.dtype = tn.dtype;
+    a.t.bgr = tn.bgr;
+    a.t.stride_c = tn.stride_c, a.t.stride_h = tn.stride_h;
+    a.rois = reinterpret_cast<const RoiRecord *>(d_rois);
+    a.dst = static_cast<uint8_t *>(d_out);
+    a.stride_n = stride_n;
+    a.status = d_status;
+    a.n_rois = n_rois;
+    a.inv_ow = 1.0f / (float)a.t.r.ow, a.inv_oh = 1.0f / (float)a.t.r.oh;
+    *out = a;
+    return H263MI_OK;
+}
+
+static int roi_tensor_launch(const RoiArgs &a, hipStream_t stream)
+{
+    if (!launch_roi_tensor) return H263MI_ERR_HIP;         // (kernels.h: only a stub runtime lacks it)
+    auto queue = [&]() -> int {
+        HIP_TRY(launch_roi_tensor(a, stream));
+        return H263MI_OK;
+    };
+    return digest_rc(queue());                             // (the call allocates nothing: whatever the runtime refuses is H263MI_ERR_HIP)
+}
+
+int h263mi_roi_tensor_on(const h263mi_backend_cfg *cfg, const uint8_t *d_rgba, uint64_t rgba_bytes, uint32_t n_pictures, uint16_t width,
+                         uint16_t height, const h263mi_roi *d_rois, uint32_t n_rois, const h263mi_tensor_out *t, void *d_out,
+                         uint64_t out_bytes, uint32_t *d_status)
+{
+    RoiArgs a;
+    RC_TRY(roi_tensor_args(d_rgba, rgba_bytes, n_pictures, width, height, d_rois, n_rois, t, d_out, out_bytes, d_status, &a));
+    if (!n_rois) return H263MI_OK;
+    const int dev = cfg ? cfg->device_id : 0;
+    RC_TRY(check_device(dev));
+    DeviceGuard g(dev);
+    if (!g.ok) return H263MI_ERR_NO_DEVICE;
+    return roi_tensor_launch(a, cfg ? (hipStream_t)cfg->stream : nullptr);
+}
+
+int h263mi_batch_roi_tensor(h263mi_batch *b, const uint8_t *d_rgba, uint64_t rgba_bytes, const h263mi_roi *d_rois, uint32_t n_rois,
+                            const h263mi_tensor_out *t, void *d_out, uint64_t out_bytes, uint32_t *d_status)
+{
+    if (!b) return H263MI_ERR_INVALID_ARGUMENT;
+    RoiArgs a;
+    RC_TRY(roi_tensor_args(d_rgba, rgba_bytes, b->n, b->L.width, b->L.height, d_rois, n_rois, t, d_out, out_bytes, d_status, &a));
+    DeviceGuard g(b->device);
+    RC_TRY(b->sync());                           // (the deferred rendering of a pipelined batch, the second stream of an overlapped one)
+    if (!n_rois) return H263MI_OK;
+    return roi_tensor_launch(a, b->stream);
+}
+
 int h263mi_batch_timing_begin(h263mi_batch *b)
 {
     if (!b) return H263MI_ERR_INVALID_ARGUMENT;

@@ -9,6 +9,7 @@
 #include "plane_filter_kernel.inl"
 #include "plane_resize_kernel.inl"
 #include "resize_kernel.inl"
+#include "roi_kernel.inl"
 #include "tensor_resize_kernel.inl"
 
 namespace h263mi {
@@ -60,6 +61,9 @@ hipError_t launch_tensor_resize(const TensorArgs &args, hipStream_t stream) __at
 // launch_rgba_resize; the host refuses a framed shape without them.
 hipError_t launch_rgba_resize_framed(const FramedResizeArgs &args, hipStream_t stream) __attribute__((weak));
 hipError_t launch_tensor_resize_framed(const FramedTensorArgs &args, hipStream_t stream) __attribute__((weak));
+// k_roi_tensor over args.n_rois regions of interest (roi_kernel.inl; bands and chunk are set here): k_tensor_resize's launch shape with
+// the region in the place of the picture.  Weak like launch_rgba_resize; h263mi_roi_tensor_on refuses to run without it.
+hipError_t launch_roi_tensor(const RoiArgs &args, hipStream_t stream) __attribute__((weak));
 // k_rgba_filter / k_tensor_filter (h263mi_filter: bilinear, bicubic; filter_kernel.inl): args.f is the W' x H' output that the
 // launch covers and the place of the args.dw x args.dh rectangle in it (bands and chunk are set here).  Weak like
 // launch_rgba_resize; the host refuses a filtered shape without them.

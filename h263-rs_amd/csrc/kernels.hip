@@ -9,6 +9,7 @@
 #include "plane_filter_kernel.inl"
 #include "plane_resize_kernel.inl"
 #include "resize_kernel.inl"
+#include "roi_kernel.inl"
 #include "tensor_resize_kernel.inl"
 #include "synth.inl"
 
@@ -1184,6 +1185,38 @@ hipError_t launch_probe(int mode, int shape, const void *in, void *out, size_t b
     else if (shape == 0) hipLaunchKernelGGL((k_probe<2, 1, false>), dim3(256), dim3(256), 0, stream, pi, po, n);
     else if (shape == 1) hipLaunchKernelGGL((k_probe<2, 8, false>), dim3(256), dim3(1024), 0, stream, pi, po, n);
     else hipLaunchKernelGGL((k_probe<2, 1, true>), dim3(256), dim3(256), 0, stream, pi, po, n);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
+// k_roi_tensor: a device table of regions of interest over full-size RGBA, each cut out and area-averaged into its own
+// 3 x H' x W' tensor (h263mi_roi_tensor_on; roi_kernel.inl).  k_tensor_resize's launch shape with the region in the place of the
+// picture: one wave per workgroup, no barrier, blockIdx.y = region, blockIdx.z = segment of 64 output columns, blockIdx.x = band
+// of RESIZE_ROWS output rows in XCD order.  A wave validates its region and makes its spans itself.
+// (Last in the file: the kernels above compile to what they were, to the branch labels' numbers.)
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_roi_tensor(RoiArgs a)
+{
+    __shared__ __attribute__((aligned(16))) ResizeLds lds;
+    const uint32_t band = (blockIdx.x & 7u) * a.t.r.chunk + (blockIdx.x >> 3);
+    if (band >= a.t.r.bands) return;
+    const int lane = threadIdx.x & 63;
+    RoiLane t;
+    roi_tensor_item(a, lds, band, blockIdx.z, blockIdx.y, [&](auto f) { f(lane, t); });
+}
+
+hipError_t launch_roi_tensor(const RoiArgs &args, hipStream_t stream)
+{
+    if (!args.n_rois) return hipSuccess;
+    const ResizeArgs &r = args.t.r;
+    if (args.n_rois > 65535 || args.t.dtype > TENSOR_BF16 || !r.ow || !r.oh || r.ow > 65535 || r.oh > 65535 || !r.w || !r.h || r.w > 65535 ||
+        r.h > 65535 || (uint64_t)r.w * r.h >= (1ull << 30) || !r.n_pictures || !r.src || !args.rois || !args.dst)
+        return hipErrorInvalidValue;
+    RoiArgs a = args;
+    a.t.r.bands = (r.oh + RESIZE_ROWS - 1) / RESIZE_ROWS;
+    a.t.r.chunk = (a.t.r.bands + 7) / 8;
+    const dim3 grid(a.t.r.chunk * 8, a.n_rois, (r.ow + 63) / 64);
+    hipLaunchKernelGGL(k_roi_tensor, grid, dim3(64), 0, stream, a);
     return hipGetLastError();
 }
 

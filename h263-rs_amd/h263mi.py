@@ -106,6 +106,8 @@ EXPORTS = [
     "h263mi_filter_taps", "h263mi_batch_set_rgba_resize_filtered", "h263mi_batch_set_tensor_output_filtered",
     "h263mi_render_rgba_resize_filtered", "h263mi_render_tensor_filtered", "h263mi_mixed_set_rgba_resize_filtered",
     "h263mi_mixed_set_tensor_output_filtered", "h263mi_batch_set_yuv_resize_filtered", "h263mi_render_yuv_resize_filtered",
+    # ABI 7, additive: a device table of ROIs over full-size RGBA, cut out and resized into one tensor batch
+    "h263mi_roi_tensor_on", "h263mi_batch_roi_tensor",
 ]
 FILTER_AREA, FILTER_BILINEAR, FILTER_BICUBIC = 0, 1, 2
 FRAME_STRETCH, FRAME_LETTERBOX, FRAME_COVER, FRAME_WINDOW = 0, 1, 2, 3
@@ -410,6 +412,33 @@ def adler32_spans(dev_ptr, buffer_bytes, spans, seed=1, n_digests=None, device_i
     return list(out)[:n_digests]
 
 
+class Roi(C.Structure):
+    """h263mi_roi: the rectangle (x, y, w, h) of full-size picture `picture`; reserved is 0"""
+    _fields_ = [("picture", C.c_uint32), ("x", C.c_uint16), ("y", C.c_uint16), ("w", C.c_uint16), ("h", C.c_uint16),
+                ("reserved", C.c_uint32)]
+
+
+def roi_table(rois):
+    """(picture, x, y, w, h[, reserved]) tuples -> the table as a (K, 4) uint32 array, 16 bytes a record: what is uploaded to
+    the device (fields are cut to their widths, as a C caller's would be)"""
+    out = np.zeros((len(rois), 4), np.uint32)
+    for k, r in enumerate(rois):
+        picture, x, y, w, h = r[:5]
+        out[k] = (picture & 0xffffffff, (x & 0xffff) | (y & 0xffff) << 16, (w & 0xffff) | (h & 0xffff) << 16,
+                  (r[5] if len(r) > 5 else 0) & 0xffffffff)
+    return out
+
+
+def roi_tensor(d_rgba, rgba_bytes, n_pictures, width, height, d_rois, n_rois, tensor, d_out, out_bytes, d_status=None, device_id=0,
+               stream=None):
+    """h263mi_roi_tensor_on: queues the launch that cuts the n_rois ROIs of the DEVICE table d_rois out of the full-size RGBA
+    pictures at d_rgba into the tensor batch at d_out (extent: tensor_extent(n_rois, tensor)); does not wait.  d_status (device,
+    n_rois words, or None): 0 per valid ROI, 1 per invalid one."""
+    cfg = BackendCfg(device_id, 0, stream)
+    _check(lib().h263mi_roi_tensor_on(C.byref(cfg), d_rgba, rgba_bytes, n_pictures, width, height, d_rois, n_rois, _opt(tensor), d_out,
+                                      out_bytes, d_status), "roi_tensor")
+
+
 def _back_to_back(n_streams, picture_bytes):
     return [s * picture_bytes for s in range(n_streams)]
 
@@ -620,6 +649,8 @@ def lib():
         L.h263mi_mixed_set_tensor_output_filtered.argtypes = [vp, vp, vp, vp]
         L.h263mi_batch_set_yuv_resize_filtered.argtypes = [vp, vp, vp]
         L.h263mi_render_yuv_resize_filtered.argtypes = [vp, u8, vp, vp, vp]
+        L.h263mi_roi_tensor_on.argtypes = [vp, vp, C.c_uint64, u32, u16, u16, vp, u32, vp, vp, C.c_uint64, vp]
+        L.h263mi_batch_roi_tensor.argtypes = [vp, vp, C.c_uint64, vp, u32, vp, vp, C.c_uint64, vp]
         _lib = L
     return _lib
 
@@ -1262,6 +1293,12 @@ class Batch:
         out = (C.c_uint32 * max(n_digests, 1))()
         _check(lib().h263mi_batch_adler32_spans(self._h, dev_ptr, buffer_bytes, arr, n, seed, out, n_digests), "batch_adler32_spans")
         return list(out)[:n_digests]
+
+    def roi_tensor(self, d_rgba, rgba_bytes, d_rois, n_rois, tensor, d_out, out_bytes, d_status=None):
+        """h263mi_batch_roi_tensor: sync, then roi_tensor on the batch's device and stream over the pictures it has written into
+        d_rgba in the default shape"""
+        _check(lib().h263mi_batch_roi_tensor(self._h, d_rgba, rgba_bytes, d_rois, n_rois, _opt(tensor), d_out, out_bytes, d_status),
+               "batch_roi_tensor")
 
     def timing_begin(self):
         _check(lib().h263mi_batch_timing_begin(self._h), "timing_begin")

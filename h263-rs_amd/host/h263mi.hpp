@@ -470,6 +470,16 @@ inline std::vector<uint32_t> adler32_spans(const uint8_t *d_base, uint64_t buffe
     return out;
 }
 
+// Queues the launch that cuts the n_rois ROIs of the DEVICE table d_rois out of the n_pictures full-size RGBA pictures at d_rgba
+// into the tensor batch at d_out (h263mi_roi_tensor_on; the extent is h263mi_tensor_extent(n_rois, t)); it does not wait.
+// d_status (device, n_rois words, or nullptr): 0 per valid ROI, 1 per invalid one, decided on the device.
+inline void roi_tensor(const uint8_t *d_rgba, uint64_t rgba_bytes, uint32_t n_pictures, uint16_t width, uint16_t height,
+                       const h263mi_roi *d_rois, uint32_t n_rois, const h263mi_tensor_out &t, void *d_out, uint64_t out_bytes,
+                       uint32_t *d_status = nullptr, const h263mi_backend_cfg *cfg = nullptr)
+{
+    check(h263mi_roi_tensor_on(cfg, d_rgba, rgba_bytes, n_pictures, width, height, d_rois, n_rois, &t, d_out, out_bytes, d_status));
+}
+
 }  // namespace h263
 
 namespace deblock {

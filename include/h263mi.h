@@ -971,6 +971,46 @@ int h263mi_digest_yuv(const h263mi_state *s, uint32_t seed, uint32_t *digest);
 int h263mi_batch_digest_yuv(h263mi_batch *b, uint32_t seed, uint32_t *digests, int *stream_rc);
 int h263mi_mixed_digest_yuv(h263mi_mixed *m, uint32_t seed, uint32_t *digests, int *stream_rc);
 
+/*
+ * ROI CROP-AND-RESIZE (additive, ABI 7): a DEVICE table of boxes over full-size RGBA pictures, each cut out and area-averaged
+ * into one n_rois x 3 x H' x W' tensor batch -- the second stage of a detection pipeline (classifier, re-identification, OCR)
+ * without a trip to the host: the detector writes the table on the stream, this call follows it on the same stream.
+ * d_rgba is what a batch writes into d_rgba in its default shape: picture p at p * width*height*4, rows 4*width bytes apart.
+ * Element (k, p, Y, X) lies k*stride_n + p*stride_c + Y*stride_h + X ELEMENTS behind d_out and is, bit for bit, what
+ * h263mi_render_tensor_framed gives for H263MI_FRAME_WINDOW with the source (x, y, w, h) of ROI k, the destination
+ * (0, 0, W', H'), picture `picture` as the full-size RGBA and the same t: the area average with divisor w*h, one rounding half
+ * up, then fl32(fl32(u * scale[c]) + bias[c]), converted as h263mi_tensor_out documents.  The extent is
+ * h263mi_tensor_extent(n_rois, t).
+ * Validity is decided per ROI ON THE DEVICE -- the host never reads d_rois.  A ROI is valid when reserved == 0,
+ * picture < n_pictures, w >= 1, h >= 1, x + w <= width and y + h <= height (the sums taken in 32 bits).  For an invalid ROI
+ * nothing of d_rgba is read and no element of its tensor is written; d_status[k] becomes 1, for a valid ROI 0.  d_status may be
+ * NULL.  Any garbage in the table is safe.
+ */
+typedef struct h263mi_roi {
+    uint32_t picture;        /* index into the n_pictures full-size pictures */
+    uint16_t x, y, w, h;     /* the source rectangle, in pixels of that picture */
+    uint32_t reserved;       /* 0 */
+} h263mi_roi;                /* 16 bytes */
+
+/* Queues ONE launch on cfg's device and stream (NULL: device 0, the null stream) and returns; it does not wait.  d_rgba, d_rois,
+ * d_out and d_status are DEVICE pointers; picture sizes are any 1..65535 with width*height < 2^30, not only decodable ones.
+ * H263MI_ERR_INVALID_ARGUMENT, decided on the host before any device call: t NULL or anything h263mi_tensor_extent(n_rois, t)
+ * refuses (for n_rois == 0: h263mi_tensor_extent(1, t)); n_pictures, width or height 0; width*height >= 2^30; n_rois > 65535;
+ * d_rgba, d_rois or d_out NULL while n_rois > 0; d_rgba not a multiple of 16; d_out not a multiple of the element size;
+ * rgba_bytes < n_pictures * width*height*4; out_bytes below the extent.  n_rois == 0 is H263MI_OK with no launch.  Without a
+ * device: H263MI_ERR_NO_DEVICE, after the argument checks.  A failure of the HIP runtime is H263MI_ERR_HIP; the same call then
+ * succeeds. */
+int h263mi_roi_tensor_on(const h263mi_backend_cfg *cfg,
+                         const uint8_t *d_rgba, uint64_t rgba_bytes, uint32_t n_pictures, uint16_t width, uint16_t height,
+                         const h263mi_roi *d_rois, uint32_t n_rois,
+                         const h263mi_tensor_out *t, void *d_out, uint64_t out_bytes, uint32_t *d_status);
+/* h263mi_batch_sync(b) -- which delivers a deferred rendering of H263MI_CFG_PIPELINE_POST --, then the call above with the
+ * batch's device, stream and picture size and n_pictures = the batch's streams: the way to cut ROIs out of what the batch has
+ * written into d_rgba in its default shape.  An error of the sync is returned and nothing is queued. */
+int h263mi_batch_roi_tensor(h263mi_batch *b, const uint8_t *d_rgba, uint64_t rgba_bytes,
+                            const h263mi_roi *d_rois, uint32_t n_rois,
+                            const h263mi_tensor_out *t, void *d_out, uint64_t out_bytes, uint32_t *d_status);
+
 /* ======================================================================= */
 /* Device memory + synthetic macroblock records (bench / test support)      */
 /* ======================================================================= */
