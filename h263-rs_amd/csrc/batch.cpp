@@ -1258,6 +1258,161 @@ int h263mi_batch_roi_tensor(h263mi_batch *b, const uint8_t *d_rgba, uint64_t rgb
     return roi_tensor_launch(a, b->stream);
 }
 
+// =========================================================================================
+// change maps (change_kernel.inl)
+// =========================================================================================
+int h263mi_change_extent(uint32_t n_pictures, uint32_t width, uint32_t height, const h263mi_change *c, uint32_t *gw, uint32_t *gh,
+                         uint64_t *cells_bytes)
+{
+    static_assert(sizeof(h263mi_change) == 16 && sizeof(h263mi_plane_set) == 32, "the structures are part of the ABI");
+    if (!c || c->reserved[0] || c->reserved[1] || c->reserved2 || c->cell_log2 < 3 || c->cell_log2 > 6 || c->roll > 1)
+        return H263MI_ERR_INVALID_ARGUMENT;
+    if (!width || !height || width > 65535 || height > 65535 || (uint64_t)width * height >= (1ull << 30)) return H263MI_ERR_INVALID_ARGUMENT;
+    if (n_pictures > CHANGE_MAX_PICTURES) return H263MI_ERR_INVALID_ARGUMENT;
+    const uint32_t w = ((width - 1u) >> c->cell_log2) + 1u, h = ((height - 1u) >> c->cell_log2) + 1u;
+    if (gw) *gw = w;
+    if (gh) *gh = h;
+    if (cells_bytes) *cells_bytes = (uint64_t)n_pictures * w * h * 4u;        // (below 2^16 * 2^24 * 4)
+    return H263MI_OK;
+}
+
+// the bytes from a set's base to behind the last byte of its n pictures; false: the sum wraps
+static bool plane_set_end(const h263mi_plane_set &s, uint32_t n, uint32_t w, uint32_t h, uint64_t *end)
+{
+    uint64_t a, b;
+    if (__builtin_mul_overflow((uint64_t)(n - 1u), s.picture_stride, &a) || __builtin_mul_overflow((uint64_t)(h - 1u), s.pitch, &b) ||
+        __builtin_add_overflow(a, b, &a) || __builtin_add_overflow(a, (uint64_t)w, &a))
+        return false;
+    *end = a;
+    return true;
+}
+
+// The arguments of a change map, decided on the host in the order include/h263mi.h lists; *out, *sel: the launches they come to.
+// cur_span: the bytes behind cur->d_base that prev may not touch under roll (0: the n pictures of cur).
+static int change_args(const h263mi_plane_set *cur, const h263mi_plane_set *prev, uint32_t n, uint32_t w, uint32_t h, const h263mi_change *c,
+                       uint32_t *d_cells, uint64_t cells_bytes, h263mi_change_summary *d_summary, uint32_t *d_selected, uint32_t *d_count,
+                       uint64_t cur_span, ChangeArgs *out, ChangeSelectArgs *sel)
+{
+    uint32_t gw = 0, gh = 0;
+    uint64_t extent = 0;
+    RC_TRY(h263mi_change_extent(n, w, h, c, &gw, &gh, &extent));
+    ChangeArgs a{};
+    if (n) {
+        if (!cur || !prev || !d_summary || !cur->d_base || !prev->d_base) return H263MI_ERR_INVALID_ARGUMENT;
+        if (h > 1 && (cur->pitch < w || prev->pitch < w)) return H263MI_ERR_INVALID_ARGUMENT;
+        uint64_t cur_end, prev_end;
+        if (!plane_set_end(*cur, n, w, h, &cur_end) || cur_end > cur->bytes) return H263MI_ERR_INVALID_ARGUMENT;
+        if (!plane_set_end(*prev, n, w, h, &prev_end) || prev_end > prev->bytes) return H263MI_ERR_INVALID_ARGUMENT;
+        if (d_cells && cells_bytes < extent) return H263MI_ERR_INVALID_ARGUMENT;
+        if (!d_selected != !d_count) return H263MI_ERR_INVALID_ARGUMENT;
+        if (c->roll) {
+            uint64_t one = 0;
+            plane_set_end(*prev, 1, w, h, &one);                              // (no more than prev_end)
+            if (n > 1 && prev->picture_stride < one) return H263MI_ERR_INVALID_ARGUMENT;
+            const uintptr_t c0 = (uintptr_t)cur->d_base, p0 = (uintptr_t)prev->d_base;
+            const uint64_t span = cur_span ? cur_span : cur_end;
+            if (p0 < c0 + span && c0 < p0 + prev_end) return H263MI_ERR_INVALID_ARGUMENT;
+        }
+        a.cur = cur->d_base;
+        a.prev = prev->d_base;
+        a.cur_pitch = cur->pitch, a.cur_stride = cur->picture_stride;
+        a.prev_pitch = prev->pitch, a.prev_stride = prev->picture_stride;
+        a.cur_align = change_align(cur->d_base, cur->pitch, cur->picture_stride);
+        a.prev_align = change_align(prev->d_base, prev->pitch, prev->picture_stride);
+    } else if (!d_selected != !d_count) {
+        return H263MI_ERR_INVALID_ARGUMENT;
+    }
+    a.cells = d_cells;
+    a.summary = d_summary;
+    a.w = w, a.h = h, a.gw = gw, a.gh = gh;
+    a.cell_log2 = c->cell_log2, a.roll = c->roll, a.threshold = c->cell_threshold;
+    a.n_pictures = n;
+    a.segs = (w + CHANGE_SEG - 1u) / CHANGE_SEG;
+    *out = a;
+    *sel = ChangeSelectArgs{d_summary, nullptr, d_selected, d_count, n, c->min_changed_cells};
+    return H263MI_OK;
+}
+
+// the clearing of the summaries, k_change, and k_change_select when a list is wanted, queued on `stream` of the current device
+static int change_launch(const ChangeArgs &a, const ChangeSelectArgs &sel, hipStream_t stream)
+{
+    if (!a.n_pictures && !sel.count) return H263MI_OK;
+    if (!launch_change) return H263MI_ERR_HIP;             // (kernels.h: only a stub runtime lacks it)
+    auto queue = [&]() -> int {
+        if (a.n_pictures) HIP_TRY(hipMemsetAsync(a.summary, 0, (size_t)a.n_pictures * sizeof(h263mi_change_summary), stream));
+        HIP_TRY(launch_change(a, sel.count ? &sel : nullptr, stream));
+        return H263MI_OK;
+    };
+    return digest_rc(queue());                             // (whatever the runtime refuses is H263MI_ERR_HIP)
+}
+
+int h263mi_batch::change_last(const h263mi_plane_set *prev, const h263mi_change *c, uint32_t *d_cells, uint64_t cells_bytes,
+                              h263mi_change_summary *d_summary, uint32_t *d_selected, uint32_t *d_count, int *stream_rc)
+{
+    // the luma planes of the frame store, as copy_yuv reads them: set 0 at frames[0], set 1 behind it
+    const uint64_t set_bytes = (uint64_t)(frames[1] - frames[0]);
+    const h263mi_plane_set store{frames[0], 2 * set_bytes, L.pitch_y, L.frame_bytes};
+    ChangeArgs a;
+    ChangeSelectArgs sel;
+    RC_TRY(change_args(&store, prev, n, L.width, L.height, c, d_cells, cells_bytes, d_summary, d_selected, d_count, store.bytes, &a, &sel));
+    RC_TRY(time_close());                        // a change map is not part of any kernel's time
+    std::vector<uint32_t> words(n);
+    bool missing = false, same = true;
+    for (uint32_t i = 0; i < n; i++) {
+        words[i] = ss[i].cur < 0 ? 0u : (CHANGE_VALID | (ss[i].cur == 1 ? CHANGE_SET1 : 0u));
+        missing |= ss[i].cur < 0;
+        same &= words[i] == words[0];
+    }
+    a.cur_set1 = set_bytes;
+    a.cur_align = change_align(store.d_base, store.pitch, store.picture_stride, set_bytes);
+    if (same && !missing) {
+        a.cur = frames[ss[0].cur];               // every stream's picture lies in one set: no words
+    } else {
+        const uint32_t *d_words = nullptr;
+        RC_TRY(digest_rc(upload(word_ring, words.data(), &d_words, stream)));
+        a.words = sel.words = d_words;
+    }
+    RC_TRY(change_launch(a, sel, stream));
+    if (stream_rc)
+        for (uint32_t i = 0; i < n; i++) stream_rc[i] = ss[i].cur < 0 ? H263MI_ERR_NO_PICTURE : H263MI_OK;
+    return missing && !stream_rc ? H263MI_ERR_NO_PICTURE : H263MI_OK;
+}
+
+int h263mi_change_map_on(const h263mi_backend_cfg *cfg, const h263mi_plane_set *cur, const h263mi_plane_set *prev, uint32_t n_pictures,
+                         uint32_t width, uint32_t height, const h263mi_change *c, uint32_t *d_cells, uint64_t cells_bytes,
+                         h263mi_change_summary *d_summary, uint32_t *d_selected, uint32_t *d_count)
+{
+    ChangeArgs a;
+    ChangeSelectArgs sel;
+    RC_TRY(change_args(cur, prev, n_pictures, width, height, c, d_cells, cells_bytes, d_summary, d_selected, d_count, 0, &a, &sel));
+    if (!n_pictures && !d_count) return H263MI_OK;
+    const int dev = cfg ? cfg->device_id : 0;
+    RC_TRY(check_device(dev));
+    DeviceGuard g(dev);
+    if (!g.ok) return H263MI_ERR_NO_DEVICE;
+    return change_launch(a, sel, cfg ? (hipStream_t)cfg->stream : nullptr);
+}
+
+int h263mi_batch_change_map(h263mi_batch *b, const h263mi_plane_set *cur, const h263mi_plane_set *prev, const h263mi_change *c,
+                            uint32_t *d_cells, uint64_t cells_bytes, h263mi_change_summary *d_summary, uint32_t *d_selected, uint32_t *d_count)
+{
+    if (!b) return H263MI_ERR_INVALID_ARGUMENT;
+    ChangeArgs a;
+    ChangeSelectArgs sel;
+    RC_TRY(change_args(cur, prev, b->n, b->L.width, b->L.height, c, d_cells, cells_bytes, d_summary, d_selected, d_count, 0, &a, &sel));
+    DeviceGuard g(b->device);
+    RC_TRY(b->sync());                           // (the deferred rendering of a pipelined batch, the second stream of an overlapped one)
+    return change_launch(a, sel, b->stream);
+}
+
+int h263mi_batch_change_last(h263mi_batch *b, const h263mi_plane_set *prev, const h263mi_change *c, uint32_t *d_cells, uint64_t cells_bytes,
+                             h263mi_change_summary *d_summary, uint32_t *d_selected, uint32_t *d_count, int *stream_rc)
+{
+    if (!b) return H263MI_ERR_INVALID_ARGUMENT;
+    DeviceGuard g(b->device);
+    return b->change_last(prev, c, d_cells, cells_bytes, d_summary, d_selected, d_count, stream_rc);
+}
+
 int h263mi_batch_timing_begin(h263mi_batch *b)
 {
     if (!b) return H263MI_ERR_INVALID_ARGUMENT;

@@ -250,6 +250,11 @@ struct h263mi_batch {
     // the Adler-32 of Y, Cb, Cr of every stream's last picture, read in place (3 spans per stream, one launch pair); a stream
     // without a picture: digest 0, stream_rc H263MI_ERR_NO_PICTURE -- which is also what the call returns when stream_rc is null
     int digest_yuv(uint32_t seed, uint32_t *digests, int *stream_rc);
+    // ---- change maps (h263mi_batch_change_last): cur is the luma of every stream's last picture, read in place; the streams'
+    // CHANGE_* words (valid, frame set) travel through word_ring unless every stream has a picture in the same set.  Queues the
+    // launches on `stream` and returns; a stream without a picture is left out as digest_yuv reports it
+    int change_last(const h263mi_plane_set *prev, const h263mi_change *c, uint32_t *d_cells, uint64_t cells_bytes,
+                    h263mi_change_summary *d_summary, uint32_t *d_selected, uint32_t *d_count, int *stream_rc);
 };
 
 namespace h263mi {

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "dev_common.h"
+#include "change_kernel.inl"
 #include "digest_kernel.inl"
 #include "filter_kernel.inl"
 #include "plane_filter_kernel.inl"
@@ -64,6 +65,10 @@ hipError_t launch_tensor_resize_framed(const FramedTensorArgs &args, hipStream_t
 // k_roi_tensor over args.n_rois regions of interest (roi_kernel.inl; bands and chunk are set here): k_tensor_resize's launch shape with
 // the region in the place of the picture.  Weak like launch_rgba_resize; h263mi_roi_tensor_on refuses to run without it.
 hipError_t launch_roi_tensor(const RoiArgs &args, hipStream_t stream) __attribute__((weak));
+// k_change over the args.n_pictures x gh x segs work items of a change map (change_kernel.inl; p0 and items_per_wave are set here: a call of very many
+// items goes out in several launches), then, with sel, k_change_select over the summaries.  The caller has cleared the summaries
+// on the stream.  Weak like launch_rgba_resize; the change-map entry points refuse to run without it.
+hipError_t launch_change(const ChangeArgs &args, const ChangeSelectArgs *sel, hipStream_t stream) __attribute__((weak));
 // k_rgba_filter / k_tensor_filter (h263mi_filter: bilinear, bicubic; filter_kernel.inl): args.f is the W' x H' output that the
 // launch covers and the place of the args.dw x args.dh rectangle in it (bands and chunk are set here).  Weak like
 // launch_rgba_resize; the host refuses a filtered shape without them.

@@ -2,6 +2,7 @@
 // Built with: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (no fast-math).
 #include "kernels.h"
 
+#include "change_kernel.inl"
 #include "digest_kernel.inl"
 #include "post_kernel.inl"
 #include "recon_kernel.inl"
@@ -1218,6 +1219,59 @@ hipError_t launch_roi_tensor(const RoiArgs &args, hipStream_t stream)
     const dim3 grid(a.t.r.chunk * 8, a.n_rois, (r.ow + 63) / 64);
     hipLaunchKernelGGL(k_roi_tensor, grid, dim3(64), 0, stream, a);
     return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
+// k_change, k_change_select: change maps of 8-bit planes (h263mi_change_map_on, h263mi_batch_change_last; change_kernel.inl).
+// One wave per workgroup, no barrier: blockIdx.x = the wave's run of items_per_wave work items (segments of CHANGE_SEG columns of
+// a cell row, row after row), blockIdx.y = picture (from args.p0).  A launch holds at most CHANGE_GRID_MAX workgroups, whole
+// pictures; the select kernel is one wave.
+// (Behind everything else in the file, as k_roi_tensor was: the kernels above compile to what they were.)
+// ---------------------------------------------------------------------------------------
+constexpr uint64_t CHANGE_GRID_MAX = 1u << 24;
+
+__global__ __launch_bounds__(64) void k_change(ChangeArgs a)
+{
+    __shared__ __attribute__((aligned(16))) ChangeLds lds;
+    const int lane = threadIdx.x & 63;
+    ChangeLane t;
+    change_wave(a, lds, a.p0 + blockIdx.y, blockIdx.x * a.items_per_wave, [&](auto f) { f(lane, t); });
+}
+
+__global__ __launch_bounds__(64) void k_change_select(ChangeSelectArgs f)
+{
+    __shared__ __attribute__((aligned(16))) ChangeLds lds;
+    const int lane = threadIdx.x & 63;
+    ChangeLane t;
+    change_select(f, lds, [&](auto g) { g(lane, t); });
+}
+
+hipError_t launch_change(const ChangeArgs &args, const ChangeSelectArgs *sel, hipStream_t stream)
+{
+    if (args.n_pictures) {
+        if (args.n_pictures > CHANGE_MAX_PICTURES || args.cell_log2 < 3 || args.cell_log2 > 6 || !args.w || !args.h || args.w > 65535 ||
+            args.h > 65535 || (uint64_t)args.w * args.h >= (1ull << 30) || !args.cur || !args.prev || !args.summary ||
+            args.gw != ((args.w - 1u) >> args.cell_log2) + 1u || args.gh != ((args.h - 1u) >> args.cell_log2) + 1u ||
+            args.segs != (args.w + CHANGE_SEG - 1u) / CHANGE_SEG)
+            return hipErrorInvalidValue;
+        ChangeArgs a = args;
+        const uint32_t items = a.gh * a.segs;                              // of a picture (below 2^19: w * h < 2^30)
+        a.items_per_wave = change_items_per_wave((uint64_t)items * a.n_pictures);
+        const uint32_t per_picture = (items + a.items_per_wave - 1u) / a.items_per_wave;
+        const uint32_t per_launch = (uint32_t)(CHANGE_GRID_MAX / per_picture);
+        for (a.p0 = 0; a.p0 < a.n_pictures; a.p0 += per_launch) {
+            const uint32_t n = a.n_pictures - a.p0 < per_launch ? a.n_pictures - a.p0 : per_launch;
+            hipLaunchKernelGGL(k_change, dim3(per_picture, n), dim3(64), 0, stream, a);
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return e;
+        }
+    }
+    if (sel) {
+        if (!sel->selected || !sel->count || (sel->n_pictures && !sel->summary)) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_change_select, dim3(1), dim3(64), 0, stream, *sel);
+        return hipGetLastError();
+    }
+    return hipSuccess;
 }
 
 }  // namespace h263mi

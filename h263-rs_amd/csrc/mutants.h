@@ -32,6 +32,12 @@
 //   -DH263MI_MUTATE_FILTER_SINGLE_ROUNDING   the horizontal pass hands on its unrounded sum: one weighted sum, one rounding
 //   -DH263MI_MUTATE_FILTER_NO_CLAMP          the horizontal pass keeps the low 8 bits of a value outside 0..255 instead of
 //                                            clamping it
+// ... and two of the change maps (change_kernel.inl), which the CPU checker alone is built with (tests/test_sim_change.py):
+//   -DH263MI_MUTATE_CHANGE_EDGE_AS_FULL      change_judge compares an edge cell as if it were full: the raw SAD against the
+//                                            threshold instead of the mean difference
+//   -DH263MI_MUTATE_CHANGE_SEGMENT_CELL      change_item takes a later segment's first cell from the pixel in front of the
+//                                            segment: its first chunk (and every one behind it) is attributed to the cell on
+//                                            its left
 // Two parts.  The switches need nothing and are included by post_kernel.inl and recon_kernel.inl; the IDCT helper is included
 // by recon_kernel.inl (which defines H263MI_MUTANTS_WITH_IDCT) behind the definitions it uses (f32x2, splat2, BasisPtr,
 // basis_pair).
@@ -105,6 +111,16 @@ constexpr bool kFilterSingleRounding = false;
 constexpr bool kFilterNoClamp = true;
 #else
 constexpr bool kFilterNoClamp = false;
+#endif
+#if defined(H263MI_MUTATE_CHANGE_EDGE_AS_FULL)
+constexpr bool kChangeEdgeAsFull = true;
+#else
+constexpr bool kChangeEdgeAsFull = false;
+#endif
+#if defined(H263MI_MUTATE_CHANGE_SEGMENT_CELL)
+constexpr bool kChangeSegmentCell = true;
+#else
+constexpr bool kChangeSegmentCell = false;
 #endif
 
 }  // namespace mutants

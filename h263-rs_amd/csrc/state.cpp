@@ -250,6 +250,15 @@ int h263mi_digest_yuv(const h263mi_state *s, uint32_t seed, uint32_t *digest)
     return digest_rc(s->b->digest_yuv(seed, digest, nullptr));
 }
 
+int h263mi_change_last(const h263mi_state *s, const h263mi_plane_set *prev, const h263mi_change *c, uint32_t *d_cells, uint64_t cells_bytes,
+                       h263mi_change_summary *d_summary, uint32_t *d_selected, uint32_t *d_count)
+{
+    if (!s) return H263MI_ERR_INVALID_ARGUMENT;
+    if (!s->has_last || !s->b) return H263MI_ERR_NO_PICTURE;
+    DeviceGuard g(s->cfg.device_id);
+    return s->b->change_last(prev, c, d_cells, cells_bytes, d_summary, d_selected, d_count, nullptr);
+}
+
 // `strength` of the rendering calls: 0..12, or H263MI_STRENGTH_FROM_HEADER = what the last picture's own header asks for
 // (QUANT_TO_STRENGTH[quantizer] when USE_DEBLOCKER is set: deblock.rs:5-8, picture.rs:61-64)
 static int state_strength(const h263mi_state *s, uint8_t strength, h263mi_batch::Strengths &st)

@@ -108,6 +108,8 @@ EXPORTS = [
     "h263mi_mixed_set_tensor_output_filtered", "h263mi_batch_set_yuv_resize_filtered", "h263mi_render_yuv_resize_filtered",
     # ABI 7, additive: a device table of ROIs over full-size RGBA, cut out and resized into one tensor batch
     "h263mi_roi_tensor_on", "h263mi_batch_roi_tensor",
+    # ABI 7, additive: change maps -- per-cell SAD of two plane sets, per-picture summaries, the list of changed pictures
+    "h263mi_change_extent", "h263mi_change_map_on", "h263mi_batch_change_map", "h263mi_batch_change_last", "h263mi_change_last",
 ]
 FILTER_AREA, FILTER_BILINEAR, FILTER_BICUBIC = 0, 1, 2
 FRAME_STRETCH, FRAME_LETTERBOX, FRAME_COVER, FRAME_WINDOW = 0, 1, 2, 3
@@ -439,6 +441,52 @@ def roi_tensor(d_rgba, rgba_bytes, n_pictures, width, height, d_rois, n_rois, te
                                       out_bytes, d_status), "roi_tensor")
 
 
+class Change(C.Structure):
+    """h263mi_change: cells of 1 << cell_log2 pixels (3..6); a cell is changed when sad * c*c > cell_threshold * pixels(cell); a
+    picture is selected when changed_cells >= min_changed_cells; roll: prev takes cur's pixels"""
+    _fields_ = [("cell_log2", C.c_uint8), ("roll", C.c_uint8), ("reserved", C.c_uint8 * 2), ("cell_threshold", C.c_uint32),
+                ("min_changed_cells", C.c_uint32), ("reserved2", C.c_uint32)]
+
+
+class PlaneSet(C.Structure):
+    """h263mi_plane_set: `bytes` bytes of device memory at d_base; rows `pitch` apart, picture p's plane at p * picture_stride"""
+    _fields_ = [("d_base", C.c_void_p), ("bytes", C.c_uint64), ("pitch", C.c_uint64), ("picture_stride", C.c_uint64)]
+
+
+class ChangeSummary(C.Structure):
+    _fields_ = [("sad", C.c_uint64), ("changed_cells", C.c_uint32), ("max_cell_sad", C.c_uint32)]
+
+
+CHANGE_SUMMARY_DTYPE = np.dtype([("sad", np.uint64), ("changed_cells", np.uint32), ("max_cell_sad", np.uint32)])
+
+
+def make_change(cell_log2=4, cell_threshold=0, min_changed_cells=1, roll=0):
+    return Change(cell_log2, roll, (C.c_uint8 * 2)(0, 0), cell_threshold, min_changed_cells, 0)
+
+
+def planes_default_set(d_deblocked, n_streams, w, h):
+    """the luma planes of the tightly packed Y, Cb, Cr that a batch without a YUV layout writes to d_deblocked, as a PlaneSet"""
+    picture = w * h + 2 * ((w + 1) // 2) * ((h + 1) // 2)
+    return PlaneSet(d_deblocked, n_streams * picture, w, picture)
+
+
+def change_extent(n_pictures, width, height, change):
+    """h263mi_change_extent -> (gw, gh, cells_bytes)"""
+    gw, gh, nb = C.c_uint32(0), C.c_uint32(0), C.c_uint64(0)
+    _check(lib().h263mi_change_extent(n_pictures, width, height, _opt(change), C.byref(gw), C.byref(gh), C.byref(nb)), "change_extent")
+    return gw.value, gh.value, nb.value
+
+
+def change_map(cur, prev, n_pictures, width, height, change, d_cells, cells_bytes, d_summary, d_selected=None, d_count=None, device_id=0,
+               stream=None):
+    """h263mi_change_map_on: queues the launches that compare the PlaneSets cur and prev picture by picture -- cell SADs to d_cells
+    (device, or None), a ChangeSummary per picture to d_summary, the ascending list of the pictures with changed_cells >=
+    min_changed_cells to d_selected and its length to d_count (both device, or both None); does not wait."""
+    cfg = BackendCfg(device_id, 0, stream)
+    _check(lib().h263mi_change_map_on(C.byref(cfg), _opt(cur), _opt(prev), n_pictures, width, height, _opt(change), d_cells, cells_bytes,
+                                      d_summary, d_selected, d_count), "change_map")
+
+
 def _back_to_back(n_streams, picture_bytes):
     return [s * picture_bytes for s in range(n_streams)]
 
@@ -651,6 +699,11 @@ def lib():
         L.h263mi_render_yuv_resize_filtered.argtypes = [vp, u8, vp, vp, vp]
         L.h263mi_roi_tensor_on.argtypes = [vp, vp, C.c_uint64, u32, u16, u16, vp, u32, vp, vp, C.c_uint64, vp]
         L.h263mi_batch_roi_tensor.argtypes = [vp, vp, C.c_uint64, vp, u32, vp, vp, C.c_uint64, vp]
+        L.h263mi_change_extent.argtypes = [u32, u32, u32, vp, vp, vp, vp]
+        L.h263mi_change_map_on.argtypes = [vp, vp, vp, u32, u32, u32, vp, vp, C.c_uint64, vp, vp, vp]
+        L.h263mi_batch_change_map.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, vp, vp, vp]
+        L.h263mi_batch_change_last.argtypes = [vp, vp, vp, vp, C.c_uint64, vp, vp, vp, vp]
+        L.h263mi_change_last.argtypes = [vp, vp, vp, vp, C.c_uint64, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -818,6 +871,11 @@ class H263State:
         d = C.c_uint32(0)
         _check(lib().h263mi_digest_yuv(self._h, seed, C.byref(d)), "digest_yuv")
         return d.value
+
+    def change_last(self, prev, change, d_cells, cells_bytes, d_summary, d_selected=None, d_count=None):
+        """h263mi_change_last: change_map with the last picture's luma, read in place, as cur (one picture); queues and returns"""
+        _check(lib().h263mi_change_last(self._h, _opt(prev), _opt(change), d_cells, cells_bytes, d_summary, d_selected, d_count),
+               "change_last")
 
     def render_rgba(self, strength=0):
         v = self._view(lib().h263mi_get_last_picture, "get_last_picture")
@@ -1299,6 +1357,20 @@ class Batch:
         d_rgba in the default shape"""
         _check(lib().h263mi_batch_roi_tensor(self._h, d_rgba, rgba_bytes, d_rois, n_rois, _opt(tensor), d_out, out_bytes, d_status),
                "batch_roi_tensor")
+
+    def change_map(self, cur, prev, change, d_cells, cells_bytes, d_summary, d_selected=None, d_count=None):
+        """h263mi_batch_change_map: sync, then change_map on the batch's device and stream with its picture size and stream count
+        -- for two d_deblocked buffers a caller alternates between (planes_default_set)"""
+        _check(lib().h263mi_batch_change_map(self._h, _opt(cur), _opt(prev), _opt(change), d_cells, cells_bytes, d_summary, d_selected,
+                                             d_count), "batch_change_map")
+
+    def change_last(self, prev, change, d_cells, cells_bytes, d_summary, d_selected=None, d_count=None, stream_rc=True):
+        """h263mi_batch_change_last: change_map with the luma of every stream's last picture, read in place, as cur; queues and
+        returns -> rcs (per stream 0 or ERR_NO_PICTURE).  stream_rc=None: a stream without a picture raises ERR_NO_PICTURE"""
+        rcs = (C.c_int * self.n)() if stream_rc is not None else None
+        _check(lib().h263mi_batch_change_last(self._h, _opt(prev), _opt(change), d_cells, cells_bytes, d_summary, d_selected, d_count,
+                                              rcs), "batch_change_last")
+        return list(rcs) if rcs is not None else None
 
     def timing_begin(self):
         _check(lib().h263mi_batch_timing_begin(self._h), "timing_begin")

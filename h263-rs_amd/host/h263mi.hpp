@@ -254,6 +254,17 @@ public:
         return d;
     }
 
+    // The change map of the last picture's luma, read in place, against `prev` (h263mi_change_last; one picture): queues its
+    // launches and returns.  false before the first picture, when nothing is queued
+    bool change_last(const h263mi_plane_set &prev, const h263mi_change &c, uint32_t *d_cells, uint64_t cells_bytes,
+                     h263mi_change_summary *d_summary, uint32_t *d_selected = nullptr, uint32_t *d_count = nullptr) const
+    {
+        const int rc = h263mi_change_last(s_, &prev, &c, d_cells, cells_bytes, d_summary, d_selected, d_count);
+        if (rc == H263MI_ERR_NO_PICTURE) return false;
+        check(rc);
+        return true;
+    }
+
     h263mi_state *raw() { return s_; }
 
 private:
@@ -478,6 +489,45 @@ inline void roi_tensor(const uint8_t *d_rgba, uint64_t rgba_bytes, uint32_t n_pi
                        uint32_t *d_status = nullptr, const h263mi_backend_cfg *cfg = nullptr)
 {
     check(h263mi_roi_tensor_on(cfg, d_rgba, rgba_bytes, n_pictures, width, height, d_rois, n_rois, &t, d_out, out_bytes, d_status));
+}
+
+// The grid of a change map and the bytes of n_pictures grids (h263mi_change_extent); throws for a description it refuses
+struct ChangeExtent {
+    uint32_t gw, gh;
+    uint64_t cells_bytes;
+};
+inline ChangeExtent change_extent(uint32_t n_pictures, uint32_t width, uint32_t height, const h263mi_change &c)
+{
+    ChangeExtent e{};
+    check(h263mi_change_extent(n_pictures, width, height, &c, &e.gw, &e.gh, &e.cells_bytes));
+    return e;
+}
+
+// Queues the launches that compare the plane sets cur and prev picture by picture (h263mi_change_map_on): cell SADs to d_cells
+// (device, or nullptr), one summary per picture to d_summary, the ascending list of the pictures with changed_cells >=
+// min_changed_cells to d_selected and its length to d_count (both device, or both nullptr); it does not wait.
+inline void change_map(const h263mi_plane_set &cur, const h263mi_plane_set &prev, uint32_t n_pictures, uint32_t width, uint32_t height,
+                       const h263mi_change &c, uint32_t *d_cells, uint64_t cells_bytes, h263mi_change_summary *d_summary,
+                       uint32_t *d_selected = nullptr, uint32_t *d_count = nullptr, const h263mi_backend_cfg *cfg = nullptr)
+{
+    check(h263mi_change_map_on(cfg, &cur, &prev, n_pictures, width, height, &c, d_cells, cells_bytes, d_summary, d_selected, d_count));
+}
+// ... over what batch b has written: h263mi_batch_sync, then the call above with the batch's device, stream, size and streams
+inline void batch_change_map(h263mi_batch *b, const h263mi_plane_set &cur, const h263mi_plane_set &prev, const h263mi_change &c,
+                             uint32_t *d_cells, uint64_t cells_bytes, h263mi_change_summary *d_summary, uint32_t *d_selected = nullptr,
+                             uint32_t *d_count = nullptr)
+{
+    check(h263mi_batch_change_map(b, &cur, &prev, &c, d_cells, cells_bytes, d_summary, d_selected, d_count));
+}
+// ... with the luma of every stream's last picture, read in place, as cur (h263mi_batch_change_last) -> per stream H263MI_OK or
+// H263MI_ERR_NO_PICTURE (n_streams: the batch's)
+inline std::vector<int> batch_change_last(h263mi_batch *b, uint32_t n_streams, const h263mi_plane_set &prev, const h263mi_change &c,
+                                          uint32_t *d_cells, uint64_t cells_bytes, h263mi_change_summary *d_summary,
+                                          uint32_t *d_selected = nullptr, uint32_t *d_count = nullptr)
+{
+    std::vector<int> rc(n_streams);
+    check(h263mi_batch_change_last(b, &prev, &c, d_cells, cells_bytes, d_summary, d_selected, d_count, rc.data()));
+    return rc;
 }
 
 }  // namespace h263

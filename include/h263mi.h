@@ -1011,6 +1011,94 @@ int h263mi_batch_roi_tensor(h263mi_batch *b, const uint8_t *d_rgba, uint64_t rgb
                             const h263mi_roi *d_rois, uint32_t n_rois,
                             const h263mi_tensor_out *t, void *d_out, uint64_t out_bytes, uint32_t *d_status);
 
+/*
+ * CHANGE MAPS (additive, ABI 7): which pictures are worth consuming.  Two sets of 8-bit planes of the same size, `cur` and
+ * `prev`, are compared picture by picture on the device; integers only, so every result is exact and independent of the order of
+ * summation.
+ *   Cells.    Pictures are W x H, 1..65535 each, W*H < 2^30.  Cells are squares of c = 1 << cell_log2 pixels, cell_log2 in 3..6,
+ *             anchored at the picture's origin: the grid is gw = ceil(W/c) by gh = ceil(H/c), edge cells are partial, and
+ *             pixels(cell) is the number of picture pixels in a cell.
+ *   Cell SAD. sad(p, cy, cx) = the sum of |cur - prev| over the cell's pixels, a uint32.  Bytes between rows or behind column W
+ *             never enter.
+ *   Changed.  A cell is changed when (uint64)sad * c*c > (uint64)cell_threshold * pixels(cell): sad > cell_threshold for a full
+ *             cell, the same mean difference for an edge cell.
+ *   Summary.  Per picture: sad = the sum over all cells, changed_cells = the count of changed cells, max_cell_sad = the largest
+ *             raw cell SAD.
+ *   Selection. The indices of the valid pictures with changed_cells >= min_changed_cells go to d_selected[0 .. count), ascending;
+ *             count goes to d_count[0]; entries at count and behind are not written.  d_selected and d_count: both or neither.
+ *   Roll.     With roll = 1 every W x H pixel of prev of a valid picture holds cur's pixel after the launch (bytes outside the rows
+ *             are untouched): the next call measures frame-to-frame change without a copy.  With roll = 0 prev is an anchor and
+ *             is never written.
+ * Out of scope: sets of mixed sizes (one grid has no meaning across sizes); chroma (run h263mi_change_map_on on the chroma
+ * planes); RGBA; per-pixel thresholds.
+ */
+typedef struct h263mi_change {
+    uint8_t  cell_log2;          /* 3..6 */
+    uint8_t  roll;               /* 0 or 1 */
+    uint8_t  reserved[2];        /* 0 */
+    uint32_t cell_threshold;
+    uint32_t min_changed_cells;
+    uint32_t reserved2;          /* 0 */
+} h263mi_change;                 /* 16 bytes */
+
+typedef struct h263mi_plane_set {
+    uint8_t *d_base;             /* DEVICE pointer */
+    uint64_t bytes;              /* behind d_base */
+    uint64_t pitch;              /* bytes from a row to the next; >= W when H > 1 */
+    uint64_t picture_stride;     /* picture p's plane starts at p * picture_stride */
+} h263mi_plane_set;
+
+typedef struct h263mi_change_summary {
+    uint64_t sad;
+    uint32_t changed_cells;
+    uint32_t max_cell_sad;
+} h263mi_change_summary;         /* 16 bytes */
+
+/* The grid and the bytes of n_pictures grids (n_pictures * gw * gh * 4); gw, gh and cells_bytes may each be NULL.  No device.
+ * Also the validator of c: H263MI_ERR_INVALID_ARGUMENT for c NULL, a reserved byte set, cell_log2 outside 3..6, roll > 1, a zero
+ * size, a side above 65535, width*height >= 2^30 or n_pictures > 65535. */
+int h263mi_change_extent(uint32_t n_pictures, uint32_t width, uint32_t height, const h263mi_change *c,
+                         uint32_t *gw, uint32_t *gh, uint64_t *cells_bytes);
+/* Queues its launches (the clearing of the summaries, k_change, k_change_select when a list is wanted) on cfg's device and stream
+ * (NULL: device 0, the null stream) and returns; it does not wait.  d_cells (n_pictures grids, picture p's at d_cells + p*gw*gh,
+ * row-major; may be NULL: no grid wanted), d_summary (n_pictures records, required), d_selected (room for n_pictures indices) and
+ * d_count are DEVICE pointers.  cur is only read: its pictures may overlap and any picture_stride is allowed (0: one plane for
+ * every picture).  Any alignment works; sets whose d_base, pitch and picture_stride are multiples of 16 take the fast path.
+ * H263MI_ERR_INVALID_ARGUMENT, decided on the host before any device call: anything h263mi_change_extent refuses; cur, prev or
+ * d_summary NULL, or a set's d_base NULL, while n_pictures > 0; pitch < width with height > 1; a set whose last byte,
+ * (n_pictures-1) * picture_stride + (height-1) * pitch + width computed without wrapping, lies behind `bytes`; d_cells given with
+ * cells_bytes below the extent; d_selected and d_count not both set or both NULL; under roll, prev pictures that overlap one
+ * another (n_pictures > 1 and picture_stride < (height-1) * pitch + width) or prev's byte range intersecting cur's.
+ * n_pictures == 0 is H263MI_OK with no launch, except that d_count, if given, still becomes 0.  Without a device:
+ * H263MI_ERR_NO_DEVICE, after the argument checks.  A failure of the HIP runtime is H263MI_ERR_HIP; the same call then
+ * succeeds. */
+int h263mi_change_map_on(const h263mi_backend_cfg *cfg, const h263mi_plane_set *cur, const h263mi_plane_set *prev,
+                         uint32_t n_pictures, uint32_t width, uint32_t height, const h263mi_change *c,
+                         uint32_t *d_cells, uint64_t cells_bytes, h263mi_change_summary *d_summary,
+                         uint32_t *d_selected, uint32_t *d_count);
+/* h263mi_batch_sync(b) -- which delivers a deferred rendering of H263MI_CFG_PIPELINE_POST and waits for the second stream of
+ * H263MI_CFG_OVERLAP_POST --, then the call above with the batch's device, stream and picture size and n_pictures = the batch's
+ * streams: the way to compare two d_deblocked buffers that a caller alternates between.  The luma planes of the default plane
+ * output are the set {d_deblocked, n * (w*h + 2*cw*ch), w, w*h + 2*cw*ch}.  An error of the sync is returned and nothing is
+ * queued. */
+int h263mi_batch_change_map(h263mi_batch *b, const h263mi_plane_set *cur, const h263mi_plane_set *prev, const h263mi_change *c,
+                            uint32_t *d_cells, uint64_t cells_bytes, h263mi_change_summary *d_summary,
+                            uint32_t *d_selected, uint32_t *d_count);
+/* cur is the luma of each stream's last decoded picture, read in place from the frame store: the plane h263mi_copy_yuv /
+ * h263mi_batch_copy_yuv would deliver at that moment (the reference planes, not the deblocked ones).  Ordered behind the decodes
+ * already queued; an open timing bracket is closed first; the call queues its launches and returns.  A stream without a picture
+ * is INVALID: nothing of its prev is read or written, its cells are not written, its summary is all zero, it is never selected,
+ * and stream_rc[s] = H263MI_ERR_NO_PICTURE (else 0); with stream_rc NULL the call returns that code after queuing the rest.  The
+ * refusals are those of h263mi_change_map_on without cur; under roll prev may not intersect the frame store. */
+int h263mi_batch_change_last(h263mi_batch *b, const h263mi_plane_set *prev, const h263mi_change *c,
+                             uint32_t *d_cells, uint64_t cells_bytes, h263mi_change_summary *d_summary,
+                             uint32_t *d_selected, uint32_t *d_count, int *stream_rc);
+/* ... of one H263State: one picture.  Before the first picture nothing is queued and the call returns H263MI_ERR_NO_PICTURE,
+ * like h263mi_digest_yuv. */
+int h263mi_change_last(const h263mi_state *s, const h263mi_plane_set *prev, const h263mi_change *c,
+                       uint32_t *d_cells, uint64_t cells_bytes, h263mi_change_summary *d_summary,
+                       uint32_t *d_selected, uint32_t *d_count);
+
 /* ======================================================================= */
 /* Device memory + synthetic macroblock records (bench / test support)      */
 /* ======================================================================= */
