@@ -190,6 +190,28 @@ inline uint32_t change_items_per_wave(uint64_t items)
     return k < 1u ? 1u : (k > 16u ? 16u : (uint32_t)k);
 }
 
+// The launches of k_change (HOST): a call goes out `pictures` whole pictures at a time from p0 = 0 on, the last launch the rest,
+// `waves` workgroups a picture -- at most CHANGE_GRID_MAX workgroups a launch.  items_per_wave: 0 = change_items_per_wave's (the
+// launcher), another value the checker's.
+constexpr uint64_t CHANGE_GRID_MAX = 1u << 24;
+
+struct ChangeLaunch {
+    uint32_t waves, pictures;
+};
+
+inline bool change_plan(ChangeArgs &a, ChangeLaunch &l, uint32_t items_per_wave = 0)
+{
+    if (a.n_pictures > CHANGE_MAX_PICTURES || a.cell_log2 < 3 || a.cell_log2 > 6 || !a.w || !a.h || a.w > 65535 || a.h > 65535 ||
+        (uint64_t)a.w * a.h >= (1ull << 30) || !a.cur || !a.prev || !a.summary || a.gw != ((a.w - 1u) >> a.cell_log2) + 1u ||
+        a.gh != ((a.h - 1u) >> a.cell_log2) + 1u || a.segs != (a.w + CHANGE_SEG - 1u) / CHANGE_SEG)
+        return false;
+    const uint32_t items = a.gh * a.segs;                              // of a picture (below 2^19: w * h < 2^30)
+    a.items_per_wave = items_per_wave ? items_per_wave : change_items_per_wave((uint64_t)items * a.n_pictures);
+    l.waves = (items + a.items_per_wave - 1u) / a.items_per_wave;
+    l.pictures = (uint32_t)(CHANGE_GRID_MAX / l.waves);
+    return true;
+}
+
 // One wave's work: the items first .. first + items_per_wave - 1 of picture p, an item being segment seg of cell row cy and
 // their number cy * segs + seg.  `each(f)` runs f(lane, lane_state) for the lanes this thread stands for: the one of its hardware
 // lane on the GPU, all 64 in turn in the CPU checker.  Everything outside `each` is wave-uniform.

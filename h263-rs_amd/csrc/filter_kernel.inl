@@ -82,6 +82,25 @@ struct TensorFilterArgs {
     TensorArgs t;                // scale, bias, dtype, bgr, strides; t.r is not used
 };
 
+// what a filter launch must hold before a wave runs: tables, a rectangle that is not empty and lies inside the output, a source
+// picture
+inline bool filter_args_ok(const FilterArgs &a)
+{
+    const FrameRect &f = a.f;
+    return a.src && a.dst && a.x.span && a.x.coeff && a.y.span && a.y.coeff && a.x.ksize && a.y.ksize && a.w && a.h && a.dw && a.dh &&
+           f.cw && f.ch && f.keep <= 1 && f.dx <= f.cw && a.dw <= f.cw - f.dx && f.dy <= f.ch && a.dh <= f.ch - f.dy && a.n_pictures <= 65535;
+}
+
+// the launches of k_rgba_filter and k_tensor_filter over the f.cw x f.ch output (HOST)
+inline bool filter_rgba_plan(FilterArgs &a, LaunchDims &d)
+{
+    if (!filter_args_ok(a)) return false;
+    d = band_grid(a.f.ch, FILTER_ROWS, a.n_pictures, (a.f.cw + 63) / 64, a.bands, a.chunk);
+    return true;
+}
+
+inline bool filter_tensor_plan(TensorFilterArgs &a, LaunchDims &d) { return a.t.dtype <= TENSOR_BF16 && filter_rgba_plan(a.fl, d); }
+
 struct FilterLds {
     ResizeLds hand;              // v[0][0..255]: the staged pixels of a chunk; then v[c][lane]: the tensor's 16-bit hand-off
     int32_t kx[FILTER_LDS_TAPS][64];

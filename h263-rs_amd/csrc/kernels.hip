@@ -760,22 +760,29 @@ hipError_t launch_frame_yuv(const ReconArgs &rargs, const PostArgs &pargs, const
 __global__ __launch_bounds__(64) void k_rgba_resize(ResizeArgs a)
 {
     __shared__ __attribute__((aligned(16))) ResizeLds lds;
-    const uint32_t band = (blockIdx.x & 7u) * a.chunk + (blockIdx.x >> 3);
+    const uint32_t band = xcd_band(blockIdx.x, a.chunk);
     if (band >= a.bands) return;
     const int lane = threadIdx.x & 63;
     ResizeLane t;
     resize_item(a, lds, band, blockIdx.z, blockIdx.y, [&](auto f) { f(lane, t); });
 }
 
+// A banded launch (band_launch.h) of `count` pictures or regions: none is no launch; the kernel's plan (beside its Args) refuses
+// the arguments or fills bands, chunk (segs_y) and the grid; one wave per workgroup.
+template <class Args>
+static hipError_t launch_banded(void (*kernel)(Args), bool (*plan)(Args &, LaunchDims &), const Args &args, uint32_t count, hipStream_t stream)
+{
+    if (!count) return hipSuccess;
+    Args a = args;
+    LaunchDims d;
+    if (!plan(a, d)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(kernel, dim3(d.x, d.y, d.z), dim3(64), 0, stream, a);
+    return hipGetLastError();
+}
+
 hipError_t launch_rgba_resize(const ResizeArgs &args, hipStream_t stream)
 {
-    if (!args.n_pictures) return hipSuccess;
-    ResizeArgs a = args;
-    a.bands = (a.oh + RESIZE_ROWS - 1) / RESIZE_ROWS;
-    a.chunk = (a.bands + 7) / 8;
-    const dim3 grid(a.chunk * 8, a.n_pictures, (a.ow + 63) / 64);
-    hipLaunchKernelGGL(k_rgba_resize, grid, dim3(64), 0, stream, a);
-    return hipGetLastError();
+    return launch_banded(k_rgba_resize, resize_plan, args, args.n_pictures, stream);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -786,7 +793,7 @@ hipError_t launch_rgba_resize(const ResizeArgs &args, hipStream_t stream)
 __global__ __launch_bounds__(64) void k_tensor_resize(TensorArgs a)
 {
     __shared__ __attribute__((aligned(16))) ResizeLds lds;
-    const uint32_t band = (blockIdx.x & 7u) * a.r.chunk + (blockIdx.x >> 3);
+    const uint32_t band = xcd_band(blockIdx.x, a.r.chunk);
     if (band >= a.r.bands) return;
     const int lane = threadIdx.x & 63;
     TensorLane t;
@@ -795,14 +802,7 @@ __global__ __launch_bounds__(64) void k_tensor_resize(TensorArgs a)
 
 hipError_t launch_tensor_resize(const TensorArgs &args, hipStream_t stream)
 {
-    if (!args.r.n_pictures) return hipSuccess;
-    if (args.r.n_pictures > 65535 || args.dtype > TENSOR_BF16) return hipErrorInvalidValue;
-    TensorArgs a = args;
-    a.r.bands = (a.r.oh + RESIZE_ROWS - 1) / RESIZE_ROWS;
-    a.r.chunk = (a.r.bands + 7) / 8;
-    const dim3 grid(a.r.chunk * 8, a.r.n_pictures, (a.r.ow + 63) / 64);
-    hipLaunchKernelGGL(k_tensor_resize, grid, dim3(64), 0, stream, a);
-    return hipGetLastError();
+    return launch_banded(k_tensor_resize, tensor_resize_plan, args, args.r.n_pictures, stream);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -814,7 +814,7 @@ hipError_t launch_tensor_resize(const TensorArgs &args, hipStream_t stream)
 __global__ __launch_bounds__(64) void k_rgba_resize_framed(FramedResizeArgs a)
 {
     __shared__ __attribute__((aligned(16))) ResizeLds lds;
-    const uint32_t band = (blockIdx.x & 7u) * a.r.chunk + (blockIdx.x >> 3);
+    const uint32_t band = xcd_band(blockIdx.x, a.r.chunk);
     if (band >= a.r.bands) return;
     const int lane = threadIdx.x & 63;
     ResizeLane t;
@@ -824,41 +824,21 @@ __global__ __launch_bounds__(64) void k_rgba_resize_framed(FramedResizeArgs a)
 __global__ __launch_bounds__(64) void k_tensor_resize_framed(FramedTensorArgs a)
 {
     __shared__ __attribute__((aligned(16))) ResizeLds lds;
-    const uint32_t band = (blockIdx.x & 7u) * a.t.r.chunk + (blockIdx.x >> 3);
+    const uint32_t band = xcd_band(blockIdx.x, a.t.r.chunk);
     if (band >= a.t.r.bands) return;
     const int lane = threadIdx.x & 63;
     TensorLane t;
     framed_tensor_item(a, lds, band, blockIdx.z, blockIdx.y, [&](auto f) { f(lane, t); });
 }
 
-// what a framed launch must hold before a wave runs: a rectangle that is not empty and lies inside the output
-static bool frame_rect_ok(const ResizeArgs &r, const FrameRect &f)
-{
-    return r.ow && r.oh && f.cw && f.ch && f.keep <= 1 && f.dx <= f.cw && r.ow <= f.cw - f.dx && f.dy <= f.ch && r.oh <= f.ch - f.dy;
-}
-
 hipError_t launch_rgba_resize_framed(const FramedResizeArgs &args, hipStream_t stream)
 {
-    if (!args.r.n_pictures) return hipSuccess;
-    if (args.r.n_pictures > 65535 || !frame_rect_ok(args.r, args.f)) return hipErrorInvalidValue;
-    FramedResizeArgs a = args;
-    a.r.bands = (a.f.ch + RESIZE_ROWS - 1) / RESIZE_ROWS;
-    a.r.chunk = (a.r.bands + 7) / 8;
-    const dim3 grid(a.r.chunk * 8, a.r.n_pictures, (a.f.cw + 63) / 64);
-    hipLaunchKernelGGL(k_rgba_resize_framed, grid, dim3(64), 0, stream, a);
-    return hipGetLastError();
+    return launch_banded(k_rgba_resize_framed, framed_resize_plan, args, args.r.n_pictures, stream);
 }
 
 hipError_t launch_tensor_resize_framed(const FramedTensorArgs &args, hipStream_t stream)
 {
-    if (!args.t.r.n_pictures) return hipSuccess;
-    if (args.t.r.n_pictures > 65535 || args.t.dtype > TENSOR_BF16 || !frame_rect_ok(args.t.r, args.f)) return hipErrorInvalidValue;
-    FramedTensorArgs a = args;
-    a.t.r.bands = (a.f.ch + RESIZE_ROWS - 1) / RESIZE_ROWS;
-    a.t.r.chunk = (a.t.r.bands + 7) / 8;
-    const dim3 grid(a.t.r.chunk * 8, a.t.r.n_pictures, (a.f.cw + 63) / 64);
-    hipLaunchKernelGGL(k_tensor_resize_framed, grid, dim3(64), 0, stream, a);
-    return hipGetLastError();
+    return launch_banded(k_tensor_resize_framed, framed_tensor_plan, args, args.t.r.n_pictures, stream);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -870,7 +850,7 @@ hipError_t launch_tensor_resize_framed(const FramedTensorArgs &args, hipStream_t
 __global__ __launch_bounds__(64) void k_rgba_filter(FilterArgs a)
 {
     __shared__ __attribute__((aligned(16))) FilterLds lds;
-    const uint32_t band = (blockIdx.x & 7u) * a.chunk + (blockIdx.x >> 3);
+    const uint32_t band = xcd_band(blockIdx.x, a.chunk);
     if (band >= a.bands) return;
     const int lane = threadIdx.x & 63;
     FilterLane t;
@@ -880,44 +860,21 @@ __global__ __launch_bounds__(64) void k_rgba_filter(FilterArgs a)
 __global__ __launch_bounds__(64) void k_tensor_filter(TensorFilterArgs a)
 {
     __shared__ __attribute__((aligned(16))) FilterLds lds;
-    const uint32_t band = (blockIdx.x & 7u) * a.fl.chunk + (blockIdx.x >> 3);
+    const uint32_t band = xcd_band(blockIdx.x, a.fl.chunk);
     if (band >= a.fl.bands) return;
     const int lane = threadIdx.x & 63;
     TensorFilterLane t;
     filter_tensor_item(a, lds, band, blockIdx.z, blockIdx.y, [&](auto f) { f(lane, t); });
 }
 
-// what a filter launch must hold before a wave runs: tables, a rectangle that is not empty and lies inside the output, a source
-// picture
-static bool filter_args_ok(const FilterArgs &a)
-{
-    const FrameRect &f = a.f;
-    return a.src && a.dst && a.x.span && a.x.coeff && a.y.span && a.y.coeff && a.x.ksize && a.y.ksize && a.w && a.h && a.dw && a.dh &&
-           f.cw && f.ch && f.keep <= 1 && f.dx <= f.cw && a.dw <= f.cw - f.dx && f.dy <= f.ch && a.dh <= f.ch - f.dy && a.n_pictures <= 65535;
-}
-
 hipError_t launch_rgba_filter(const FilterArgs &args, hipStream_t stream)
 {
-    if (!args.n_pictures) return hipSuccess;
-    if (!filter_args_ok(args)) return hipErrorInvalidValue;
-    FilterArgs a = args;
-    a.bands = (a.f.ch + FILTER_ROWS - 1) / FILTER_ROWS;
-    a.chunk = (a.bands + 7) / 8;
-    const dim3 grid(a.chunk * 8, a.n_pictures, (a.f.cw + 63) / 64);
-    hipLaunchKernelGGL(k_rgba_filter, grid, dim3(64), 0, stream, a);
-    return hipGetLastError();
+    return launch_banded(k_rgba_filter, filter_rgba_plan, args, args.n_pictures, stream);
 }
 
 hipError_t launch_tensor_filter(const TensorFilterArgs &args, hipStream_t stream)
 {
-    if (!args.fl.n_pictures) return hipSuccess;
-    if (!filter_args_ok(args.fl) || args.t.dtype > TENSOR_BF16) return hipErrorInvalidValue;
-    TensorFilterArgs a = args;
-    a.fl.bands = (a.fl.f.ch + FILTER_ROWS - 1) / FILTER_ROWS;
-    a.fl.chunk = (a.fl.bands + 7) / 8;
-    const dim3 grid(a.fl.chunk * 8, a.fl.n_pictures, (a.fl.f.cw + 63) / 64);
-    hipLaunchKernelGGL(k_tensor_filter, grid, dim3(64), 0, stream, a);
-    return hipGetLastError();
+    return launch_banded(k_tensor_filter, filter_tensor_plan, args, args.fl.n_pictures, stream);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -929,7 +886,7 @@ hipError_t launch_tensor_filter(const TensorFilterArgs &args, hipStream_t stream
 __global__ __launch_bounds__(64) void k_plane_resize(PlaneResizeArgs a)
 {
     __shared__ __attribute__((aligned(16))) PlaneLds lds;
-    const uint32_t band = (blockIdx.x & 7u) * a.chunk + (blockIdx.x >> 3);
+    const uint32_t band = xcd_band(blockIdx.x, a.chunk);
     if (band >= a.bands) return;
     const int lane = threadIdx.x & 63;
     PlaneLane t;
@@ -938,15 +895,7 @@ __global__ __launch_bounds__(64) void k_plane_resize(PlaneResizeArgs a)
 
 hipError_t launch_plane_resize(const PlaneResizeArgs &args, hipStream_t stream)
 {
-    if (!args.n_pictures) return hipSuccess;
-    if (args.n_pictures > 65535) return hipErrorInvalidValue;
-    PlaneResizeArgs a = args;
-    a.bands = (a.oh + PLANE_ROWS - 1) / PLANE_ROWS;
-    a.chunk = (a.bands + 7) / 8;
-    a.segs_y = (a.ow + PLANE_OUT - 1) / PLANE_OUT;
-    const dim3 grid(a.chunk * 8, a.n_pictures, a.segs_y + (a.cow + PLANE_OUT - 1) / PLANE_OUT);
-    hipLaunchKernelGGL(k_plane_resize, grid, dim3(64), 0, stream, a);
-    return hipGetLastError();
+    return launch_banded(k_plane_resize, plane_resize_plan, args, args.n_pictures, stream);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -958,7 +907,7 @@ hipError_t launch_plane_resize(const PlaneResizeArgs &args, hipStream_t stream)
 __global__ __launch_bounds__(64) void k_plane_filter(PlaneFilterArgs a)
 {
     __shared__ __attribute__((aligned(16))) PlaneFilterLds lds;
-    const uint32_t band = (blockIdx.x & 7u) * a.chunk + (blockIdx.x >> 3);
+    const uint32_t band = xcd_band(blockIdx.x, a.chunk);
     if (band >= a.bands) return;
     const int lane = threadIdx.x & 63;
     PlaneFilterLane t;
@@ -967,20 +916,7 @@ __global__ __launch_bounds__(64) void k_plane_filter(PlaneFilterArgs a)
 
 hipError_t launch_plane_filter(const PlaneFilterArgs &args, hipStream_t stream)
 {
-    if (!args.n_pictures) return hipSuccess;
-    const FilterAxis *const ax[4] = {&args.xy, &args.yy, &args.xc, &args.yc};
-    for (const FilterAxis *x : ax)
-        if (!x->span || !x->coeff || !x->ksize) return hipErrorInvalidValue;
-    if (!args.src || !args.dst || !args.w || !args.h || !args.ow || !args.oh || args.cw != (args.w + 1) / 2 || args.ch != (args.h + 1) / 2 ||
-        args.cow != (args.ow + 1) / 2 || args.coh != (args.oh + 1) / 2 || args.n_pictures > 65535)
-        return hipErrorInvalidValue;
-    PlaneFilterArgs a = args;
-    a.bands = (a.oh + PFILTER_ROWS - 1) / PFILTER_ROWS;
-    a.chunk = (a.bands + 7) / 8;
-    a.segs_y = (a.ow + PLANE_OUT - 1) / PLANE_OUT;
-    const dim3 grid(a.chunk * 8, a.n_pictures, a.segs_y + (a.cow + PLANE_OUT - 1) / PLANE_OUT);
-    hipLaunchKernelGGL(k_plane_filter, grid, dim3(64), 0, stream, a);
-    return hipGetLastError();
+    return launch_banded(k_plane_filter, plane_filter_plan, args, args.n_pictures, stream);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1199,7 +1135,7 @@ hipError_t launch_probe(int mode, int shape, const void *in, void *out, size_t b
 __global__ __launch_bounds__(64) void k_roi_tensor(RoiArgs a)
 {
     __shared__ __attribute__((aligned(16))) ResizeLds lds;
-    const uint32_t band = (blockIdx.x & 7u) * a.t.r.chunk + (blockIdx.x >> 3);
+    const uint32_t band = xcd_band(blockIdx.x, a.t.r.chunk);
     if (band >= a.t.r.bands) return;
     const int lane = threadIdx.x & 63;
     RoiLane t;
@@ -1208,17 +1144,7 @@ __global__ __launch_bounds__(64) void k_roi_tensor(RoiArgs a)
 
 hipError_t launch_roi_tensor(const RoiArgs &args, hipStream_t stream)
 {
-    if (!args.n_rois) return hipSuccess;
-    const ResizeArgs &r = args.t.r;
-    if (args.n_rois > 65535 || args.t.dtype > TENSOR_BF16 || !r.ow || !r.oh || r.ow > 65535 || r.oh > 65535 || !r.w || !r.h || r.w > 65535 ||
-        r.h > 65535 || (uint64_t)r.w * r.h >= (1ull << 30) || !r.n_pictures || !r.src || !args.rois || !args.dst)
-        return hipErrorInvalidValue;
-    RoiArgs a = args;
-    a.t.r.bands = (r.oh + RESIZE_ROWS - 1) / RESIZE_ROWS;
-    a.t.r.chunk = (a.t.r.bands + 7) / 8;
-    const dim3 grid(a.t.r.chunk * 8, a.n_rois, (r.ow + 63) / 64);
-    hipLaunchKernelGGL(k_roi_tensor, grid, dim3(64), 0, stream, a);
-    return hipGetLastError();
+    return launch_banded(k_roi_tensor, roi_plan, args, args.n_rois, stream);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1228,8 +1154,6 @@ hipError_t launch_roi_tensor(const RoiArgs &args, hipStream_t stream)
 // pictures; the select kernel is one wave.
 // (Behind everything else in the file, as k_roi_tensor was: the kernels above compile to what they were.)
 // ---------------------------------------------------------------------------------------
-constexpr uint64_t CHANGE_GRID_MAX = 1u << 24;
-
 __global__ __launch_bounds__(64) void k_change(ChangeArgs a)
 {
     __shared__ __attribute__((aligned(16))) ChangeLds lds;
@@ -1249,19 +1173,12 @@ __global__ __launch_bounds__(64) void k_change_select(ChangeSelectArgs f)
 hipError_t launch_change(const ChangeArgs &args, const ChangeSelectArgs *sel, hipStream_t stream)
 {
     if (args.n_pictures) {
-        if (args.n_pictures > CHANGE_MAX_PICTURES || args.cell_log2 < 3 || args.cell_log2 > 6 || !args.w || !args.h || args.w > 65535 ||
-            args.h > 65535 || (uint64_t)args.w * args.h >= (1ull << 30) || !args.cur || !args.prev || !args.summary ||
-            args.gw != ((args.w - 1u) >> args.cell_log2) + 1u || args.gh != ((args.h - 1u) >> args.cell_log2) + 1u ||
-            args.segs != (args.w + CHANGE_SEG - 1u) / CHANGE_SEG)
-            return hipErrorInvalidValue;
         ChangeArgs a = args;
-        const uint32_t items = a.gh * a.segs;                              // of a picture (below 2^19: w * h < 2^30)
-        a.items_per_wave = change_items_per_wave((uint64_t)items * a.n_pictures);
-        const uint32_t per_picture = (items + a.items_per_wave - 1u) / a.items_per_wave;
-        const uint32_t per_launch = (uint32_t)(CHANGE_GRID_MAX / per_picture);
-        for (a.p0 = 0; a.p0 < a.n_pictures; a.p0 += per_launch) {
-            const uint32_t n = a.n_pictures - a.p0 < per_launch ? a.n_pictures - a.p0 : per_launch;
-            hipLaunchKernelGGL(k_change, dim3(per_picture, n), dim3(64), 0, stream, a);
+        ChangeLaunch l;
+        if (!change_plan(a, l)) return hipErrorInvalidValue;
+        for (a.p0 = 0; a.p0 < a.n_pictures; a.p0 += l.pictures) {
+            const uint32_t n = a.n_pictures - a.p0 < l.pictures ? a.n_pictures - a.p0 : l.pictures;
+            hipLaunchKernelGGL(k_change, dim3(l.waves, n), dim3(64), 0, stream, a);
             const hipError_t e = hipGetLastError();
             if (e != hipSuccess) return e;
         }

@@ -64,6 +64,20 @@ H263_HD void plane_filter_axes(const void *base, PlaneFilterArgs &a, uint32_t ks
     filter_axes(a.yy.coeff + (size_t)a.oh * ksy_y, a.cow, a.coh, ksx_c, ksy_c, a.xc, a.yc);
 }
 
+// the launch of k_plane_filter (HOST): k_plane_resize's shape; tables, planes and chroma sizes that are the luma's halves
+inline bool plane_filter_plan(PlaneFilterArgs &a, LaunchDims &d)
+{
+    const FilterAxis *const ax[4] = {&a.xy, &a.yy, &a.xc, &a.yc};
+    for (const FilterAxis *x : ax)
+        if (!x->span || !x->coeff || !x->ksize) return false;
+    if (!a.src || !a.dst || !a.w || !a.h || !a.ow || !a.oh || a.cw != (a.w + 1) / 2 || a.ch != (a.h + 1) / 2 ||
+        a.cow != (a.ow + 1) / 2 || a.coh != (a.oh + 1) / 2 || a.n_pictures > 65535)
+        return false;
+    a.segs_y = (a.ow + PLANE_OUT - 1) / PLANE_OUT;
+    d = band_grid(a.oh, PFILTER_ROWS, a.n_pictures, a.segs_y + (a.cow + PLANE_OUT - 1) / PLANE_OUT, a.bands, a.chunk);
+    return true;
+}
+
 struct PlaneFilterLds {
     uint32_t v[2][PFILTER_CHUNK / 4];                    // the staged samples of a chunk, per channel, four to a word
     int32_t kx[PFILTER_LDS_TAPS][PLANE_PX][64];

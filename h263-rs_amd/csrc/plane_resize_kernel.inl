@@ -59,6 +59,15 @@ struct PlaneResizeArgs {
     uint32_t n_pictures;
 };
 
+// the launch of k_plane_resize (HOST): the luma segments, then the chroma segments, in z
+inline bool plane_resize_plan(PlaneResizeArgs &a, LaunchDims &d)
+{
+    if (a.n_pictures > 65535) return false;
+    a.segs_y = (a.ow + PLANE_OUT - 1) / PLANE_OUT;
+    d = band_grid(a.oh, PLANE_ROWS, a.n_pictures, a.segs_y + (a.cow + PLANE_OUT - 1) / PLANE_OUT, a.bands, a.chunk);
+    return true;
+}
+
 // what a wave hands between its lanes: the column sums of one chunk, per channel
 struct PlaneLds {
     uint32_t v[2][PLANE_CHUNK];

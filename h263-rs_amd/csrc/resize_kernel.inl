@@ -19,6 +19,7 @@
 // (ASan / UBSan), with the same ResizeArgs and the same arithmetic.
 #pragma once
 
+#include "band_launch.h"
 #include "dev_common.h"
 
 namespace h263mi {
@@ -45,6 +46,13 @@ struct ResizeArgs {
     float inv_d;                 // 1.0f / d, rounded to nearest
     uint32_t n_pictures;
 };
+
+// the launch of k_rgba_resize (HOST: bands, chunk and the grid; nothing is refused)
+inline bool resize_plan(ResizeArgs &a, LaunchDims &d)
+{
+    d = band_grid(a.oh, RESIZE_ROWS, a.n_pictures, (a.ow + 63) / 64, a.bands, a.chunk);
+    return true;
+}
 
 // HOST ONLY (it divides): the spans of the W' output columns of a w-wide picture (rows: call it with h, H')
 inline void resize_spans(uint32_t w, uint32_t ow, ResizeSpan *out)
@@ -205,6 +213,22 @@ struct FramedResizeArgs {
     ResizeArgs r;                // pitch, dst, bands and chunk are the OUTPUT's (bands = ceil(ch / RESIZE_ROWS))
     FrameRect f;
 };
+
+// what a framed launch must hold before a wave runs: a rectangle that is not empty and lies inside the output
+inline bool frame_rect_ok(const ResizeArgs &r, const FrameRect &f)
+{
+    return r.ow && r.oh && f.cw && f.ch && f.keep <= 1 && f.dx <= f.cw && r.ow <= f.cw - f.dx && f.dy <= f.ch && r.oh <= f.ch - f.dy;
+}
+
+// the launch of a framed resize over the cw x ch output (HOST; r: the ResizeArgs inside the launch's arguments)
+inline bool framed_plan(ResizeArgs &r, const FrameRect &f, LaunchDims &d)
+{
+    if (r.n_pictures > 65535 || !frame_rect_ok(r, f)) return false;
+    d = band_grid(f.ch, RESIZE_ROWS, r.n_pictures, (f.cw + 63) / 64, r.bands, r.chunk);
+    return true;
+}
+
+inline bool framed_resize_plan(FramedResizeArgs &a, LaunchDims &d) { return framed_plan(a.r, a.f, d); }
 
 // the columns of the rectangle that segment [X0, X1] holds: [xa, xb], empty (false) when xa > xb
 H263_HD bool frame_columns(const FrameRect &f, uint32_t dw, uint32_t X0, uint32_t X1, uint32_t &xa, uint32_t &xb)

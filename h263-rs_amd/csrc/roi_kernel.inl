@@ -45,6 +45,17 @@ struct RoiArgs {
     float inv_ow, inv_oh;        // fl(1 / W'), fl(1 / H'): made on the host with a division
 };
 
+// the launch of k_roi_tensor (HOST): k_tensor_resize's shape with the region in the place of the picture
+inline bool roi_plan(RoiArgs &a, LaunchDims &d)
+{
+    ResizeArgs &r = a.t.r;
+    if (a.n_rois > 65535 || a.t.dtype > TENSOR_BF16 || !r.ow || !r.oh || r.ow > 65535 || r.oh > 65535 || !r.w || !r.h || r.w > 65535 ||
+        r.h > 65535 || (uint64_t)r.w * r.h >= (1ull << 30) || !r.n_pictures || !r.src || !a.rois || !a.dst)
+        return false;
+    d = band_grid(r.oh, RESIZE_ROWS, a.n_rois, (r.ow + 63) / 64, r.bands, r.chunk);
+    return true;
+}
+
 // what a lane keeps across the rows of a wave
 struct RoiLane {
     TensorLane t;

@@ -38,6 +38,13 @@ struct TensorArgs {
     uint64_t stride_c, stride_h; // in elements; one picture spans less than 2^32 bytes (h263mi_tensor_extent)
 };
 
+// the launch of k_tensor_resize (HOST): k_rgba_resize's shape
+inline bool tensor_resize_plan(TensorArgs &a, LaunchDims &d)
+{
+    if (a.r.n_pictures > 65535 || a.dtype > TENSOR_BF16) return false;
+    return resize_plan(a.r, d);
+}
+
 // what a lane keeps across the phases of one output row
 struct TensorLane {
     ResizeLane sums;
@@ -211,6 +218,13 @@ struct FramedTensorArgs {
     TensorArgs t;
     FrameRect f;
 };
+
+// the launch of k_tensor_resize_framed (HOST): k_rgba_resize_framed's shape
+inline bool framed_tensor_plan(FramedTensorArgs &a, LaunchDims &d)
+{
+    if (a.t.r.n_pictures > 65535 || a.t.dtype > TENSOR_BF16) return false;
+    return framed_plan(a.t.r, a.f, d);
+}
 
 // tensor_phase_store16 for the columns [wa, wb] of a row: the lane at a dword address stores its element and its right
 // neighbour's as one word where the neighbour is in the range and in the wave

@@ -68,11 +68,11 @@ int main(int argc, char **argv)
     auto each = [&](auto f) {
         for (int l = 0; l < 64; l++) f(l, lanes[l]);
     };
-    // the launch's waves: blockIdx.y = picture, x = the wave's run of items (as launch_change)
-    const uint32_t items = a.gh * a.segs;
-    a.items_per_wave = hd[7] >> 8 ? hd[7] >> 8 : change_items_per_wave((uint64_t)items * n);
+    // the launch's waves: blockIdx.y = picture, x = the wave's run of items (launch_change's plan, the case's items per wave)
+    ChangeLaunch l;
+    if (!change_plan(a, l, hd[7] >> 8)) return 2;
     for (uint32_t p = 0; p < n; p++)
-        for (uint32_t x = 0; x < (items + a.items_per_wave - 1u) / a.items_per_wave; x++) {
+        for (uint32_t x = 0; x < l.waves; x++) {
             memset(&lds, 0xA5, sizeof lds);
             memset(lanes, 0x5A, sizeof lanes);
             change_wave(a, lds, p, x * a.items_per_wave, each);

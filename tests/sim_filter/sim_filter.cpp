@@ -13,18 +13,13 @@
 //        u64 offsets[n_pictures] (BYTES into the canvas; ~0 = the picture is skipped);
 //        n_pictures full-size pictures, w*h*4 bytes each; canvas_bytes of canvas
 //   out: the canvas after the launch
-#include <stdio.h>
 #include <stdlib.h>
-#include <string.h>
-
-#include <vector>
 
 #include "../../h263-rs_amd/csrc/filter_kernel.inl"
 #include "../../h263-rs_amd/csrc/filter_taps.h"
+#include "../sim_common.h"
 
 using namespace h263mi;
-
-static bool read_all(FILE *f, void *p, size_t n) { return fread(p, 1, n, f) == n; }
 
 int main(int argc, char **argv)
 {
@@ -62,8 +57,6 @@ int main(int argc, char **argv)
     r.dh = dh;
     r.pitch = pp[1];
     r.n_pictures = n;
-    r.bands = (ch + FILTER_ROWS - 1) / FILTER_ROWS;      // (as launch_rgba_filter / launch_tensor_filter)
-    r.chunk = (r.bands + 7) / 8;
     r.f.cw = cw, r.f.ch = ch, r.f.dx = dx, r.f.dy = dy;
     r.f.pad = pp[0];
     r.f.keep = hd[7];
@@ -72,30 +65,18 @@ int main(int argc, char **argv)
     for (int c = 0; c < 3; c++) a.t.scale[c] = sb[c], a.t.bias[c] = sb[3 + c];
     a.t.stride_c = q[0];
     a.t.stride_h = q[1];
-    static FilterLds lds;
-    static TensorFilterLane lanes[64];
-    static FilterLane rlanes[64];
-    auto each = [&](auto f) {
-        for (int l = 0; l < 64; l++) f(l, lanes[l]);
-    };
-    auto each_rgba = [&](auto f) {
-        for (int l = 0; l < 64; l++) f(l, rlanes[l]);
-    };
-    // the launch's waves in grid order: blockIdx.x = XCD-ordered band, y = picture, z = column segment
-    for (uint32_t p = 0; p < n; p++)
-        for (uint32_t z = 0; z < (cw + 63) / 64; z++)
-            for (uint32_t x = 0; x < r.chunk * 8; x++) {
-                const uint32_t band = (x & 7u) * r.chunk + (x >> 3);
-                if (band >= r.bands) continue;
-                memset(&lds, 0xA5, sizeof lds);
-                memset(lanes, 0x5A, sizeof lanes);
-                memset(rlanes, 0x5A, sizeof rlanes);
-                if (dtype == 3) filter_rgba_item(r, lds, band, z, p, each_rgba);
-                else filter_tensor_item(a, lds, band, z, p, each);
-            }
-
-    FILE *out = fopen(argv[2], "wb");
-    if (!out || fwrite(canvas.data(), 1, canvas.size(), out) != canvas.size()) return 2;
-    fclose(out);
-    return 0;
+    LaunchDims d;
+    if (!n) return write_canvas(argv[2], canvas);        // (as the launchers: no picture, no launch)
+    if (dtype == 3) {
+        if (!filter_rgba_plan(r, d)) return 2;
+        run_banded<FilterLds, FilterLane>(d, r.bands, r.chunk, [&](FilterLds &lds, uint32_t band, uint32_t z, uint32_t p, auto each) {
+            filter_rgba_item(r, lds, band, z, p, each);
+        });
+    } else {
+        if (!filter_tensor_plan(a, d)) return 2;
+        run_banded<FilterLds, TensorFilterLane>(d, r.bands, r.chunk, [&](FilterLds &lds, uint32_t band, uint32_t z, uint32_t p, auto each) {
+            filter_tensor_item(a, lds, band, z, p, each);
+        });
+    }
+    return write_canvas(argv[2], canvas);
 }

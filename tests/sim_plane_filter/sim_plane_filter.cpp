@@ -11,18 +11,13 @@
 //        u64 offsets[3 * n_pictures] (Y, Cb or CbCr, Cr, from canvas + base -- the d_deblocked of the call; Y = ~0: the picture
 //        is skipped); n_pictures tight I420 pictures, w*h + 2*cw*ch bytes each; canvas_bytes of canvas
 //   out: the canvas after the launch
-#include <stdio.h>
 #include <stdlib.h>
-#include <string.h>
-
-#include <vector>
 
 #include "../../h263-rs_amd/csrc/filter_taps.h"
 #include "../../h263-rs_amd/csrc/plane_filter_kernel.inl"
+#include "../sim_common.h"
 
 using namespace h263mi;
-
-static bool read_all(FILE *f, void *p, size_t n) { return fread(p, 1, n, f) == n; }
 
 int main(int argc, char **argv)
 {
@@ -70,28 +65,12 @@ int main(int argc, char **argv)
     a.d_y = w * h;
     a.d_c = cw * ch;
     a.n_pictures = n;
-    a.bands = (oh + PFILTER_ROWS - 1) / PFILTER_ROWS;    // (as launch_plane_filter)
-    a.chunk = (a.bands + 7) / 8;
-    a.segs_y = (ow + PLANE_OUT - 1) / PLANE_OUT;
-    const uint32_t segs = a.segs_y + (cow + PLANE_OUT - 1) / PLANE_OUT;
-    static PlaneFilterLds lds;
-    static PlaneFilterLane lanes[64];
-    auto each = [&](auto f) {
-        for (int l = 0; l < 64; l++) f(l, lanes[l]);
-    };
-    // the launch's waves in grid order: blockIdx.x = XCD-ordered band, y = picture, z = column segment (luma, then chroma)
-    for (uint32_t p = 0; p < n; p++)
-        for (uint32_t z = 0; z < segs; z++)
-            for (uint32_t x = 0; x < a.chunk * 8; x++) {
-                const uint32_t band = (x & 7u) * a.chunk + (x >> 3);
-                if (band >= a.bands) continue;
-                memset(&lds, 0xA5, sizeof lds);
-                memset(lanes, 0x5A, sizeof lanes);
-                plane_filter_item(a, lds, band, z, p, each);
-            }
-
-    FILE *out = fopen(argv[2], "wb");
-    if (!out || fwrite(canvas.data(), 1, canvas.size(), out) != canvas.size()) return 2;
-    fclose(out);
-    return 0;
+    LaunchDims d;
+    if (n) {                                             // (as launch_plane_filter: no picture, no launch)
+        if (!plane_filter_plan(a, d)) return 2;
+        run_banded<PlaneFilterLds, PlaneFilterLane>(d, a.bands, a.chunk, [&](PlaneFilterLds &lds, uint32_t band, uint32_t z, uint32_t p, auto each) {
+            plane_filter_item(a, lds, band, z, p, each);
+        });
+    }
+    return write_canvas(argv[2], canvas);
 }

@@ -10,17 +10,12 @@
 //   out: the canvas after the launch
 //   sim_resize --div <d>
 //        resize_div(n, d) == n / d for n = q*d - 1, q*d, q*d + d/2, q = 0..255; prints the mismatches, exit status 1 if any
-#include <stdio.h>
 #include <stdlib.h>
-#include <string.h>
-
-#include <vector>
 
 #include "../../h263-rs_amd/csrc/resize_kernel.inl"
+#include "../sim_common.h"
 
 using namespace h263mi;
-
-static bool read_all(FILE *f, void *p, size_t n) { return fread(p, 1, n, f) == n; }
 
 static int check_div(uint32_t d)
 {
@@ -74,26 +69,12 @@ int main(int argc, char **argv)
     a.d = w * h;
     a.inv_d = 1.0f / (float)a.d;
     a.n_pictures = n;
-    a.bands = (oh + RESIZE_ROWS - 1) / RESIZE_ROWS;      // (as launch_rgba_resize)
-    a.chunk = (a.bands + 7) / 8;
-    static ResizeLds lds;
-    static ResizeLane lanes[64];
-    auto each = [&](auto f) {
-        for (int l = 0; l < 64; l++) f(l, lanes[l]);
-    };
-    // the launch's waves in grid order: blockIdx.x = XCD-ordered band, y = picture, z = column segment
-    for (uint32_t p = 0; p < n; p++)
-        for (uint32_t z = 0; z < (ow + 63) / 64; z++)
-            for (uint32_t x = 0; x < a.chunk * 8; x++) {
-                const uint32_t band = (x & 7u) * a.chunk + (x >> 3);
-                if (band >= a.bands) continue;
-                memset(&lds, 0xA5, sizeof lds);
-                memset(lanes, 0x5A, sizeof lanes);
-                resize_item(a, lds, band, z, p, each);
-            }
-
-    FILE *out = fopen(argv[2], "wb");
-    if (!out || fwrite(canvas.data(), 1, canvas.size(), out) != canvas.size()) return 2;
-    fclose(out);
-    return 0;
+    LaunchDims d;
+    if (n) {                                             // (as launch_rgba_resize: no picture, no launch)
+        if (!resize_plan(a, d)) return 2;
+        run_banded<ResizeLds, ResizeLane>(d, a.bands, a.chunk, [&](ResizeLds &lds, uint32_t band, uint32_t z, uint32_t p, auto each) {
+            resize_item(a, lds, band, z, p, each);
+        });
+    }
+    return write_canvas(argv[2], canvas);
 }

@@ -17,17 +17,12 @@
 //        resize_div(n, d, inv) == n / d for n = q*d - 1, q*d, q*d + d/2, q = 0..255, with inv = fl(1/d), its two neighbours (a
 //        reciprocal good to 1 ulp) and roi_inv_d(d); exit status 1 if any differs
 #include <math.h>
-#include <stdio.h>
 #include <stdlib.h>
-#include <string.h>
-
-#include <vector>
 
 #include "../../h263-rs_amd/csrc/roi_kernel.inl"
+#include "../sim_common.h"
 
 using namespace h263mi;
-
-static bool read_all(FILE *f, void *p, size_t n) { return fread(p, 1, n, f) == n; }
 
 static int bad_spans = 0;
 
@@ -105,8 +100,6 @@ int main(int argc, char **argv)
     r.src = src.data();
     r.w = w, r.h = h, r.ow = ow, r.oh = oh;
     r.n_pictures = n;
-    r.bands = (oh + RESIZE_ROWS - 1) / RESIZE_ROWS;          // (as launch_roi_tensor)
-    r.chunk = (r.bands + 7) / 8;
     a.t.dtype = dtype;
     a.t.bgr = hd[6];
     for (int c = 0; c < 3; c++) a.t.scale[c] = sb[c], a.t.bias[c] = sb[3 + c];
@@ -118,25 +111,12 @@ int main(int argc, char **argv)
     a.status = status.data();
     a.n_rois = n_rois;
     a.inv_ow = 1.0f / (float)ow, a.inv_oh = 1.0f / (float)oh;
-    static ResizeLds lds;
-    static RoiLane lanes[64];
-    auto each = [&](auto f) {
-        for (int l = 0; l < 64; l++) f(l, lanes[l]);
-    };
-    // the launch's waves in grid order: blockIdx.x = XCD-ordered band, y = region, z = column segment
-    for (uint32_t k = 0; k < n_rois; k++)
-        for (uint32_t z = 0; z < (ow + 63) / 64; z++)
-            for (uint32_t x = 0; x < r.chunk * 8; x++) {
-                const uint32_t band = (x & 7u) * r.chunk + (x >> 3);
-                if (band >= r.bands) continue;
-                memset(&lds, 0xA5, sizeof lds);
-                memset(lanes, 0x5A, sizeof lanes);
-                roi_tensor_item(a, lds, band, z, k, each);
-            }
-
-    FILE *out = fopen(argv[2], "wb");
-    if (!out || fwrite(canvas.data(), 1, canvas.size(), out) != canvas.size()) return 2;
-    if (n_rois && fwrite(status.data(), 4, n_rois, out) != n_rois) return 2;
-    fclose(out);
-    return 0;
+    LaunchDims d;
+    if (n_rois) {                                            // (as launch_roi_tensor: no region, no launch)
+        if (!roi_plan(a, d)) return 2;
+        run_banded<ResizeLds, RoiLane>(d, r.bands, r.chunk, [&](ResizeLds &lds, uint32_t band, uint32_t z, uint32_t k, auto each) {
+            roi_tensor_item(a, lds, band, z, k, each);
+        });
+    }
+    return write_canvas(argv[2], canvas, status.data(), 4 * (size_t)n_rois);
 }

@@ -12,17 +12,12 @@
 //   sim_tensor --cvt <in> <out>
 //   in : binary32 bit patterns (u32 each);  out: per pattern u16 binary16 bits, u16 bfloat16 bits -- the integer conversions
 //        of the host build
-#include <stdio.h>
 #include <stdlib.h>
-#include <string.h>
-
-#include <vector>
 
 #include "../../h263-rs_amd/csrc/tensor_resize_kernel.inl"
+#include "../sim_common.h"
 
 using namespace h263mi;
-
-static bool read_all(FILE *f, void *p, size_t n) { return fread(p, 1, n, f) == n; }
 
 static int convert(const char *in_path, const char *out_path)
 {
@@ -80,31 +75,17 @@ int main(int argc, char **argv)
     a.r.d = w * h;
     a.r.inv_d = 1.0f / (float)a.r.d;
     a.r.n_pictures = n;
-    a.r.bands = (oh + RESIZE_ROWS - 1) / RESIZE_ROWS;    // (as launch_tensor_resize)
-    a.r.chunk = (a.r.bands + 7) / 8;
     a.dtype = hd[5];
     a.bgr = hd[6];
     for (int c = 0; c < 3; c++) a.scale[c] = sb[c], a.bias[c] = sb[3 + c];
     a.stride_c = q[0];
     a.stride_h = q[1];
-    static ResizeLds lds;
-    static TensorLane lanes[64];
-    auto each = [&](auto f) {
-        for (int l = 0; l < 64; l++) f(l, lanes[l]);
-    };
-    // the launch's waves in grid order: blockIdx.x = XCD-ordered band, y = picture, z = column segment
-    for (uint32_t p = 0; p < n; p++)
-        for (uint32_t z = 0; z < (ow + 63) / 64; z++)
-            for (uint32_t x = 0; x < a.r.chunk * 8; x++) {
-                const uint32_t band = (x & 7u) * a.r.chunk + (x >> 3);
-                if (band >= a.r.bands) continue;
-                memset(&lds, 0xA5, sizeof lds);
-                memset(lanes, 0x5A, sizeof lanes);
-                tensor_resize_item(a, lds, band, z, p, each);
-            }
-
-    FILE *out = fopen(argv[2], "wb");
-    if (!out || fwrite(canvas.data(), 1, canvas.size(), out) != canvas.size()) return 2;
-    fclose(out);
-    return 0;
+    LaunchDims d;
+    if (n) {                                             // (as launch_tensor_resize: no picture, no launch)
+        if (!tensor_resize_plan(a, d)) return 2;
+        run_banded<ResizeLds, TensorLane>(d, a.r.bands, a.r.chunk, [&](ResizeLds &lds, uint32_t band, uint32_t z, uint32_t p, auto each) {
+            tensor_resize_item(a, lds, band, z, p, each);
+        });
+    }
+    return write_canvas(argv[2], canvas);
 }

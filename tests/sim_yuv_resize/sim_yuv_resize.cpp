@@ -11,17 +11,12 @@
 //   sim_yuv_resize --div <d>
 //        resize_div(n, d) == n / d for n = q*d - 1, q*d, q*d + d/2, q = 0..255 (q = 255 with + d/2 is a constant plane of 255,
 //        q = 0 one of 0, at pw*ph = d); prints the mismatches, exit status 1 if any
-#include <stdio.h>
 #include <stdlib.h>
-#include <string.h>
-
-#include <vector>
 
 #include "../../h263-rs_amd/csrc/plane_resize_kernel.inl"
+#include "../sim_common.h"
 
 using namespace h263mi;
-
-static bool read_all(FILE *f, void *p, size_t n) { return fread(p, 1, n, f) == n; }
 
 static int check_div(uint32_t d)
 {
@@ -90,28 +85,12 @@ int main(int argc, char **argv)
     a.inv_d_y = 1.0f / (float)a.d_y;
     a.inv_d_c = 1.0f / (float)a.d_c;
     a.n_pictures = n;
-    a.bands = (oh + PLANE_ROWS - 1) / PLANE_ROWS;        // (as launch_plane_resize)
-    a.chunk = (a.bands + 7) / 8;
-    a.segs_y = (ow + PLANE_OUT - 1) / PLANE_OUT;
-    const uint32_t segs = a.segs_y + (cow + PLANE_OUT - 1) / PLANE_OUT;
-    static PlaneLds lds;
-    static PlaneLane lanes[64];
-    auto each = [&](auto f) {
-        for (int l = 0; l < 64; l++) f(l, lanes[l]);
-    };
-    // the launch's waves in grid order: blockIdx.x = XCD-ordered band, y = picture, z = column segment (luma, then chroma)
-    for (uint32_t p = 0; p < n; p++)
-        for (uint32_t z = 0; z < segs; z++)
-            for (uint32_t x = 0; x < a.chunk * 8; x++) {
-                const uint32_t band = (x & 7u) * a.chunk + (x >> 3);
-                if (band >= a.bands) continue;
-                memset(&lds, 0xA5, sizeof lds);
-                memset(lanes, 0x5A, sizeof lanes);
-                plane_resize_item(a, lds, band, z, p, each);
-            }
-
-    FILE *out = fopen(argv[2], "wb");
-    if (!out || fwrite(canvas.data(), 1, canvas.size(), out) != canvas.size()) return 2;
-    fclose(out);
-    return 0;
+    LaunchDims d;
+    if (n) {                                             // (as launch_plane_resize: no picture, no launch)
+        if (!plane_resize_plan(a, d)) return 2;
+        run_banded<PlaneLds, PlaneLane>(d, a.bands, a.chunk, [&](PlaneLds &lds, uint32_t band, uint32_t z, uint32_t p, auto each) {
+            plane_resize_item(a, lds, band, z, p, each);
+        });
+    }
+    return write_canvas(argv[2], canvas);
 }
