@@ -1,0 +1,88 @@
+// analysis_kernels.hip -- digests and change maps of pictures in device memory: __global__ wrappers and launchers.
+// Built with the flags of decode_kernels.hip.
+#include "kernels.h"
+
+#include "change_kernel.inl"
+#include "digest_kernel.inl"
+
+namespace h263mi {
+
+// ---------------------------------------------------------------------------------------
+// k_digest, k_digest_final: Adler-32 of pitched rows in device memory (digest_kernel.inl).  One wave per workgroup, no barrier;
+// a wave takes the work items blockIdx.x, blockIdx.x + gridDim.x, ... -- one each unless a call has more items than
+// DIGEST_GRID_MAX -- and adds their terms to the digests' accumulators; the second launch reduces and packs them.
+// ---------------------------------------------------------------------------------------
+constexpr uint64_t DIGEST_GRID_MAX = 1u << 20;
+
+__global__ __launch_bounds__(64) void k_digest(DigestArgs a)
+{
+    __shared__ __attribute__((aligned(16))) DigestLds lds;
+    const int lane = threadIdx.x & 63;
+    DigestLane t;
+    for (uint64_t item = blockIdx.x; item < a.n_items; item += gridDim.x)
+        digest_item(a, lds, item, [&](auto f) { f(lane, t); });
+}
+
+__global__ __launch_bounds__(256) void k_digest_final(DigestFinalArgs f)
+{
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k < f.n_digests) digest_final(f, k);
+}
+
+hipError_t launch_digest(const DigestArgs &args, const DigestFinalArgs &fin, hipStream_t stream)
+{
+    if (!fin.n_digests) return hipSuccess;
+    if (args.n_items) {
+        const uint32_t grid = (uint32_t)(args.n_items < DIGEST_GRID_MAX ? args.n_items : DIGEST_GRID_MAX);
+        hipLaunchKernelGGL(k_digest, dim3(grid), dim3(64), 0, stream, args);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_digest_final, dim3((fin.n_digests + 255u) / 256u), dim3(256), 0, stream, fin);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
+// k_change, k_change_select: change maps of 8-bit planes (h263mi_change_map_on, h263mi_batch_change_last; change_kernel.inl).
+// One wave per workgroup, no barrier: blockIdx.x = the wave's run of items_per_wave work items (segments of CHANGE_SEG columns of
+// a cell row, row after row), blockIdx.y = picture (from args.p0).  A launch holds at most CHANGE_GRID_MAX workgroups, whole
+// pictures; the select kernel is one wave.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_change(ChangeArgs a)
+{
+    __shared__ __attribute__((aligned(16))) ChangeLds lds;
+    const int lane = threadIdx.x & 63;
+    ChangeLane t;
+    change_wave(a, lds, a.p0 + blockIdx.y, blockIdx.x * a.items_per_wave, [&](auto f) { f(lane, t); });
+}
+
+__global__ __launch_bounds__(64) void k_change_select(ChangeSelectArgs f)
+{
+    __shared__ __attribute__((aligned(16))) ChangeLds lds;
+    const int lane = threadIdx.x & 63;
+    ChangeLane t;
+    change_select(f, lds, [&](auto g) { g(lane, t); });
+}
+
+hipError_t launch_change(const ChangeArgs &args, const ChangeSelectArgs *sel, hipStream_t stream)
+{
+    if (args.n_pictures) {
+        ChangeArgs a = args;
+        ChangeLaunch l;
+        if (!change_plan(a, l)) return hipErrorInvalidValue;
+        for (a.p0 = 0; a.p0 < a.n_pictures; a.p0 += l.pictures) {
+            const uint32_t n = a.n_pictures - a.p0 < l.pictures ? a.n_pictures - a.p0 : l.pictures;
+            hipLaunchKernelGGL(k_change, dim3(l.waves, n), dim3(64), 0, stream, a);
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return e;
+        }
+    }
+    if (sel) {
+        if (!sel->selected || !sel->count || (sel->n_pictures && !sel->summary)) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_change_select, dim3(1), dim3(64), 0, stream, *sel);
+        return hipGetLastError();
+    }
+    return hipSuccess;
+}
+
+}  // namespace h263mi

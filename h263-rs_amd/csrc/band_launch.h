@@ -1,6 +1,6 @@
 // band_launch.h -- the launch shape that the banded output kernels share (the resizes, the filters, the plane kernels, the ROI
 // tensors): one wave per workgroup, blockIdx.x = band of output rows in XCD order, blockIdx.y = picture or region, blockIdx.z =
-// column segment.  Plain C++: the kernels, their launchers (kernels.hip) and the CPU checkers (tests/sim_*) all read it from here.
+// column segment.  Plain C++: the kernels, their launchers (output_kernels.hip) and the CPU checkers (tests/sim_*) all read it from here.
 #pragma once
 
 #include <stdint.h>

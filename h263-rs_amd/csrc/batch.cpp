@@ -1,7 +1,7 @@
 // batch.cpp -- h263mi_batch: the device-resident frame store of N streams, the reference bookkeeping of
 // state.rs:464-483 per stream, submit / render / sync, launch timing, and the entry points that take DEVICE records
 // (h263mi_batch_submit / _decode / _decode_events / _render_rgba / _sync ...).  Compiled with hipcc; every compute path
-// launches the gfx950 kernels of kernels.hip -- there is no CPU fallback.
+// launches the gfx950 kernels of the *_kernels.hip units -- there is no CPU fallback.
 #include "batch.h"
 
 #include <algorithm>

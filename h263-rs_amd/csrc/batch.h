@@ -46,7 +46,7 @@ struct h263mi_batch {
     hipEvent_t ev_recon_done = nullptr, ev_post_done[2] = {nullptr, nullptr};   // post events per frame set
     bool overlap_post = false;
     // H263MI_CFG_PIPELINE_POST: h263mi_batch_decode defers the post-processing of a picture to the launch that
-    // reconstructs the NEXT one (k_frame: both read the same frame set, see kernels.hip); `pending` is that deferred
+    // reconstructs the NEXT one (k_frame: both read the same frame set, see decode_kernels.hip); `pending` is that deferred
     // half.  Flushed (as a plain k_post launch) by sync, render, submit, reset.
     bool pipeline_post = false;
     // H263MI_CFG_TRUSTED_ARRAYS: the caller vouches for the device arrays it hands to h263mi_batch_submit / _decode /

@@ -1,18 +1,10 @@
-// kernels.hip -- __global__ wrappers and launchers of the gfx950 kernels.
-// Built with: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (no fast-math).
+// decode_kernels.hip -- the decoding hot path: __global__ wrappers and launchers of k_recon, k_post* and k_frame*.
+// Built with: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (no fast-math).  The only kernel unit that the arithmetic
+// mutants of the tests (mutants.h) rebuild.
 #include "kernels.h"
 
-#include "change_kernel.inl"
-#include "digest_kernel.inl"
 #include "post_kernel.inl"
 #include "recon_kernel.inl"
-#include "filter_kernel.inl"
-#include "plane_filter_kernel.inl"
-#include "plane_resize_kernel.inl"
-#include "resize_kernel.inl"
-#include "roi_kernel.inl"
-#include "tensor_resize_kernel.inl"
-#include "synth.inl"
 
 namespace h263mi {
 
@@ -604,6 +596,36 @@ __global__ __launch_bounds__(POST_THREADS) void k_post_yuv(StreamWords, PostArgs
     post_kernel<-1, FMT>(a, strips, yo);
 }
 
+static hipError_t launch_post_any(const PostArgs &args, hipStream_t stream, const uint32_t *words, const YuvOut *yuv)
+{
+    if (!args.n_pictures) return hipSuccess;
+    if (args.n_pictures > 65535 || args.tiles_x * args.tiles_y >= (1u << 20)) return hipErrorInvalidValue;
+    if (words && args.n_pictures > STREAM_WORDS_INLINE) return hipErrorInvalidValue;
+    PostArgs a = args;
+    StreamWords sw{};
+    a.words_inline = inline_words(words, args.n_pictures, sw) ? 1u : 0u;
+    a.inv_tiles_x = reciprocal_u32(args.tiles_x);
+    const uint32_t groups_y = (args.tiles_y + POST_GROUP - 1) / POST_GROUP;
+    const uint32_t upp = args.tiles_x * groups_y * (POST_GROUP / POST_WAVES), chunk = (upp + 7) / 8;
+    const dim3 grid(chunk * 8, args.n_pictures);
+    if (yuv && yuv->format == YUV_OUT_I420) hipLaunchKernelGGL(k_post_yuv<(int)YUV_OUT_I420>, grid, dim3(POST_THREADS), 0, stream, sw, a, *yuv);
+    else if (yuv && yuv->format == YUV_OUT_NV12) hipLaunchKernelGGL(k_post_yuv<(int)YUV_OUT_NV12>, grid, dim3(POST_THREADS), 0, stream, sw, a, *yuv);
+    else if (yuv) return hipErrorInvalidValue;
+    else if (!a.rgba_pitch) hipLaunchKernelGGL(k_post, grid, dim3(POST_THREADS), 0, stream, sw, a);
+    else if (a.rgba_scale == 0) hipLaunchKernelGGL(k_post_layout<0>, grid, dim3(POST_THREADS), 0, stream, sw, a);
+    else if (a.rgba_scale == 1) hipLaunchKernelGGL(k_post_layout<1>, grid, dim3(POST_THREADS), 0, stream, sw, a);
+    else if (a.rgba_scale == 2) hipLaunchKernelGGL(k_post_layout<2>, grid, dim3(POST_THREADS), 0, stream, sw, a);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+hipError_t launch_post(const PostArgs &args, hipStream_t stream, const uint32_t *words) { return launch_post_any(args, stream, words, nullptr); }
+
+hipError_t launch_post_yuv(const PostArgs &args, const YuvOut &yuv, hipStream_t stream, const uint32_t *words)
+{
+    return launch_post_any(args, stream, words, &yuv);
+}
+
 // ---------------------------------------------------------------------------------------
 // k_frame: reconstruction of picture f and post-processing of picture f - 1 of every stream in ONE launch
 // (the frame-pipelined form of h263mi_batch_decode).  Both halves read the same frame set -- k_recon as its
@@ -749,446 +771,6 @@ hipError_t launch_frame_yuv(const ReconArgs &rargs, const PostArgs &pargs, const
                             const uint32_t *words)
 {
     return launch_frame_any(rargs, pargs, stream, descending, words, &yuv);
-}
-
-// ---------------------------------------------------------------------------------------
-// k_rgba_resize: area-average resampling of full-size RGBA (resize_kernel.inl).  One wave per workgroup, no barrier;
-// blockIdx.y = picture, blockIdx.z = segment of 64 output columns, blockIdx.x = band of RESIZE_ROWS output rows in XCD
-// order: XCD k (blockIdx.x & 7, gridDim.x a multiple of 8) takes a contiguous run of bands, so the source rows that two
-// neighbouring bands share are fetched into one L2.
-// ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_rgba_resize(ResizeArgs a)
-{
-    __shared__ __attribute__((aligned(16))) ResizeLds lds;
-    const uint32_t band = xcd_band(blockIdx.x, a.chunk);
-    if (band >= a.bands) return;
-    const int lane = threadIdx.x & 63;
-    ResizeLane t;
-    resize_item(a, lds, band, blockIdx.z, blockIdx.y, [&](auto f) { f(lane, t); });
-}
-
-// A banded launch (band_launch.h) of `count` pictures or regions: none is no launch; the kernel's plan (beside its Args) refuses
-// the arguments or fills bands, chunk (segs_y) and the grid; one wave per workgroup.
-template <class Args>
-static hipError_t launch_banded(void (*kernel)(Args), bool (*plan)(Args &, LaunchDims &), const Args &args, uint32_t count, hipStream_t stream)
-{
-    if (!count) return hipSuccess;
-    Args a = args;
-    LaunchDims d;
-    if (!plan(a, d)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(kernel, dim3(d.x, d.y, d.z), dim3(64), 0, stream, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_rgba_resize(const ResizeArgs &args, hipStream_t stream)
-{
-    return launch_banded(k_rgba_resize, resize_plan, args, args.n_pictures, stream);
-}
-
-// ---------------------------------------------------------------------------------------
-// k_tensor_resize: the area average of k_rgba_resize, normalised and stored as three planes of binary32, binary16 or bfloat16
-// (tensor_resize_kernel.inl).  The launch shape is k_rgba_resize's: one wave per workgroup, no barrier, blockIdx.y = picture,
-// blockIdx.z = segment of 64 output columns, blockIdx.x = band of RESIZE_ROWS output rows in XCD order.
-// ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_tensor_resize(TensorArgs a)
-{
-    __shared__ __attribute__((aligned(16))) ResizeLds lds;
-    const uint32_t band = xcd_band(blockIdx.x, a.r.chunk);
-    if (band >= a.r.bands) return;
-    const int lane = threadIdx.x & 63;
-    TensorLane t;
-    tensor_resize_item(a, lds, band, blockIdx.z, blockIdx.y, [&](auto f) { f(lane, t); });
-}
-
-hipError_t launch_tensor_resize(const TensorArgs &args, hipStream_t stream)
-{
-    return launch_banded(k_tensor_resize, tensor_resize_plan, args, args.r.n_pictures, stream);
-}
-
-// ---------------------------------------------------------------------------------------
-// k_rgba_resize_framed, k_tensor_resize_framed: a source window into a destination rectangle of the W' x H' output, the rest
-// padded or kept (h263mi_framing; resize_kernel.inl, tensor_resize_kernel.inl).  Instantiations of their own: k_rgba_resize and
-// k_tensor_resize above are not touched.  The launch shape is theirs over the W' x H' output: one wave per workgroup, no
-// barrier, blockIdx.y = picture, blockIdx.z = segment of 64 output columns, blockIdx.x = band in XCD order.
-// ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_rgba_resize_framed(FramedResizeArgs a)
-{
-    __shared__ __attribute__((aligned(16))) ResizeLds lds;
-    const uint32_t band = xcd_band(blockIdx.x, a.r.chunk);
-    if (band >= a.r.bands) return;
-    const int lane = threadIdx.x & 63;
-    ResizeLane t;
-    framed_resize_item(a, lds, band, blockIdx.z, blockIdx.y, [&](auto f) { f(lane, t); });
-}
-
-__global__ __launch_bounds__(64) void k_tensor_resize_framed(FramedTensorArgs a)
-{
-    __shared__ __attribute__((aligned(16))) ResizeLds lds;
-    const uint32_t band = xcd_band(blockIdx.x, a.t.r.chunk);
-    if (band >= a.t.r.bands) return;
-    const int lane = threadIdx.x & 63;
-    TensorLane t;
-    framed_tensor_item(a, lds, band, blockIdx.z, blockIdx.y, [&](auto f) { f(lane, t); });
-}
-
-hipError_t launch_rgba_resize_framed(const FramedResizeArgs &args, hipStream_t stream)
-{
-    return launch_banded(k_rgba_resize_framed, framed_resize_plan, args, args.r.n_pictures, stream);
-}
-
-hipError_t launch_tensor_resize_framed(const FramedTensorArgs &args, hipStream_t stream)
-{
-    return launch_banded(k_tensor_resize_framed, framed_tensor_plan, args, args.t.r.n_pictures, stream);
-}
-
-// ---------------------------------------------------------------------------------------
-// k_rgba_filter, k_tensor_filter: Pillow's bilinear / bicubic resampling of a source window into a destination rectangle of the
-// W' x H' output, both passes in one kernel (h263mi_filter; filter_kernel.inl).  One instantiation each serves the framed and
-// the unframed shapes.  The launch shape is that of the framed resizes over the W' x H' output: one wave per workgroup, no
-// barrier, blockIdx.y = picture, blockIdx.z = segment of 64 output columns, blockIdx.x = band of FILTER_ROWS rows in XCD order.
-// ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_rgba_filter(FilterArgs a)
-{
-    __shared__ __attribute__((aligned(16))) FilterLds lds;
-    const uint32_t band = xcd_band(blockIdx.x, a.chunk);
-    if (band >= a.bands) return;
-    const int lane = threadIdx.x & 63;
-    FilterLane t;
-    filter_rgba_item(a, lds, band, blockIdx.z, blockIdx.y, [&](auto f) { f(lane, t); });
-}
-
-__global__ __launch_bounds__(64) void k_tensor_filter(TensorFilterArgs a)
-{
-    __shared__ __attribute__((aligned(16))) FilterLds lds;
-    const uint32_t band = xcd_band(blockIdx.x, a.fl.chunk);
-    if (band >= a.fl.bands) return;
-    const int lane = threadIdx.x & 63;
-    TensorFilterLane t;
-    filter_tensor_item(a, lds, band, blockIdx.z, blockIdx.y, [&](auto f) { f(lane, t); });
-}
-
-hipError_t launch_rgba_filter(const FilterArgs &args, hipStream_t stream)
-{
-    return launch_banded(k_rgba_filter, filter_rgba_plan, args, args.n_pictures, stream);
-}
-
-hipError_t launch_tensor_filter(const TensorFilterArgs &args, hipStream_t stream)
-{
-    return launch_banded(k_tensor_filter, filter_tensor_plan, args, args.fl.n_pictures, stream);
-}
-
-// ---------------------------------------------------------------------------------------
-// k_plane_resize: area-average resampling of the full-size deblocked planes into I420 or NV12 (plane_resize_kernel.inl).  One
-// wave per workgroup, no barrier; blockIdx.y = picture, blockIdx.z = segment of PLANE_OUT output columns (the luma segments,
-// then the chroma segments: one launch for all planes), blockIdx.x = band of PLANE_ROWS output rows in XCD order, as
-// k_rgba_resize.  A chroma wave whose band lies below its planes (they have half the rows) leaves at once.
-// ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_plane_resize(PlaneResizeArgs a)
-{
-    __shared__ __attribute__((aligned(16))) PlaneLds lds;
-    const uint32_t band = xcd_band(blockIdx.x, a.chunk);
-    if (band >= a.bands) return;
-    const int lane = threadIdx.x & 63;
-    PlaneLane t;
-    plane_resize_item(a, lds, band, blockIdx.z, blockIdx.y, [&](auto f) { f(lane, t); });
-}
-
-hipError_t launch_plane_resize(const PlaneResizeArgs &args, hipStream_t stream)
-{
-    return launch_banded(k_plane_resize, plane_resize_plan, args, args.n_pictures, stream);
-}
-
-// ---------------------------------------------------------------------------------------
-// k_plane_filter: Pillow's bilinear / bicubic resampling of the full-size deblocked planes into I420 or NV12, both passes in one
-// kernel (plane_filter_kernel.inl).  The launch shape is k_plane_resize's: one wave per workgroup, no barrier; blockIdx.y =
-// picture, blockIdx.z = segment of PLANE_OUT output columns (luma, then chroma), blockIdx.x = band of PFILTER_ROWS output rows in
-// XCD order.
-// ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_plane_filter(PlaneFilterArgs a)
-{
-    __shared__ __attribute__((aligned(16))) PlaneFilterLds lds;
-    const uint32_t band = xcd_band(blockIdx.x, a.chunk);
-    if (band >= a.bands) return;
-    const int lane = threadIdx.x & 63;
-    PlaneFilterLane t;
-    plane_filter_item(a, lds, band, blockIdx.z, blockIdx.y, [&](auto f) { f(lane, t); });
-}
-
-hipError_t launch_plane_filter(const PlaneFilterArgs &args, hipStream_t stream)
-{
-    return launch_banded(k_plane_filter, plane_filter_plan, args, args.n_pictures, stream);
-}
-
-// ---------------------------------------------------------------------------------------
-// k_digest, k_digest_final: Adler-32 of pitched rows in device memory (digest_kernel.inl).  One wave per workgroup, no barrier;
-// a wave takes the work items blockIdx.x, blockIdx.x + gridDim.x, ... -- one each unless a call has more items than
-// DIGEST_GRID_MAX -- and adds their terms to the digests' accumulators; the second launch reduces and packs them.
-// ---------------------------------------------------------------------------------------
-constexpr uint64_t DIGEST_GRID_MAX = 1u << 20;
-
-__global__ __launch_bounds__(64) void k_digest(DigestArgs a)
-{
-    __shared__ __attribute__((aligned(16))) DigestLds lds;
-    const int lane = threadIdx.x & 63;
-    DigestLane t;
-    for (uint64_t item = blockIdx.x; item < a.n_items; item += gridDim.x)
-        digest_item(a, lds, item, [&](auto f) { f(lane, t); });
-}
-
-__global__ __launch_bounds__(256) void k_digest_final(DigestFinalArgs f)
-{
-    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
-    if (k < f.n_digests) digest_final(f, k);
-}
-
-hipError_t launch_digest(const DigestArgs &args, const DigestFinalArgs &fin, hipStream_t stream)
-{
-    if (!fin.n_digests) return hipSuccess;
-    if (args.n_items) {
-        const uint32_t grid = (uint32_t)(args.n_items < DIGEST_GRID_MAX ? args.n_items : DIGEST_GRID_MAX);
-        hipLaunchKernelGGL(k_digest, dim3(grid), dim3(64), 0, stream, args);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(k_digest_final, dim3((fin.n_digests + 255u) / 256u), dim3(256), 0, stream, fin);
-    return hipGetLastError();
-}
-
-static hipError_t launch_post_any(const PostArgs &args, hipStream_t stream, const uint32_t *words, const YuvOut *yuv)
-{
-    if (!args.n_pictures) return hipSuccess;
-    if (args.n_pictures > 65535 || args.tiles_x * args.tiles_y >= (1u << 20)) return hipErrorInvalidValue;
-    if (words && args.n_pictures > STREAM_WORDS_INLINE) return hipErrorInvalidValue;
-    PostArgs a = args;
-    StreamWords sw{};
-    a.words_inline = inline_words(words, args.n_pictures, sw) ? 1u : 0u;
-    a.inv_tiles_x = reciprocal_u32(args.tiles_x);
-    const uint32_t groups_y = (args.tiles_y + POST_GROUP - 1) / POST_GROUP;
-    const uint32_t upp = args.tiles_x * groups_y * (POST_GROUP / POST_WAVES), chunk = (upp + 7) / 8;
-    const dim3 grid(chunk * 8, args.n_pictures);
-    if (yuv && yuv->format == YUV_OUT_I420) hipLaunchKernelGGL(k_post_yuv<(int)YUV_OUT_I420>, grid, dim3(POST_THREADS), 0, stream, sw, a, *yuv);
-    else if (yuv && yuv->format == YUV_OUT_NV12) hipLaunchKernelGGL(k_post_yuv<(int)YUV_OUT_NV12>, grid, dim3(POST_THREADS), 0, stream, sw, a, *yuv);
-    else if (yuv) return hipErrorInvalidValue;
-    else if (!a.rgba_pitch) hipLaunchKernelGGL(k_post, grid, dim3(POST_THREADS), 0, stream, sw, a);
-    else if (a.rgba_scale == 0) hipLaunchKernelGGL(k_post_layout<0>, grid, dim3(POST_THREADS), 0, stream, sw, a);
-    else if (a.rgba_scale == 1) hipLaunchKernelGGL(k_post_layout<1>, grid, dim3(POST_THREADS), 0, stream, sw, a);
-    else if (a.rgba_scale == 2) hipLaunchKernelGGL(k_post_layout<2>, grid, dim3(POST_THREADS), 0, stream, sw, a);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
-}
-
-hipError_t launch_post(const PostArgs &args, hipStream_t stream, const uint32_t *words) { return launch_post_any(args, stream, words, nullptr); }
-
-hipError_t launch_post_yuv(const PostArgs &args, const YuvOut &yuv, hipStream_t stream, const uint32_t *words)
-{
-    return launch_post_any(args, stream, words, &yuv);
-}
-
-// ---------------------------------------------------------------------------------------
-// synthetic record generators (bench / test support)
-// ---------------------------------------------------------------------------------------
-__global__ void k_synth_headers(SynthArgs a)
-{
-    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= a.n_streams * a.mbs_per_picture) return;
-    const uint32_t p = g / a.mbs_per_picture, mb = g % a.mbs_per_picture;
-    MbRecord r = synth_mb_header(a.kind, a.first_stream_id + p * a.stream_stride, a.frame_idx, mb);
-    a.mbs[g] = r;
-    a.counts[g] = (uint32_t)__popc(r.cbp);
-}
-
-// exclusive scan of the per-macroblock coded-block counts of one picture -> coeff_index
-__global__ __launch_bounds__(1024) void k_synth_scan(SynthArgs a)
-{
-    __shared__ uint32_t sums[1024];
-    const uint32_t p = blockIdx.x, tid = threadIdx.x;
-    const uint32_t n = a.mbs_per_picture, chunk = (n + 1023) / 1024;
-    const uint32_t lo = tid * chunk, hi = lo + chunk < n ? lo + chunk : n;
-    uint32_t local = 0;
-    for (uint32_t i = lo; i < hi; i++) local += a.counts[p * n + i];
-    sums[tid] = local;
-    __syncthreads();
-    for (uint32_t off = 1; off < 1024; off <<= 1) {
-        uint32_t v = tid >= off ? sums[tid - off] : 0;
-        __syncthreads();
-        sums[tid] += v;
-        __syncthreads();
-    }
-    uint32_t run = sums[tid] - local;     // exclusive prefix of this thread's chunk
-    for (uint32_t i = lo; i < hi; i++) {
-        a.mbs[p * n + i].coeff_index = run;
-        run += a.counts[p * n + i];
-    }
-    if (tid == 1023) a.totals[p] = sums[1023];
-}
-
-__global__ void k_synth_coeffs(SynthArgs a)
-{
-    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= a.n_streams * a.mbs_per_picture * 6) return;
-    const uint32_t blk = g % 6, gm = g / 6, p = gm / a.mbs_per_picture, mb = gm % a.mbs_per_picture;
-    const MbRecord r = a.mbs[gm];
-    if (!((r.cbp >> blk) & 1)) return;
-    int16_t c[64];
-    synth_block_coeffs(a.kind, a.first_stream_id + p * a.stream_stride, a.frame_idx, mb, (int)blk, c);
-    const uint64_t idx = a.coeff_base[p] + r.coeff_index + (uint64_t)__popc(r.cbp & ((1u << blk) - 1u));
-    uint4 *dst = reinterpret_cast<uint4 *>(a.coeffs + idx * 64);
-#pragma unroll
-    for (int q = 0; q < 8; q++) {
-        uint32_t w[4];
-        for (int k = 0; k < 4; k++) w[k] = (uint16_t)c[q * 8 + 2 * k] | ((uint32_t)(uint16_t)c[q * 8 + 2 * k + 1] << 16);
-        dst[q] = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-}
-
-hipError_t launch_synth_headers(const SynthArgs &a, hipStream_t stream)
-{
-    const uint32_t n = a.n_streams * a.mbs_per_picture;
-    hipLaunchKernelGGL(k_synth_headers, dim3((n + 255) / 256), dim3(256), 0, stream, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_synth_scan, dim3(a.n_streams), dim3(1024), 0, stream, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_synth_coeffs(const SynthArgs &a, hipStream_t stream)
-{
-    const uint32_t n = a.n_streams * a.mbs_per_picture * 6;
-    hipLaunchKernelGGL(k_synth_coeffs, dim3((n + 255) / 256), dim3(256), 0, stream, a);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------
-// on-box memory ceilings (bench support: roofline.peak_measured).  Streaming kernels with 16-byte accesses: the rate the
-// HBM system of THIS box sustains for a copy, a pure read and a pure write.  Round 2's plain grid-stride probes
-// (2 048 workgroups, one access per iteration) reported 4.8 TB/s for a copy where the MI355X guide measures 6.29:
-// tools/probes/ceiling.hip swept the launch shape (profiles/r03_a_ceiling_probe.txt) -- what reaches 6.2 TB/s is
-// non-temporal accesses, four of them in flight per lane (copy); a read wants non-temporal loads, a write is fastest
-// with few (256) workgroups of plain stores.  `shape` selects among the winners; the C entry point reports the best.
-// ---------------------------------------------------------------------------------------
-typedef uint32_t probe_u32x4 __attribute__((ext_vector_type(4)));
-template <int MODE, int U, bool NT>
-__global__ __launch_bounds__(1024) void k_probe(const probe_u32x4 *__restrict__ in, probe_u32x4 *__restrict__ out, size_t n)
-{
-    // a workgroup walks the buffer in steps of gridDim * blockDim * U elements; its U accesses of a step are blockDim apart
-    const size_t step = (size_t)gridDim.x * blockDim.x * U;
-    probe_u32x4 acc = {0, 0, 0, 0};
-    for (size_t base = (size_t)blockIdx.x * blockDim.x * U + threadIdx.x; base < n; base += step) {
-        probe_u32x4 v[U];
-        if (MODE != 2) {
-#pragma unroll
-            for (int u = 0; u < U; u++) {
-                const size_t i = base + (size_t)u * blockDim.x;
-                v[u] = i < n ? (NT ? __builtin_nontemporal_load(in + i) : in[i]) : acc;
-            }
-        }
-        if (MODE == 1) {
-#pragma unroll
-            for (int u = 0; u < U; u++) acc ^= v[u];
-        } else {
-#pragma unroll
-            for (int u = 0; u < U; u++) {
-                const size_t i = base + (size_t)u * blockDim.x;
-                if (MODE == 2) v[u] = probe_u32x4{(uint32_t)i, 1, 2, 3};
-                if (i < n) {
-                    if (NT) __builtin_nontemporal_store(v[u], out + i);
-                    else out[i] = v[u];
-                }
-            }
-        }
-    }
-    if (MODE == 1 && (acc.x ^ acc.y ^ acc.z ^ acc.w) == 0x12345678u) out[0] = acc;      // never true for the probe's fill pattern
-}
-
-int probe_shapes(int mode) { return mode == 0 ? 2 : mode == 1 ? 2 : 3; }
-const char *probe_shape_name(int mode, int shape)
-{
-    static const char *names[3][3] = {
-        {"non-temporal, 4 accesses in flight, 4096 x 256 threads", "non-temporal, 4 accesses in flight, 256 x 512 threads", ""},
-        {"non-temporal loads, 4 in flight, 256 x 512 threads", "non-temporal loads, 512 x 1024 threads", ""},
-        {"plain stores, 256 x 256 threads", "plain stores, 8 per iteration, 256 x 1024 threads", "non-temporal stores, 256 x 256 threads"}};
-    return names[mode][shape];
-}
-
-hipError_t launch_probe(int mode, int shape, const void *in, void *out, size_t bytes, hipStream_t stream)
-{
-    const size_t n = bytes / 16;
-    const probe_u32x4 *pi = (const probe_u32x4 *)in;
-    probe_u32x4 *po = (probe_u32x4 *)out;
-    if (mode == 0 && shape == 0) hipLaunchKernelGGL((k_probe<0, 4, true>), dim3(4096), dim3(256), 0, stream, pi, po, n);
-    else if (mode == 0) hipLaunchKernelGGL((k_probe<0, 4, true>), dim3(256), dim3(512), 0, stream, pi, po, n);
-    else if (mode == 1 && shape == 0) hipLaunchKernelGGL((k_probe<1, 4, true>), dim3(256), dim3(512), 0, stream, pi, po, n);
-    else if (mode == 1) hipLaunchKernelGGL((k_probe<1, 1, true>), dim3(512), dim3(1024), 0, stream, pi, po, n);
-    else if (shape == 0) hipLaunchKernelGGL((k_probe<2, 1, false>), dim3(256), dim3(256), 0, stream, pi, po, n);
-    else if (shape == 1) hipLaunchKernelGGL((k_probe<2, 8, false>), dim3(256), dim3(1024), 0, stream, pi, po, n);
-    else hipLaunchKernelGGL((k_probe<2, 1, true>), dim3(256), dim3(256), 0, stream, pi, po, n);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------
-// k_roi_tensor: a device table of regions of interest over full-size RGBA, each cut out and area-averaged into its own
-// 3 x H' x W' tensor (h263mi_roi_tensor_on; roi_kernel.inl).  k_tensor_resize's launch shape with the region in the place of the
-// picture: one wave per workgroup, no barrier, blockIdx.y = region, blockIdx.z = segment of 64 output columns, blockIdx.x = band
-// of RESIZE_ROWS output rows in XCD order.  A wave validates its region and makes its spans itself.
-// (Last in the file: the kernels above compile to what they were, to the branch labels' numbers.)
-// ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_roi_tensor(RoiArgs a)
-{
-    __shared__ __attribute__((aligned(16))) ResizeLds lds;
-    const uint32_t band = xcd_band(blockIdx.x, a.t.r.chunk);
-    if (band >= a.t.r.bands) return;
-    const int lane = threadIdx.x & 63;
-    RoiLane t;
-    roi_tensor_item(a, lds, band, blockIdx.z, blockIdx.y, [&](auto f) { f(lane, t); });
-}
-
-hipError_t launch_roi_tensor(const RoiArgs &args, hipStream_t stream)
-{
-    return launch_banded(k_roi_tensor, roi_plan, args, args.n_rois, stream);
-}
-
-// ---------------------------------------------------------------------------------------
-// k_change, k_change_select: change maps of 8-bit planes (h263mi_change_map_on, h263mi_batch_change_last; change_kernel.inl).
-// One wave per workgroup, no barrier: blockIdx.x = the wave's run of items_per_wave work items (segments of CHANGE_SEG columns of
-// a cell row, row after row), blockIdx.y = picture (from args.p0).  A launch holds at most CHANGE_GRID_MAX workgroups, whole
-// pictures; the select kernel is one wave.
-// (Behind everything else in the file, as k_roi_tensor was: the kernels above compile to what they were.)
-// ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_change(ChangeArgs a)
-{
-    __shared__ __attribute__((aligned(16))) ChangeLds lds;
-    const int lane = threadIdx.x & 63;
-    ChangeLane t;
-    change_wave(a, lds, a.p0 + blockIdx.y, blockIdx.x * a.items_per_wave, [&](auto f) { f(lane, t); });
-}
-
-__global__ __launch_bounds__(64) void k_change_select(ChangeSelectArgs f)
-{
-    __shared__ __attribute__((aligned(16))) ChangeLds lds;
-    const int lane = threadIdx.x & 63;
-    ChangeLane t;
-    change_select(f, lds, [&](auto g) { g(lane, t); });
-}
-
-hipError_t launch_change(const ChangeArgs &args, const ChangeSelectArgs *sel, hipStream_t stream)
-{
-    if (args.n_pictures) {
-        ChangeArgs a = args;
-        ChangeLaunch l;
-        if (!change_plan(a, l)) return hipErrorInvalidValue;
-        for (a.p0 = 0; a.p0 < a.n_pictures; a.p0 += l.pictures) {
-            const uint32_t n = a.n_pictures - a.p0 < l.pictures ? a.n_pictures - a.p0 : l.pictures;
-            hipLaunchKernelGGL(k_change, dim3(l.waves, n), dim3(64), 0, stream, a);
-            const hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return e;
-        }
-    }
-    if (sel) {
-        if (!sel->selected || !sel->count || (sel->n_pictures && !sel->summary)) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(k_change_select, dim3(1), dim3(64), 0, stream, *sel);
-        return hipGetLastError();
-    }
-    return hipSuccess;
 }
 
 }  // namespace h263mi

@@ -1,7 +1,7 @@
 // dev_common.h -- types and helpers shared by the HIP kernels and their host launchers.
 //
 // Kernel bodies are written as per-phase inline functions taking an explicit lane index
-// and wave position (recon_kernel.inl, post_kernel.inl); kernels.hip calls them from the
+// and wave position (recon_kernel.inl, post_kernel.inl); decode_kernels.hip calls them from the
 // __global__ functions, one wave per workgroup, no barriers.  tests/sim/ compiles the
 // same phase functions with g++ (ASan/UBSan) and runs the 64 lanes of a wave in a loop,
 // one phase at a time -- a logic checker for index math and edge handling, used by the

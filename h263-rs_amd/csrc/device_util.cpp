@@ -307,7 +307,7 @@ static int probe_bandwidth(const h263mi_backend_cfg *cfg, int mode, size_t bytes
         (void)hipEventDestroy(e0);
         return H263MI_ERR_HIP;
     }
-    // every launch shape of the mode (kernels.hip: probe_shapes), the fastest one is the box's ceiling
+    // every launch shape of the mode (support_kernels.hip: probe_shapes), the fastest one is the box's ceiling
     hipError_t e = hipSuccess;
     float best_ms = 0.f;
     for (int shape = 0; shape < probe_shapes(mode) && e == hipSuccess; shape++) {

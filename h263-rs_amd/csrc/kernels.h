@@ -1,4 +1,5 @@
-// kernels.h -- host-visible launchers of the gfx950 kernels (kernels.hip).
+// kernels.h -- host-visible launchers of the gfx950 kernels (decode_kernels.hip, output_kernels.hip,
+// analysis_kernels.hip, support_kernels.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -52,7 +53,7 @@ hipError_t launch_frame_yuv(const ReconArgs &rargs, const PostArgs &pargs, const
                             const uint32_t *words = nullptr) __attribute__((weak));
 // k_rgba_resize over args.n_pictures pictures (resize_kernel.inl; bands and chunk are set here).  Declared weak: the host
 // objects are also linked, in the CPU suite's ThreadSanitizer build (tests/tsan), against a stub runtime that has no resize
-// launcher.  The library always defines it (kernels.hip); h263mi_batch::launch_resize refuses to run without it.
+// launcher.  The library always defines it (output_kernels.hip); h263mi_batch::launch_resize refuses to run without it.
 hipError_t launch_rgba_resize(const ResizeArgs &args, hipStream_t stream) __attribute__((weak));
 // k_tensor_resize over args.r.n_pictures pictures (tensor_resize_kernel.inl; bands and chunk are set here): k_rgba_resize's launch
 // shape, planar float stores.  Weak like launch_rgba_resize; h263mi_batch::launch_resize refuses to write a tensor without it.
@@ -88,7 +89,7 @@ hipError_t launch_digest(const DigestArgs &args, const DigestFinalArgs &fin, hip
 hipError_t launch_synth_headers(const SynthArgs &args, hipStream_t stream);
 hipError_t launch_synth_coeffs(const SynthArgs &args, hipStream_t stream);
 // streaming probes: mode 0 copy in -> out, 1 read in (out = 16-byte sink), 2 write out; bytes is a multiple of 16;
-// shape < probe_shapes(mode) picks the launch shape (kernels.hip)
+// shape < probe_shapes(mode) picks the launch shape (support_kernels.hip)
 int probe_shapes(int mode);
 const char *probe_shape_name(int mode, int shape);
 hipError_t launch_probe(int mode, int shape, const void *in, void *out, size_t bytes, hipStream_t stream);

@@ -14,7 +14,7 @@
 // x PLANE_ROWS output rows of one plane JOB of one picture.  A job is the luma plane (one channel) or the chroma pair (two
 // channels: Cb and Cr have one geometry, are resized at the same output positions and, for NV12, leave interleaved in one
 // store).  blockIdx.y = picture, blockIdx.z = column segment -- the luma segments first, the chroma segments behind them --,
-// blockIdx.x = band in XCD order (kernels.hip: k_plane_resize): ONE launch serves all planes of all pictures.
+// blockIdx.x = band in XCD order (output_kernels.hip: k_plane_resize): ONE launch serves all planes of all pictures.
 // Per output row the wave walks the source columns that its output columns cover in chunks of PLANE_CHUNK: each lane sums
 // PLANE_SRC adjacent source samples down the row's source rows (one 16-byte load per row where the plane's start and width are
 // multiples of 16, bytes otherwise), the wave hands the column sums through LDS, and each lane weighs the ones its output

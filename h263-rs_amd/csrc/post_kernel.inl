@@ -12,7 +12,7 @@
 // any other wave: load strip -> H-edge -> V-edges -> convert -> 16-byte RGBA stores, through
 // 1.5 KB of wave-private LDS, with NO workgroup barrier (DS operations of one wave execute in
 // order, which is all the cross-lane hand-offs need).  A workgroup is four such waves (a
-// 128x32 tile) only so that the XCD-aware work order of kernels.hip keeps neighbours together.
+// 128x32 tile) only so that the XCD-aware work order of decode_kernels.hip keeps neighbours together.
 //
 // The reference mixes two integer semantics by position: its
 // SIMD lanes use arithmetic shifts (floor), its scalar tails use `/` (truncation).

@@ -9,7 +9,7 @@
 // and Cr -- 48 block tasks, 3 072 reconstructed bytes.  A wave needs nothing from any other wave, so there is NO
 // workgroup barrier: hand-offs between lanes go through 5.9 KB of wave-private LDS and rely only on the DS
 // operations of one wave executing in order.  One wave is one workgroup (its LDS and registers are released when it
-// ends); the XCD-aware work order of kernels.hip keeps neighbouring waves on one L2.
+// ends); the XCD-aware work order of decode_kernels.hip keeps neighbouring waves on one L2.
 //
 // Round 3 redesign (profiles/README.md, r03): the wave was reshaped to execute fewer instructions -- vector, scalar and
 // vector-memory alike -- per reconstructed byte (what limits the launch is the CU's memory pipeline with the vector ALUs
@@ -967,7 +967,7 @@ H263_DEV RowClass recon_row_class(const RowIn &ri, int lane)
 // pass with 1.0 in the place of B[0][i]: T[r][i] = C[r][0] exactly, for every i, so that the column pass finds the
 // untouched first column in whichever column of T it reads.
 // DENSE (round 4): the round is known to be "all Full" -- eight blocks, every coefficient row of every one of them with a
-// non-zero LEVEL in its last pair (kernels.hip: recon_round_rows decides it with one ballot).  Nothing of what the general
+// non-zero LEVEL in its last pair (decode_kernels.hip: recon_round_rows decides it with one ballot).  Nothing of what the general
 // form spends on being general is left: no activity mask, no class, no column count -- dequantise 4 pairs, 8 terms, store.
 // The arithmetic is the general form's with n_cols = 8 and no first-column-only block: bit for bit the same results.
 // WIDE (round 5): some LEVEL of the round lies outside [-512, 511] (RowIn::wide): the dequantiser is the wrapping

@@ -9,7 +9,7 @@
 // small table made on the host (resize_spans: it divides, the device does not -- DESIGN section 3).
 //
 // One wave per workgroup, no barrier: a wave = 64 output columns (one per lane) x RESIZE_ROWS output rows of one picture;
-// blockIdx.y = picture, blockIdx.z = column segment, blockIdx.x = band in XCD order (kernels.hip: k_rgba_resize).
+// blockIdx.y = picture, blockIdx.z = column segment, blockIdx.x = band in XCD order (output_kernels.hip: k_rgba_resize).
 // Per output row it walks the source columns its 64 columns cover in chunks of 256: each lane sums 4 adjacent source pixels
 // down the row's source rows (coalesced 16-byte loads when a row is 16-byte aligned), the wave hands the 256 column sums
 // through LDS, and each lane weighs the ones its output column covers.  Source pixels are read once per output row that

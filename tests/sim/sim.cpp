@@ -2,7 +2,7 @@
 //
 // Compiles h263-rs_amd/csrc/{recon,post}_kernel.inl with g++ (-fsanitize=address,undefined,
 // -ffp-contract=off) and runs the 256 threads of each workgroup in a loop, one phase at a
-// time, in the order kernels.hip separates them with __syncthreads().  It catches index,
+// time, in the order decode_kernels.hip separates them with __syncthreads().  It catches index,
 // bounds and edge-case mistakes before a GPU run; it is never linked into the product and
 // measures nothing.
 #include <stdlib.h>
@@ -157,7 +157,7 @@ int sim_recon_ex(uint32_t w, uint32_t h, uint32_t n_pictures, const MbRecord *mb
     a.tiles_y = (a.L.mbh + TILE_MBY - 1) / TILE_MBY;
     a.groups_per_picture = a.tiles_x * a.L.mbh;
     ReconWave *s = (ReconWave *)aligned_alloc(16, (sizeof(ReconWave) + 15) / 16 * 16);
-    // same work units as kernels.hip::k_recon: XCD-ordered tiles, one independent wave per macroblock row of a tile (the
+    // same work units as decode_kernels.hip::k_recon: XCD-ordered tiles, one independent wave per macroblock row of a tile (the
     // order of units does not matter)
     const uint32_t tpp = a.tiles_x * a.tiles_y, total = tpp * n_pictures, chunk = (total + 7) / 8;
     static WaveFetch f[64];
@@ -181,7 +181,7 @@ int sim_recon_ex(uint32_t w, uint32_t h, uint32_t n_pictures, const MbRecord *mb
             ws.pic = (uint32_t)p.pic; ws.mby = (uint32_t)p.mby; ws.group = (uint32_t)(p.mbx0 >> 3);
             ws.valid = recon_valid_mask(a, p);
             ws.group_word = group_word;
-            if (a.mb_group_index && (group_word & 0xffu) == 0 && a.has_ref && recon_valid_mask(a, p) == 0xffu) {   // as kernels.hip::recon_wave
+            if (a.mb_group_index && (group_word & 0xffu) == 0 && a.has_ref && recon_valid_mask(a, p) == 0xffu) {   // as decode_kernels.hip::recon_wave
                 for (int l = 0; l < 64; l++) recon_phase_copy(a, l, p);
                 ws.is_static = 2;
                 wave_stats.push_back(ws);
@@ -208,14 +208,14 @@ int sim_recon_ex(uint32_t w, uint32_t h, uint32_t n_pictures, const MbRecord *mb
             bool any_moving = false;
             for (int l = 0; l < 64; l++) any_moving = any_moving || ti[l].moving;
             ws.n_active = (uint32_t)recon_n_active(km);
-            if (recon_wave_is_static(a, km, any_moving)) {  // as kernels.hip::recon_wave
+            if (recon_wave_is_static(a, km, any_moving)) {  // as decode_kernels.hip::recon_wave
                 for (int l = 0; l < 64; l++) recon_phase_copy(a, l, p);
                 ws.is_static = 1;
                 wave_stats.push_back(ws);
                 round_stats.push_back(rs);
                 continue;
             }
-            const bool mc = a.has_ref && km.inter;          // the dispatch of kernels.hip: recon_tail<MC>
+            const bool mc = a.has_ref && km.inter;          // the dispatch of decode_kernels.hip: recon_tail<MC>
             ws.mc = mc;
             ws.all_inter = mc && a.has_ref && km.inter == km.valid && km.valid == 0xffu;     // as recon_phase_predict<true>
             for (int l = 0; l < 64; l++) {
@@ -223,7 +223,7 @@ int sim_recon_ex(uint32_t w, uint32_t h, uint32_t n_pictures, const MbRecord *mb
                 else recon_phase_fetch<false>(a, *s, f[l], l, p, km);
             }
             const int n_active = recon_n_active(km);
-            // as kernels.hip::recon_tail: row pass of round 0, prediction into the strip, column pass of round 0, the
+            // as decode_kernels.hip::recon_tail: row pass of round 0, prediction into the strip, column pass of round 0, the
             // remaining rounds, store
             for (int round = 0; round == 0 || round * ROUND_BLOCKS < n_active; round++) {
                 static RowIn ri[64];
@@ -241,12 +241,12 @@ int sim_recon_ex(uint32_t w, uint32_t h, uint32_t n_pictures, const MbRecord *mb
                         if (rc.any) { rows_any |= 1ull << l; rm |= 1u << (l & 7); }
                         if (rc.beyond_first) cols_any |= 1ull << l;
                     }
-                    bool wide = false;                                      // as kernels.hip: recon_round_rows
+                    bool wide = false;                                      // as decode_kernels.hip: recon_round_rows
                     for (int l = 0; l < 64; l++) wide = wide || ri[l].wide != 0;
                     if (force_wide_rounds) wide = true;
                     // the dense round: not wide, and a non-zero LEVEL in columns 6..7 of EVERY lane's coefficient row (one
                     // ballot on the device); it takes the <true> instantiations of both passes, with the arguments of
-                    // kernels.hip: recon_round_rows / recon_round_cols
+                    // decode_kernels.hip: recon_round_rows / recon_round_cols
                     dense = !wide;
                     for (int l = 0; l < 64; l++) dense = dense && ri[l].w[3] != 0;
                     for (int l = 0; l < 64; l++) {
@@ -313,7 +313,7 @@ int sim_post(uint32_t w, uint32_t h, uint32_t n_pictures, const uint8_t *frames,
     a.tiles_y = (post_strips_y(h) + POST_STRIPS - 1) / POST_STRIPS;
     a.luma_only = luma_only;
     PostStrip *s = (PostStrip *)aligned_alloc(16, (sizeof(PostStrip) + 15) / 16 * 16);
-    // same work decomposition as kernels.hip::k_post: XCD-ordered workgroups of 4 waves, one tile
+    // same work decomposition as decode_kernels.hip::k_post: XCD-ordered workgroups of 4 waves, one tile
     // (4 strips) per wave, all loads of the tile first
     const uint32_t groups_y = (a.tiles_y + POST_GROUP - 1) / POST_GROUP;
     const uint32_t wpp = a.tiles_x * groups_y, wgs = wpp * n_pictures, chunk = (wgs + 7) / 8;
@@ -326,7 +326,7 @@ int sim_post(uint32_t w, uint32_t h, uint32_t n_pictures, const uint8_t *frames,
             const int sx = rem % (int)a.tiles_x + (int)a.wrap, ty = (rem / (int)a.tiles_x) * POST_GROUP + wave;
             if (ty >= (int)a.tiles_y) continue;
             const int sy0 = ty * POST_STRIPS;
-            // interior tiles take the instantiations without bounds handling, as on the device (kernels.hip: post_wave)
+            // interior tiles take the instantiations without bounds handling, as on the device (decode_kernels.hip: post_wave)
             if (post_tile_is_interior(a, sx, ty)) sim_post_tile<true>(a, *s, pf, sx, sy0, pic, strength);
             else sim_post_tile<false>(a, *s, pf, sx, sy0, pic, strength);
         }

@@ -98,27 +98,33 @@ def test_kernel_isa_has_no_fused_multiply_add_and_no_compiler_selected_ashr_pk()
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("hipcc not available")
-    src = os.path.join(ROOT, "h263-rs_amd", "csrc", "kernels.hip")
-    with tempfile.TemporaryDirectory() as td:
-        out = os.path.join(td, "k.s")
-        subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
-                               "-fno-fast-math", "-S", "--cuda-device-only", "-x", "hip", src, "-o", out],
-                              stderr=subprocess.DEVNULL)
-        asm = open(out).read()
-    body = asm[asm.index("k_recon"):]
-    for bad in ("v_fma_f32", "v_fmac_f32", "v_mac_f32", "v_mad_f32", "v_pk_fma_f32", "v_fma_mix"):
-        assert bad not in asm, bad
-    # v_ashr_pk_u8_i32 may only come from the hand-written asm of post_kernel.inl (which merges its
-    # 16-bit halves with a byte permute), never from the compiler's own lowering
-    in_asm = False
-    for line in asm.splitlines():
-        if "#ASMSTART" in line:
-            in_asm = True
-        elif "#ASMEND" in line:
-            in_asm = False
-        elif "v_ashr_pk_" in line:
-            assert in_asm, "compiler-selected v_ashr_pk: " + line
-    assert "v_pk_mul_f32" in body or "v_mul_f32" in body
+    # the kernel units of the library, from the one place that lists them
+    makefile = open(os.path.join(ROOT, "h263-rs_amd", "Makefile")).read()
+    units = re.search(r"^KERNEL_UNITS\s*=\s*(.+)$", makefile, re.M).group(1).split()
+    assert "decode_kernels" in units
+    for unit in units:
+        src = os.path.join(ROOT, "h263-rs_amd", "csrc", unit + ".hip")
+        with tempfile.TemporaryDirectory() as td:
+            out = os.path.join(td, "k.s")
+            subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
+                                   "-fno-fast-math", "-S", "--cuda-device-only", "-x", "hip", src, "-o", out],
+                                  stderr=subprocess.DEVNULL)
+            asm = open(out).read()
+        for bad in ("v_fma_f32", "v_fmac_f32", "v_mac_f32", "v_mad_f32", "v_pk_fma_f32", "v_fma_mix"):
+            assert bad not in asm, (unit, bad)
+        # v_ashr_pk_u8_i32 may only come from the hand-written asm of post_kernel.inl (which merges its
+        # 16-bit halves with a byte permute), never from the compiler's own lowering
+        in_asm = False
+        for line in asm.splitlines():
+            if "#ASMSTART" in line:
+                in_asm = True
+            elif "#ASMEND" in line:
+                in_asm = False
+            elif "v_ashr_pk_" in line:
+                assert in_asm, "compiler-selected v_ashr_pk in %s: %s" % (unit, line)
+        if unit == "decode_kernels":
+            body = asm[asm.index("k_recon"):]
+            assert "v_pk_mul_f32" in body or "v_mul_f32" in body
 
 
 def test_oversized_pictures_are_rejected_before_any_allocation():

@@ -1,7 +1,7 @@
 """The launch plans of the banded kernels and of k_change (resize_plan ... roi_plan, change_plan: beside their Args in
 h263-rs_amd/csrc/*.inl) on the CPU under AddressSanitizer + UBSan (tests/launch_plan/launch_plan.cpp): bands, chunk, segs_y and
 the grid at the shapes where the arithmetic can go wrong, and every refusal -- one accepted argument set, then that set with one
-field pushed over its limit.  The launchers of kernels.hip are the plan and one launch; the host refuses bad arguments earlier, so
+field pushed over its limit.  The launchers of output_kernels.hip and analysis_kernels.hip are the plan and one launch; the host refuses bad arguments earlier, so
 nothing else reaches these checks.
 
 Every expected value is a literal worked out by hand from bands = ceil(rows / 4) (RESIZE_ROWS, FILTER_ROWS, PLANE_ROWS and

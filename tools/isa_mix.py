@@ -3,7 +3,7 @@
 
     python tools/isa_mix.py [k_recon|k_post|k_frame] [-D MACRO ...] > profiles/rNN_isa_mix_<kernel>.txt
 
-Builds h263-rs_amd/csrc/kernels.hip for the device only with -DH263MI_ISA_MARKERS (comments at the phase
+Builds h263-rs_amd/csrc/decode_kernels.hip for the device only with -DH263MI_ISA_MARKERS (comments at the phase
 boundaries, no instruction emitted) and counts, per phase, the instructions between two markers in program order:
 
   valu_fast  VALU opcodes that issue in ~2.4 cycles per wave64 on MI355X (profiles/r01_valu_rate.txt):
@@ -30,8 +30,8 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FAST = {"v_add_u32", "v_sub_u32", "v_subrev_u32", "v_and_b32", "v_or_b32", "v_xor_b32", "v_lshrrev_b32", "v_ashrrev_i32",
         "v_mov_b32", "v_mul_f32", "v_add_f32", "v_sub_f32", "v_fma_f32", "v_fmac_f32", "v_not_b32"}
-MANGLED = {"k_recon": "_ZN6h263mi7k_reconENS_9ReconArgsE", "k_post": "_ZN6h263mi6k_postENS_8PostArgsE",
-           "k_frame": "_ZN6h263mi7k_frameENS_9ReconArgsENS_8PostArgsENS_9FrameGeomE"}
+MANGLED = {"k_recon": "_ZN6h263mi7k_reconENS_11StreamWordsENS_9ReconArgsE", "k_post": "_ZN6h263mi6k_postENS_11StreamWordsENS_8PostArgsE",
+           "k_frame": "_ZN6h263mi7k_frameENS_11StreamWordsENS_9ReconArgsENS_8PostArgsENS_9FrameGeomE"}
 CLASSES = ["valu_fast", "valu_slow", "salu", "smem", "lds", "vmem_rd", "vmem_wr", "wait", "branch"]
 
 
@@ -74,7 +74,7 @@ def main():
         out = os.path.join(tmp, "k.s")
         cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
                "-fno-strict-aliasing", "-Wno-unused-function", "-DH263MI_ISA_MARKERS"] + ["-D" + d for d in defines] + \
-              ["-x", "hip", "--cuda-device-only", "-S", "-o", out, os.path.join(ROOT, "h263-rs_amd", "csrc", "kernels.hip")]
+              ["-x", "hip", "--cuda-device-only", "-S", "-o", out, os.path.join(ROOT, "h263-rs_amd", "csrc", "decode_kernels.hip")]
         subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
         text = open(out).read()
     name = MANGLED[kernel]

@@ -3,7 +3,7 @@
 #
 # tools/isa_mix.py is a static table: a loop body counts once, both arms of a branch count.  Here the launch's own
 # counters say what ran: a series of builds in which the reconstruction waves (H263MI_STOP_RECON=1..5) or the
-# post-processing waves (H263MI_STOP_POST=1..3) stop behind a phase (kernels.hip; results wrong by construction), each
+# post-processing waves (H263MI_STOP_POST=1..3) stop behind a phase (decode_kernels.hip; results wrong by construction), each
 # profiled with `rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR` over the bench's
 # GOPs (counters only, one pass per build).  The difference between two consecutive builds is the phase between their stops.
 # usage (GPU box, repo root; the variants built beforehand with tools/build_variant.sh stop_<name> -DH263MI_STOP_...=n):
