@@ -1,9 +1,10 @@
-// analysis_kernels.hip -- digests and change maps of pictures in device memory: __global__ wrappers and launchers.
+// analysis_kernels.hip -- digests, change maps and histograms of pictures in device memory: __global__ wrappers and launchers.
 // Built with the flags of decode_kernels.hip.
 #include "kernels.h"
 
 #include "change_kernel.inl"
 #include "digest_kernel.inl"
+#include "hist_kernel.inl"
 
 namespace h263mi {
 
@@ -80,6 +81,62 @@ hipError_t launch_change(const ChangeArgs &args, const ChangeSelectArgs *sel, hi
     if (sel) {
         if (!sel->selected || !sel->count || (sel->n_pictures && !sel->summary)) return hipErrorInvalidValue;
         hipLaunchKernelGGL(k_change_select, dim3(1), dim3(64), 0, stream, *sel);
+        return hipGetLastError();
+    }
+    return hipSuccess;
+}
+
+// ---------------------------------------------------------------------------------------
+// k_hist, k_hist_final, k_hist_select: histograms of 8-bit planes, their statistics and the scene-cut list (h263mi_hist_on,
+// h263mi_batch_hist_last; hist_kernel.inl).  One wave per workgroup, no barrier.  k_hist: blockIdx.x = the wave's run of
+// items_per_wave work items (segments of HIST_SEG columns of a band of HIST_ROWS rows, band after band), blockIdx.y = picture (from
+// args.p0); a launch holds at most HIST_GRID_MAX workgroups, whole pictures.  k_hist_final: blockIdx.x = picture.  The select
+// kernel is one wave.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_hist(HistArgs a)
+{
+    __shared__ __attribute__((aligned(16))) HistLds lds;
+    const int lane = threadIdx.x & 63;
+    HistLane t;
+    hist_wave(a, lds, a.p0 + blockIdx.y, blockIdx.x * a.items_per_wave, [&](auto f) { f(lane, t); });
+}
+
+__global__ __launch_bounds__(64) void k_hist_final(HistFinalArgs f)
+{
+    __shared__ __attribute__((aligned(16))) HistFinalLds lds;
+    const int lane = threadIdx.x & 63;
+    HistLane t;
+    hist_final(f, lds, blockIdx.x, [&](auto g) { g(lane, t); });
+}
+
+__global__ __launch_bounds__(64) void k_hist_select(HistSelectArgs f)
+{
+    __shared__ __attribute__((aligned(16))) HistFinalLds lds;
+    const int lane = threadIdx.x & 63;
+    HistLane t;
+    hist_select(f, lds, [&](auto g) { g(lane, t); });
+}
+
+hipError_t launch_hist(const HistArgs &args, const HistFinalArgs &fin, const HistSelectArgs *sel, hipStream_t stream)
+{
+    if (args.n_pictures) {
+        HistArgs a = args;
+        HistLaunch l;
+        if (!hist_plan(a, l) || fin.n_pictures != a.n_pictures || !fin.hist || !fin.stats || (fin.roll && !fin.prev))
+            return hipErrorInvalidValue;
+        for (a.p0 = 0; a.p0 < a.n_pictures; a.p0 += l.pictures) {
+            const uint32_t n = a.n_pictures - a.p0 < l.pictures ? a.n_pictures - a.p0 : l.pictures;
+            hipLaunchKernelGGL(k_hist, dim3(l.waves, n), dim3(64), 0, stream, a);
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL(k_hist_final, dim3(fin.n_pictures), dim3(64), 0, stream, fin);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    if (sel) {
+        if (!sel->selected || !sel->count || (sel->n_pictures && !sel->stats)) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_hist_select, dim3(1), dim3(64), 0, stream, *sel);
         return hipGetLastError();
     }
     return hipSuccess;

@@ -1413,6 +1413,140 @@ int h263mi_batch_change_last(h263mi_batch *b, const h263mi_plane_set *prev, cons
     return b->change_last(prev, c, d_cells, cells_bytes, d_summary, d_selected, d_count, stream_rc);
 }
 
+// =========================================================================================
+// plane histograms (hist_kernel.inl)
+// =========================================================================================
+int h263mi_hist_extent(uint32_t n_pictures, uint32_t width, uint32_t height, const h263mi_hist *h, uint64_t *hist_bytes)
+{
+    static_assert(sizeof(h263mi_hist) == 16 && sizeof(h263mi_hist_stats) == 32, "the structures are part of the ABI");
+    if (!h || h->reserved[0] || h->reserved[1] || h->reserved[2] || h->reserved2 || h->roll > 1) return H263MI_ERR_INVALID_ARGUMENT;
+    if (h->lo_permille > 1000 || h->hi_permille > 1000 || h->cut_permille > 1000 || h->lo_permille > h->hi_permille)
+        return H263MI_ERR_INVALID_ARGUMENT;
+    if (!width || !height || width > 65535 || height > 65535 || (uint64_t)width * height >= (1ull << 30)) return H263MI_ERR_INVALID_ARGUMENT;
+    if (n_pictures > HIST_MAX_PICTURES) return H263MI_ERR_INVALID_ARGUMENT;
+    if (hist_bytes) *hist_bytes = (uint64_t)n_pictures * 1024u;
+    return H263MI_OK;
+}
+
+// The arguments of a histogram call, decided on the host in the order include/h263mi.h lists; *out, *fin, *sel: the launches they
+// come to.
+static int hist_args(const h263mi_plane_set *set, uint32_t n, uint32_t w, uint32_t h, const h263mi_hist *d, uint32_t *d_hist, uint64_t hist_bytes,
+                     uint32_t *d_prev, uint64_t prev_bytes, h263mi_hist_stats *d_stats, uint32_t *d_selected, uint32_t *d_count, HistArgs *out,
+                     HistFinalArgs *fin, HistSelectArgs *sel)
+{
+    uint64_t extent = 0;
+    RC_TRY(h263mi_hist_extent(n, w, h, d, &extent));
+    HistArgs a{};
+    if (n) {
+        if (!set || !d_hist || !d_stats || !set->d_base) return H263MI_ERR_INVALID_ARGUMENT;
+        if (h > 1 && set->pitch < w) return H263MI_ERR_INVALID_ARGUMENT;
+        uint64_t end;
+        if (!plane_set_end(*set, n, w, h, &end) || end > set->bytes) return H263MI_ERR_INVALID_ARGUMENT;
+        if (hist_bytes < extent || (d_prev && prev_bytes < extent)) return H263MI_ERR_INVALID_ARGUMENT;
+        if ((uintptr_t)d_hist % 4 || (uintptr_t)d_prev % 4 || (uintptr_t)d_stats % 8) return H263MI_ERR_INVALID_ARGUMENT;
+        const uintptr_t h0 = (uintptr_t)d_hist, p0 = (uintptr_t)d_prev;
+        if (d_prev && p0 < h0 + extent && h0 < p0 + extent) return H263MI_ERR_INVALID_ARGUMENT;
+        a.src = set->d_base;
+        a.pitch = set->pitch, a.stride = set->picture_stride;
+        a.align = change_align(set->d_base, set->pitch, set->picture_stride);
+    }
+    if ((d->roll || d_selected || d_count) && !d_prev) return H263MI_ERR_INVALID_ARGUMENT;
+    if (!d_selected != !d_count) return H263MI_ERR_INVALID_ARGUMENT;
+    a.hist = d_hist;
+    a.w = w, a.h = h, a.n_pictures = n;
+    a.segs = (w + HIST_SEG - 1u) / HIST_SEG;
+    a.bands = (h + HIST_ROWS - 1u) / HIST_ROWS;
+    *out = a;
+    *fin = HistFinalArgs{d_hist, d_prev, d_stats, nullptr, (uint64_t)w * h, n, d->lo_permille, d->hi_permille, d->roll};
+    *sel = HistSelectArgs{d_stats, nullptr, d_selected, d_count, (uint64_t)w * h, n, d->cut_permille};
+    return H263MI_OK;
+}
+
+// the clearing of the histograms, k_hist, k_hist_final, and k_hist_select when a list is wanted, queued on `stream` of the current device
+static int hist_launch(const HistArgs &a, const HistFinalArgs &fin, const HistSelectArgs &sel, hipStream_t stream)
+{
+    if (!a.n_pictures && !sel.count) return H263MI_OK;
+    if (!launch_hist) return H263MI_ERR_HIP;               // (kernels.h: only a stub runtime lacks it)
+    auto queue = [&]() -> int {
+        if (a.n_pictures) HIP_TRY(hipMemsetAsync(a.hist, 0, (size_t)a.n_pictures * 1024u, stream));
+        HIP_TRY(launch_hist(a, fin, sel.count ? &sel : nullptr, stream));
+        return H263MI_OK;
+    };
+    return digest_rc(queue());                             // (whatever the runtime refuses is H263MI_ERR_HIP)
+}
+
+int h263mi_batch::hist_last(uint32_t plane, const h263mi_hist *h, uint32_t *d_hist, uint64_t hist_bytes, uint32_t *d_prev_hist,
+                            uint64_t prev_bytes, h263mi_hist_stats *d_stats, uint32_t *d_selected, uint32_t *d_count, int *stream_rc)
+{
+    if (plane > 2) return H263MI_ERR_INVALID_ARGUMENT;
+    // the planes of the frame store, as copy_yuv reads them: set 0 at frames[0], set 1 behind it
+    const uint64_t set_bytes = (uint64_t)(frames[1] - frames[0]), off = plane == 0 ? 0u : (plane == 1 ? L.off_cb : L.off_cr);
+    const uint32_t pw = plane ? L.cwidth : L.width, ph = plane ? L.cheight : L.height;
+    const h263mi_plane_set store{frames[0] + off, 2 * set_bytes - off, plane ? L.pitch_c : L.pitch_y, L.frame_bytes};
+    HistArgs a;
+    HistFinalArgs fin;
+    HistSelectArgs sel;
+    RC_TRY(hist_args(&store, n, pw, ph, h, d_hist, hist_bytes, d_prev_hist, prev_bytes, d_stats, d_selected, d_count, &a, &fin, &sel));
+    RC_TRY(time_close());                        // a histogram is not part of any kernel's time
+    std::vector<uint32_t> words(n);
+    bool missing = false, same = true;
+    for (uint32_t i = 0; i < n; i++) {
+        words[i] = ss[i].cur < 0 ? 0u : (HIST_VALID | (ss[i].cur == 1 ? HIST_SET1 : 0u));
+        missing |= ss[i].cur < 0;
+        same &= words[i] == words[0];
+    }
+    a.set1 = set_bytes;
+    a.align = change_align(store.d_base, store.pitch, store.picture_stride, set_bytes);
+    if (same && !missing) {
+        a.src = frames[ss[0].cur] + off;         // every stream's picture lies in one set: no words
+    } else {
+        const uint32_t *d_words = nullptr;
+        RC_TRY(digest_rc(upload(word_ring, words.data(), &d_words, stream)));
+        a.words = fin.words = sel.words = d_words;
+    }
+    RC_TRY(hist_launch(a, fin, sel, stream));
+    if (stream_rc)
+        for (uint32_t i = 0; i < n; i++) stream_rc[i] = ss[i].cur < 0 ? H263MI_ERR_NO_PICTURE : H263MI_OK;
+    return missing && !stream_rc ? H263MI_ERR_NO_PICTURE : H263MI_OK;
+}
+
+int h263mi_hist_on(const h263mi_backend_cfg *cfg, const h263mi_plane_set *set, uint32_t n_pictures, uint32_t width, uint32_t height,
+                   const h263mi_hist *h, uint32_t *d_hist, uint64_t hist_bytes, uint32_t *d_prev_hist, uint64_t prev_bytes,
+                   h263mi_hist_stats *d_stats, uint32_t *d_selected, uint32_t *d_count)
+{
+    HistArgs a;
+    HistFinalArgs fin;
+    HistSelectArgs sel;
+    RC_TRY(hist_args(set, n_pictures, width, height, h, d_hist, hist_bytes, d_prev_hist, prev_bytes, d_stats, d_selected, d_count, &a, &fin, &sel));
+    if (!n_pictures && !d_count) return H263MI_OK;
+    const int dev = cfg ? cfg->device_id : 0;
+    RC_TRY(check_device(dev));
+    DeviceGuard g(dev);
+    if (!g.ok) return H263MI_ERR_NO_DEVICE;
+    return hist_launch(a, fin, sel, cfg ? (hipStream_t)cfg->stream : nullptr);
+}
+
+int h263mi_batch_hist(h263mi_batch *b, const h263mi_plane_set *set, const h263mi_hist *h, uint32_t *d_hist, uint64_t hist_bytes,
+                      uint32_t *d_prev_hist, uint64_t prev_bytes, h263mi_hist_stats *d_stats, uint32_t *d_selected, uint32_t *d_count)
+{
+    if (!b) return H263MI_ERR_INVALID_ARGUMENT;
+    HistArgs a;
+    HistFinalArgs fin;
+    HistSelectArgs sel;
+    RC_TRY(hist_args(set, b->n, b->L.width, b->L.height, h, d_hist, hist_bytes, d_prev_hist, prev_bytes, d_stats, d_selected, d_count, &a, &fin, &sel));
+    DeviceGuard g(b->device);
+    RC_TRY(b->sync());                           // (the deferred rendering of a pipelined batch, the second stream of an overlapped one)
+    return hist_launch(a, fin, sel, b->stream);
+}
+
+int h263mi_batch_hist_last(h263mi_batch *b, uint32_t plane, const h263mi_hist *h, uint32_t *d_hist, uint64_t hist_bytes, uint32_t *d_prev_hist,
+                           uint64_t prev_bytes, h263mi_hist_stats *d_stats, uint32_t *d_selected, uint32_t *d_count, int *stream_rc)
+{
+    if (!b) return H263MI_ERR_INVALID_ARGUMENT;
+    DeviceGuard g(b->device);
+    return b->hist_last(plane, h, d_hist, hist_bytes, d_prev_hist, prev_bytes, d_stats, d_selected, d_count, stream_rc);
+}
+
 int h263mi_batch_timing_begin(h263mi_batch *b)
 {
     if (!b) return H263MI_ERR_INVALID_ARGUMENT;

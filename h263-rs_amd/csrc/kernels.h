@@ -8,6 +8,7 @@
 #include "change_kernel.inl"
 #include "digest_kernel.inl"
 #include "filter_kernel.inl"
+#include "hist_kernel.inl"
 #include "plane_filter_kernel.inl"
 #include "plane_resize_kernel.inl"
 #include "resize_kernel.inl"
@@ -86,6 +87,11 @@ hipError_t launch_plane_filter(const PlaneFilterArgs &args, hipStream_t stream) 
 // k_digest over args.n_items work items, then k_digest_final over fin.n_digests digests (digest_kernel.inl): the launch pair of one
 // digest call, whatever it covers.  Weak like launch_rgba_resize; the digest entry points refuse to run without it.
 hipError_t launch_digest(const DigestArgs &args, const DigestFinalArgs &fin, hipStream_t stream) __attribute__((weak));
+// k_hist over the args.n_pictures x bands x segs work items of a histogram call (hist_kernel.inl; p0 and items_per_wave are set
+// here: a call of very many items goes out in several launches of whole pictures), then k_hist_final over the pictures and, with
+// sel, k_hist_select over the statistics.  The caller has cleared the histograms on the stream.  Weak like launch_rgba_resize; the
+// histogram entry points refuse to run without it.
+hipError_t launch_hist(const HistArgs &args, const HistFinalArgs &fin, const HistSelectArgs *sel, hipStream_t stream) __attribute__((weak));
 hipError_t launch_synth_headers(const SynthArgs &args, hipStream_t stream);
 hipError_t launch_synth_coeffs(const SynthArgs &args, hipStream_t stream);
 // streaming probes: mode 0 copy in -> out, 1 read in (out = 16-byte sink), 2 write out; bytes is a multiple of 16;

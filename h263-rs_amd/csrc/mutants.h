@@ -38,6 +38,11 @@
 //   -DH263MI_MUTATE_CHANGE_SEGMENT_CELL      change_item takes a later segment's first cell from the pixel in front of the
 //                                            segment: its first chunk (and every one behind it) is attributed to the cell on
 //                                            its left
+// ... and two of the plane histograms (hist_kernel.inl), which the CPU checker alone is built with (tests/test_sim_hist.py):
+//   -DH263MI_MUTATE_HIST_CUT_CHUNK_FULL      hist_count takes a chunk that the picture's right edge cuts short as a whole one: the
+//                                            missing pixels are counted as zeros
+//   -DH263MI_MUTATE_HIST_PERCENTILE_STRICT   hist_reached compares 1000 * C(v) > q * P where the contract says >=: a percentile
+//                                            that is reached exactly moves to the next value with a count
 // Two parts.  The switches need nothing and are included by post_kernel.inl and recon_kernel.inl; the IDCT helper is included
 // by recon_kernel.inl (which defines H263MI_MUTANTS_WITH_IDCT) behind the definitions it uses (f32x2, splat2, BasisPtr,
 // basis_pair).
@@ -121,6 +126,16 @@ constexpr bool kChangeEdgeAsFull = false;
 constexpr bool kChangeSegmentCell = true;
 #else
 constexpr bool kChangeSegmentCell = false;
+#endif
+#if defined(H263MI_MUTATE_HIST_CUT_CHUNK_FULL)
+constexpr bool kHistCutChunkFull = true;
+#else
+constexpr bool kHistCutChunkFull = false;
+#endif
+#if defined(H263MI_MUTATE_HIST_PERCENTILE_STRICT)
+constexpr bool kHistPercentileStrict = true;
+#else
+constexpr bool kHistPercentileStrict = false;
 #endif
 
 }  // namespace mutants

@@ -259,6 +259,15 @@ int h263mi_change_last(const h263mi_state *s, const h263mi_plane_set *prev, cons
     return s->b->change_last(prev, c, d_cells, cells_bytes, d_summary, d_selected, d_count, nullptr);
 }
 
+int h263mi_hist_last(const h263mi_state *s, uint32_t plane, const h263mi_hist *h, uint32_t *d_hist, uint64_t hist_bytes, uint32_t *d_prev_hist,
+                     uint64_t prev_bytes, h263mi_hist_stats *d_stats, uint32_t *d_selected, uint32_t *d_count)
+{
+    if (!s) return H263MI_ERR_INVALID_ARGUMENT;
+    if (!s->has_last || !s->b) return H263MI_ERR_NO_PICTURE;
+    DeviceGuard g(s->cfg.device_id);
+    return s->b->hist_last(plane, h, d_hist, hist_bytes, d_prev_hist, prev_bytes, d_stats, d_selected, d_count, nullptr);
+}
+
 // `strength` of the rendering calls: 0..12, or H263MI_STRENGTH_FROM_HEADER = what the last picture's own header asks for
 // (QUANT_TO_STRENGTH[quantizer] when USE_DEBLOCKER is set: deblock.rs:5-8, picture.rs:61-64)
 static int state_strength(const h263mi_state *s, uint8_t strength, h263mi_batch::Strengths &st)

@@ -110,6 +110,8 @@ EXPORTS = [
     "h263mi_roi_tensor_on", "h263mi_batch_roi_tensor",
     # ABI 7, additive: change maps -- per-cell SAD of two plane sets, per-picture summaries, the list of changed pictures
     "h263mi_change_extent", "h263mi_change_map_on", "h263mi_batch_change_map", "h263mi_batch_change_last", "h263mi_change_last",
+    # ABI 7, additive: plane histograms -- 256 counts per picture, statistics and percentiles, the list of scene cuts
+    "h263mi_hist_extent", "h263mi_hist_on", "h263mi_batch_hist", "h263mi_batch_hist_last", "h263mi_hist_last",
 ]
 FILTER_AREA, FILTER_BILINEAR, FILTER_BICUBIC = 0, 1, 2
 FRAME_STRETCH, FRAME_LETTERBOX, FRAME_COVER, FRAME_WINDOW = 0, 1, 2, 3
@@ -487,6 +489,43 @@ def change_map(cur, prev, n_pictures, width, height, change, d_cells, cells_byte
                                       d_summary, d_selected, d_count), "change_map")
 
 
+class Hist(C.Structure):
+    """h263mi_hist: the percentiles p_lo and p_hi in permille; a picture is a cut when distance * 1000 > cut_permille * 2 * W*H; roll:
+    prev takes the histograms"""
+    _fields_ = [("roll", C.c_uint8), ("reserved", C.c_uint8 * 3), ("lo_permille", C.c_uint16), ("hi_permille", C.c_uint16),
+                ("cut_permille", C.c_uint32), ("reserved2", C.c_uint32)]
+
+
+class HistStats(C.Structure):
+    _fields_ = [("sum", C.c_uint64), ("sum_sq", C.c_uint64), ("distance", C.c_uint64), ("min", C.c_uint8), ("max", C.c_uint8),
+                ("p_lo", C.c_uint8), ("p_hi", C.c_uint8), ("mode", C.c_uint8), ("reserved", C.c_uint8 * 3)]
+
+
+HIST_STATS_DTYPE = np.dtype([("sum", np.uint64), ("sum_sq", np.uint64), ("distance", np.uint64), ("min", np.uint8), ("max", np.uint8),
+                             ("p_lo", np.uint8), ("p_hi", np.uint8), ("mode", np.uint8), ("reserved", np.uint8, (3,))])
+
+
+def make_hist(lo_permille=10, hi_permille=990, cut_permille=500, roll=0):
+    return Hist(roll, (C.c_uint8 * 3)(0, 0, 0), lo_permille, hi_permille, cut_permille, 0)
+
+
+def hist_extent(n_pictures, width, height, hist):
+    """h263mi_hist_extent -> hist_bytes"""
+    nb = C.c_uint64(0)
+    _check(lib().h263mi_hist_extent(n_pictures, width, height, _opt(hist), C.byref(nb)), "hist_extent")
+    return nb.value
+
+
+def hist(plane_set, n_pictures, width, height, hist, d_hist, hist_bytes, d_stats, d_prev_hist=None, prev_bytes=0, d_selected=None,
+         d_count=None, device_id=0, stream=None):
+    """h263mi_hist_on: queues the launches that count the PlaneSet's pictures -- 256 uint32 per picture to d_hist, a HistStats per
+    picture to d_stats, the distance to d_prev_hist (device, or None), the ascending list of the cuts to d_selected and its length
+    to d_count (both device, or both None); does not wait."""
+    cfg = BackendCfg(device_id, 0, stream)
+    _check(lib().h263mi_hist_on(C.byref(cfg), _opt(plane_set), n_pictures, width, height, _opt(hist), d_hist, hist_bytes, d_prev_hist,
+                                prev_bytes, d_stats, d_selected, d_count), "hist")
+
+
 def _back_to_back(n_streams, picture_bytes):
     return [s * picture_bytes for s in range(n_streams)]
 
@@ -704,6 +743,11 @@ def lib():
         L.h263mi_batch_change_map.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, vp, vp, vp]
         L.h263mi_batch_change_last.argtypes = [vp, vp, vp, vp, C.c_uint64, vp, vp, vp, vp]
         L.h263mi_change_last.argtypes = [vp, vp, vp, vp, C.c_uint64, vp, vp, vp]
+        L.h263mi_hist_extent.argtypes = [u32, u32, u32, vp, vp]
+        L.h263mi_hist_on.argtypes = [vp, vp, u32, u32, u32, vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp]
+        L.h263mi_batch_hist.argtypes = [vp, vp, vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp]
+        L.h263mi_batch_hist_last.argtypes = [vp, u32, vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp, vp]
+        L.h263mi_hist_last.argtypes = [vp, u32, vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -876,6 +920,12 @@ class H263State:
         """h263mi_change_last: change_map with the last picture's luma, read in place, as cur (one picture); queues and returns"""
         _check(lib().h263mi_change_last(self._h, _opt(prev), _opt(change), d_cells, cells_bytes, d_summary, d_selected, d_count),
                "change_last")
+
+    def hist_last(self, plane, hist, d_hist, hist_bytes, d_stats, d_prev_hist=None, prev_bytes=0, d_selected=None, d_count=None):
+        """h263mi_hist_last: hist() over plane `plane` (0 Y, 1 Cb, 2 Cr) of the last picture, read in place (one picture); queues
+        and returns"""
+        _check(lib().h263mi_hist_last(self._h, plane, _opt(hist), d_hist, hist_bytes, d_prev_hist, prev_bytes, d_stats, d_selected,
+                                      d_count), "hist_last")
 
     def render_rgba(self, strength=0):
         v = self._view(lib().h263mi_get_last_picture, "get_last_picture")
@@ -1370,6 +1420,21 @@ class Batch:
         rcs = (C.c_int * self.n)() if stream_rc is not None else None
         _check(lib().h263mi_batch_change_last(self._h, _opt(prev), _opt(change), d_cells, cells_bytes, d_summary, d_selected, d_count,
                                               rcs), "batch_change_last")
+        return list(rcs) if rcs is not None else None
+
+    def hist(self, plane_set, hist, d_hist, hist_bytes, d_stats, d_prev_hist=None, prev_bytes=0, d_selected=None, d_count=None):
+        """h263mi_batch_hist: sync, then hist() on the batch's device and stream with its picture size and stream count -- for a
+        d_deblocked buffer (planes_default_set)"""
+        _check(lib().h263mi_batch_hist(self._h, _opt(plane_set), _opt(hist), d_hist, hist_bytes, d_prev_hist, prev_bytes, d_stats,
+                                       d_selected, d_count), "batch_hist")
+
+    def hist_last(self, plane, hist, d_hist, hist_bytes, d_stats, d_prev_hist=None, prev_bytes=0, d_selected=None, d_count=None,
+                  stream_rc=True):
+        """h263mi_batch_hist_last: hist() over plane `plane` (0 Y, 1 Cb, 2 Cr) of every stream's last picture, read in place; queues
+        and returns -> rcs (per stream 0 or ERR_NO_PICTURE).  stream_rc=None: a stream without a picture raises ERR_NO_PICTURE"""
+        rcs = (C.c_int * self.n)() if stream_rc is not None else None
+        _check(lib().h263mi_batch_hist_last(self._h, plane, _opt(hist), d_hist, hist_bytes, d_prev_hist, prev_bytes, d_stats,
+                                            d_selected, d_count, rcs), "batch_hist_last")
         return list(rcs) if rcs is not None else None
 
     def timing_begin(self):

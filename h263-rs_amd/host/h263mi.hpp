@@ -265,6 +265,17 @@ public:
         return true;
     }
 
+    // The histogram of plane `plane` (0 Y, 1 Cb, 2 Cr) of the last picture, read in place (h263mi_hist_last; one picture): queues
+    // its launches and returns.  false before the first picture, when nothing is queued
+    bool hist_last(uint32_t plane, const h263mi_hist &h, uint32_t *d_hist, uint64_t hist_bytes, h263mi_hist_stats *d_stats,
+                   uint32_t *d_prev_hist = nullptr, uint64_t prev_bytes = 0, uint32_t *d_selected = nullptr, uint32_t *d_count = nullptr) const
+    {
+        const int rc = h263mi_hist_last(s_, plane, &h, d_hist, hist_bytes, d_prev_hist, prev_bytes, d_stats, d_selected, d_count);
+        if (rc == H263MI_ERR_NO_PICTURE) return false;
+        check(rc);
+        return true;
+    }
+
     h263mi_state *raw() { return s_; }
 
 private:
@@ -527,6 +538,41 @@ inline std::vector<int> batch_change_last(h263mi_batch *b, uint32_t n_streams, c
 {
     std::vector<int> rc(n_streams);
     check(h263mi_batch_change_last(b, &prev, &c, d_cells, cells_bytes, d_summary, d_selected, d_count, rc.data()));
+    return rc;
+}
+
+// The bytes of n_pictures histograms (h263mi_hist_extent); throws for a description it refuses
+inline uint64_t hist_extent(uint32_t n_pictures, uint32_t width, uint32_t height, const h263mi_hist &h)
+{
+    uint64_t bytes = 0;
+    check(h263mi_hist_extent(n_pictures, width, height, &h, &bytes));
+    return bytes;
+}
+
+// Queues the launches that count the pictures of a plane set (h263mi_hist_on): 256 counts per picture to d_hist, one statistics
+// record per picture to d_stats, the distance to d_prev_hist (device, or nullptr), the ascending list of the cuts to d_selected and
+// its length to d_count (both device, or both nullptr); it does not wait.
+inline void hist(const h263mi_plane_set &set, uint32_t n_pictures, uint32_t width, uint32_t height, const h263mi_hist &h, uint32_t *d_hist,
+                 uint64_t hist_bytes, h263mi_hist_stats *d_stats, uint32_t *d_prev_hist = nullptr, uint64_t prev_bytes = 0,
+                 uint32_t *d_selected = nullptr, uint32_t *d_count = nullptr, const h263mi_backend_cfg *cfg = nullptr)
+{
+    check(h263mi_hist_on(cfg, &set, n_pictures, width, height, &h, d_hist, hist_bytes, d_prev_hist, prev_bytes, d_stats, d_selected, d_count));
+}
+// ... over what batch b has written: h263mi_batch_sync, then the call above with the batch's device, stream, size and streams
+inline void batch_hist(h263mi_batch *b, const h263mi_plane_set &set, const h263mi_hist &h, uint32_t *d_hist, uint64_t hist_bytes,
+                       h263mi_hist_stats *d_stats, uint32_t *d_prev_hist = nullptr, uint64_t prev_bytes = 0, uint32_t *d_selected = nullptr,
+                       uint32_t *d_count = nullptr)
+{
+    check(h263mi_batch_hist(b, &set, &h, d_hist, hist_bytes, d_prev_hist, prev_bytes, d_stats, d_selected, d_count));
+}
+// ... over plane `plane` (0 Y, 1 Cb, 2 Cr) of every stream's last picture, read in place (h263mi_batch_hist_last) -> per stream
+// H263MI_OK or H263MI_ERR_NO_PICTURE (n_streams: the batch's)
+inline std::vector<int> batch_hist_last(h263mi_batch *b, uint32_t n_streams, uint32_t plane, const h263mi_hist &h, uint32_t *d_hist,
+                                        uint64_t hist_bytes, h263mi_hist_stats *d_stats, uint32_t *d_prev_hist = nullptr,
+                                        uint64_t prev_bytes = 0, uint32_t *d_selected = nullptr, uint32_t *d_count = nullptr)
+{
+    std::vector<int> rc(n_streams);
+    check(h263mi_batch_hist_last(b, plane, &h, d_hist, hist_bytes, d_prev_hist, prev_bytes, d_stats, d_selected, d_count, rc.data()));
     return rc;
 }
 

@@ -1099,6 +1099,86 @@ int h263mi_change_last(const h263mi_state *s, const h263mi_plane_set *prev, cons
                        uint32_t *d_cells, uint64_t cells_bytes, h263mi_change_summary *d_summary,
                        uint32_t *d_selected, uint32_t *d_count);
 
+/*
+ * PLANE HISTOGRAMS (additive, ABI 7): is this a new scene, and how is this picture exposed.  The grey-level histogram of every
+ * picture of a set of 8-bit planes (a h263mi_plane_set, as above; a window of a picture is a set whose base is offset), its
+ * statistics and the list of scene cuts, on the device; integers only, so every result is exact and independent of the order of
+ * summation.  Pictures are W x H, 1..65535 each, P = W*H < 2^30; n_pictures <= 65535.
+ *   Histogram.  hist[p][v], v = 0..255, = the number of pixels of picture p with value v, a uint32; picture p's 256 words lie at
+ *               d_hist + 256*p.  Bytes between rows or behind column W never enter.
+ *   Statistics. Per picture (h263mi_hist_stats): sum = the sum of v*hist[v], sum_sq = the sum of v*v*hist[v]; min and max = the
+ *               smallest and largest v with a count; mode = the smallest v among those with the largest count; p_lo, p_hi and
+ *               distance as below.
+ *   Percentiles. With C(v) = the sum of hist[u] over u <= v, pctl(q) is the smallest v with C(v) >= 1 and 1000*C(v) >= q*P, in 64
+ *               bits; p_lo = pctl(lo_permille), p_hi = pctl(hi_permille).  pctl(0) == min and pctl(1000) == max.
+ *   Distance.   With d_prev_hist (the layout of d_hist): distance = the sum over v of |hist[v] - prev[v]|, prev as it was before the
+ *               call; without it 0.  64 bits, because prev may hold anything.
+ *   Cut.        A picture is a cut when distance*1000 > (uint64)cut_permille * 2*P; 2P is the distance of two disjoint histograms
+ *               of P pixels.
+ *   Selection.  The indices of the valid cut pictures go to d_selected[0 .. count), ascending; count goes to d_count[0]; entries at
+ *               count and behind are not written.  d_selected and d_count: both or neither; a list needs d_prev_hist.
+ *   Roll.       With roll = 1, which needs d_prev_hist, prev[p] of every valid picture equals hist[p] after the call: the next call
+ *               measures picture-to-picture distance without a copy.  A zeroed prev gives distance == P on the first call, which
+ *               is a cut at every cut_permille below 500.
+ * Out of scope: sets of mixed sizes; RGBA; joint histograms of several planes; fewer than 256 bins.
+ */
+typedef struct h263mi_hist {
+    uint8_t  roll;                        /* 0 or 1 */
+    uint8_t  reserved[3];                 /* 0 */
+    uint16_t lo_permille, hi_permille;    /* 0..1000, lo <= hi */
+    uint32_t cut_permille;                /* 0..1000 */
+    uint32_t reserved2;                   /* 0 */
+} h263mi_hist;                            /* 16 bytes */
+
+typedef struct h263mi_hist_stats {
+    uint64_t sum;
+    uint64_t sum_sq;
+    uint64_t distance;
+    uint8_t  min, max;
+    uint8_t  p_lo, p_hi;
+    uint8_t  mode;
+    uint8_t  reserved[3];                 /* written as 0 */
+} h263mi_hist_stats;                      /* 32 bytes */
+
+/* The bytes of n_pictures histograms (n_pictures * 1024); hist_bytes may be NULL.  No device.  Also the validator of h:
+ * H263MI_ERR_INVALID_ARGUMENT for h NULL, a reserved byte set, roll > 1, a permille above 1000, lo_permille > hi_permille, a zero
+ * size, a side above 65535, width*height >= 2^30 or n_pictures > 65535. */
+int h263mi_hist_extent(uint32_t n_pictures, uint32_t width, uint32_t height, const h263mi_hist *h, uint64_t *hist_bytes);
+/* Queues its launches (the clearing of d_hist, k_hist, k_hist_final, k_hist_select when a list is wanted) on cfg's device and
+ * stream (NULL: device 0, the null stream) and returns; it does not wait.  d_hist (n_pictures * 256 words, required), d_prev_hist
+ * (the same, or NULL), d_stats (n_pictures records, required), d_selected (room for n_pictures indices) and d_count are DEVICE
+ * pointers.  The set is only read: its pictures may overlap and any picture_stride is allowed (0: one plane for every picture).
+ * Any alignment of the set works; one whose d_base, pitch and picture_stride are multiples of 16 takes the fast path.
+ * H263MI_ERR_INVALID_ARGUMENT, decided on the host before any device call: anything h263mi_hist_extent refuses; set, d_hist or
+ * d_stats NULL, or the set's d_base NULL, while n_pictures > 0; pitch < width with height > 1; a set whose last byte,
+ * (n_pictures-1) * picture_stride + (height-1) * pitch + width computed without wrapping, lies behind `bytes`; hist_bytes, or
+ * prev_bytes with d_prev_hist given, below the extent; d_hist or d_prev_hist not a multiple of 4, d_stats not a multiple of 8;
+ * d_prev_hist's extent intersecting d_hist's; roll or a list without d_prev_hist; d_selected and d_count not both set or both
+ * NULL.  n_pictures == 0 is H263MI_OK with no launch, except that d_count, if given, still becomes 0.  Without a device:
+ * H263MI_ERR_NO_DEVICE, after the argument checks.  A failure of the HIP runtime is H263MI_ERR_HIP; the same call then
+ * succeeds. */
+int h263mi_hist_on(const h263mi_backend_cfg *cfg, const h263mi_plane_set *set, uint32_t n_pictures, uint32_t width, uint32_t height,
+                   const h263mi_hist *h, uint32_t *d_hist, uint64_t hist_bytes, uint32_t *d_prev_hist, uint64_t prev_bytes,
+                   h263mi_hist_stats *d_stats, uint32_t *d_selected, uint32_t *d_count);
+/* h263mi_batch_sync(b), then the call above with the batch's device, stream and picture size and n_pictures = the batch's streams:
+ * the way to measure what the batch has written to d_deblocked, whose luma planes in the default plane output are the set that
+ * h263mi_batch_change_map documents.  An error of the sync is returned and nothing is queued. */
+int h263mi_batch_hist(h263mi_batch *b, const h263mi_plane_set *set, const h263mi_hist *h, uint32_t *d_hist, uint64_t hist_bytes,
+                      uint32_t *d_prev_hist, uint64_t prev_bytes, h263mi_hist_stats *d_stats, uint32_t *d_selected, uint32_t *d_count);
+/* The pictures are plane `plane` (0 = Y, 1 = Cb, 2 = Cr; anything else is refused; the chroma planes are cw x ch) of each stream's
+ * last decoded picture, read in place from the frame store: the plane h263mi_copy_yuv / h263mi_batch_copy_yuv would deliver at
+ * that moment (the reference planes, not the deblocked ones).  Ordered behind the decodes already queued; an open timing bracket is
+ * closed first; the call queues its launches and returns.  A stream without a picture is INVALID: no plane byte of it is read, its
+ * histogram and its statistics are all zero, its prev is neither read nor written, it is never selected, and stream_rc[s] =
+ * H263MI_ERR_NO_PICTURE (else 0); with stream_rc NULL the call returns that code after queuing the rest. */
+int h263mi_batch_hist_last(h263mi_batch *b, uint32_t plane, const h263mi_hist *h, uint32_t *d_hist, uint64_t hist_bytes,
+                           uint32_t *d_prev_hist, uint64_t prev_bytes, h263mi_hist_stats *d_stats, uint32_t *d_selected,
+                           uint32_t *d_count, int *stream_rc);
+/* ... of one H263State: one picture.  Before the first picture nothing is queued and the call returns H263MI_ERR_NO_PICTURE,
+ * like h263mi_change_last. */
+int h263mi_hist_last(const h263mi_state *s, uint32_t plane, const h263mi_hist *h, uint32_t *d_hist, uint64_t hist_bytes,
+                     uint32_t *d_prev_hist, uint64_t prev_bytes, h263mi_hist_stats *d_stats, uint32_t *d_selected, uint32_t *d_count);
+
 /* ======================================================================= */
 /* Device memory + synthetic macroblock records (bench / test support)      */
 /* ======================================================================= */
