@@ -1,10 +1,11 @@
-// analysis_kernels.hip -- digests, change maps and histograms of pictures in device memory: __global__ wrappers and launchers.
+// analysis_kernels.hip -- digests, change maps, histograms and motion regions of pictures in device memory: __global__ wrappers and launchers.
 // Built with the flags of decode_kernels.hip.
 #include "kernels.h"
 
 #include "change_kernel.inl"
 #include "digest_kernel.inl"
 #include "hist_kernel.inl"
+#include "regions_kernel.inl"
 
 namespace h263mi {
 
@@ -140,6 +141,44 @@ hipError_t launch_hist(const HistArgs &args, const HistFinalArgs &fin, const His
         return hipGetLastError();
     }
     return hipSuccess;
+}
+
+// ---------------------------------------------------------------------------------------
+// k_regions, k_regions_pack: the changed cells of a change map's grids as a table of ROI boxes (h263mi_regions_on,
+// h263mi_batch_regions; regions_kernel.inl).  k_regions: blockIdx.x = picture, REGIONS_THREADS threads, the grid's parents and
+// counts in sizeof(RegionsLds) bytes of static LDS -- one workgroup a CU.  The pack kernel is one wave.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(REGIONS_THREADS) void k_regions(RegionsArgs a)
+{
+    __shared__ __attribute__((aligned(16))) RegionsLds lds;
+    const int tid = threadIdx.x;
+    RegionsLane t;
+    regions_picture(a, lds, blockIdx.x, [&](auto f) { f(tid, t); });
+}
+
+__global__ __launch_bounds__(64) void k_regions_pack(RegionsPackArgs f)
+{
+    __shared__ __attribute__((aligned(16))) RegionsPackLds lds;
+    const int lane = threadIdx.x & 63;
+    RegionsPackLane t;
+    regions_pack(f, lds, [&](auto g) { g(lane, t); });
+}
+
+hipError_t launch_regions(const RegionsArgs &args, const RegionsPackArgs &pack, hipStream_t stream)
+{
+    if (!pack.rois || !pack.count || !pack.max_rois || pack.max_rois > REGIONS_MAX_ROIS || pack.n_pictures != args.n_pictures)
+        return hipErrorInvalidValue;
+    if (args.n_pictures) {
+        if (!args.cells || !args.work || !args.info || pack.work != args.work || pack.info != args.info || !args.gw || !args.gh ||
+            (uint64_t)args.gw * args.gh > REGIONS_MAX_CELLS || !args.max_per || args.max_per > REGIONS_MAX_PER_PICTURE ||
+            pack.max_per != args.max_per || args.n_pictures > CHANGE_MAX_PICTURES)
+            return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_regions, dim3(args.n_pictures), dim3(REGIONS_THREADS), 0, stream, args);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_regions_pack, dim3(1), dim3(64), 0, stream, pack);
+    return hipGetLastError();
 }
 
 }  // namespace h263mi

@@ -1547,6 +1547,111 @@ int h263mi_batch_hist_last(h263mi_batch *b, uint32_t plane, const h263mi_hist *h
     return b->hist_last(plane, h, d_hist, hist_bytes, d_prev_hist, prev_bytes, d_stats, d_selected, d_count, stream_rc);
 }
 
+// =========================================================================================
+// motion regions (regions_kernel.inl)
+// =========================================================================================
+int h263mi_regions_extent(uint32_t n_pictures, uint32_t width, uint32_t height, const h263mi_regions *r, uint32_t *gw, uint32_t *gh,
+                          uint64_t *cells_bytes, uint64_t *work_bytes)
+{
+    static_assert(sizeof(h263mi_regions) == 16 && sizeof(h263mi_region_info) == 16 && sizeof(h263mi_region_stat) == 16,
+                  "the structures are part of the ABI");
+    if (!r || r->reserved || r->cell_log2 < 3 || r->cell_log2 > 6 || (r->connectivity != 4 && r->connectivity != 8) ||
+        r->margin_cells > REGIONS_MAX_MARGIN || !r->min_cells || !r->max_per_picture || r->max_per_picture > REGIONS_MAX_PER_PICTURE)
+        return H263MI_ERR_INVALID_ARGUMENT;
+    if (!width || !height || width > 65535 || height > 65535 || (uint64_t)width * height >= (1ull << 30)) return H263MI_ERR_INVALID_ARGUMENT;
+    if (n_pictures > CHANGE_MAX_PICTURES) return H263MI_ERR_INVALID_ARGUMENT;
+    const uint32_t w = ((width - 1u) >> r->cell_log2) + 1u, h = ((height - 1u) >> r->cell_log2) + 1u;
+    if ((uint64_t)w * h > REGIONS_MAX_CELLS) return H263MI_ERR_INVALID_ARGUMENT;
+    if (gw) *gw = w;
+    if (gh) *gh = h;
+    if (cells_bytes) *cells_bytes = (uint64_t)n_pictures * w * h * 4u;
+    if (work_bytes) *work_bytes = (uint64_t)n_pictures * r->max_per_picture * REGIONS_ENTRY;
+    return H263MI_OK;
+}
+
+// The arguments of a regions call, decided on the host in the order include/h263mi.h lists; *out, *pack: the launches they come to.
+static int regions_args(const uint32_t *d_cells, uint64_t cells_bytes, const h263mi_change_summary *d_summary, uint32_t n, uint32_t w,
+                        uint32_t h, const h263mi_regions *r, void *d_work, uint64_t work_bytes, h263mi_roi *d_rois, uint32_t max_rois,
+                        h263mi_region_stat *d_stats, h263mi_region_info *d_info, uint32_t *d_count, RegionsArgs *out, RegionsPackArgs *pack)
+{
+    uint32_t gw = 0, gh = 0;
+    uint64_t cells_extent = 0, work_extent = 0;
+    RC_TRY(h263mi_regions_extent(n, w, h, r, &gw, &gh, &cells_extent, &work_extent));
+    if (!d_rois || !d_count) return H263MI_ERR_INVALID_ARGUMENT;
+    if (n && (!d_cells || !d_work || !d_info)) return H263MI_ERR_INVALID_ARGUMENT;
+    if (cells_bytes < cells_extent || work_bytes < work_extent) return H263MI_ERR_INVALID_ARGUMENT;
+    if (!max_rois || max_rois > REGIONS_MAX_ROIS) return H263MI_ERR_INVALID_ARGUMENT;
+    if ((uintptr_t)d_cells % 4 || (uintptr_t)d_rois % 4 || (uintptr_t)d_info % 4 || (uintptr_t)d_count % 4 || (uintptr_t)d_work % 8 ||
+        (uintptr_t)d_stats % 8 || (uintptr_t)d_summary % 8)
+        return H263MI_ERR_INVALID_ARGUMENT;
+    // the byte ranges: the five outputs first, then the two inputs; an absent or empty one intersects nothing
+    const struct {
+        uintptr_t at;
+        uint64_t bytes;
+    } range[7] = {{(uintptr_t)d_rois, (uint64_t)max_rois * sizeof(h263mi_roi)},
+                  {(uintptr_t)d_stats, d_stats ? (uint64_t)max_rois * sizeof(h263mi_region_stat) : 0u},
+                  {(uintptr_t)d_info, (uint64_t)n * sizeof(h263mi_region_info)},
+                  {(uintptr_t)d_count, 8u},
+                  {(uintptr_t)d_work, work_extent},
+                  {(uintptr_t)d_cells, cells_extent},
+                  {(uintptr_t)d_summary, d_summary ? (uint64_t)n * sizeof(h263mi_change_summary) : 0u}};
+    for (int i = 0; i < 5; i++)
+        for (int j = i + 1; j < 7; j++)
+            if (range[i].bytes && range[j].bytes && range[i].at < range[j].at + range[j].bytes && range[j].at < range[i].at + range[i].bytes)
+                return H263MI_ERR_INVALID_ARGUMENT;
+    RegionsArgs a{};
+    a.cells = d_cells;
+    a.summary = d_summary;
+    a.work = static_cast<uint8_t *>(d_work);
+    a.info = d_info;
+    a.w = w, a.h = h, a.gw = gw, a.gh = gh;
+    a.cell_log2 = r->cell_log2, a.connectivity = r->connectivity, a.margin = r->margin_cells, a.threshold = r->cell_threshold;
+    a.min_cells = r->min_cells, a.max_per = r->max_per_picture, a.n_pictures = n;
+    *out = a;
+    *pack = RegionsPackArgs{d_summary, a.work, d_rois, d_stats, d_info, d_count, n, r->max_per_picture, max_rois, 0};
+    return H263MI_OK;
+}
+
+// k_regions over the pictures and k_regions_pack, queued on `stream` of the current device
+static int regions_launch(const RegionsArgs &a, const RegionsPackArgs &pack, hipStream_t stream)
+{
+    if (!launch_regions) return H263MI_ERR_HIP;            // (kernels.h: only a stub runtime lacks it)
+    auto queue = [&]() -> int {
+        HIP_TRY(launch_regions(a, pack, stream));
+        return H263MI_OK;
+    };
+    return digest_rc(queue());                             // (whatever the runtime refuses is H263MI_ERR_HIP)
+}
+
+int h263mi_regions_on(const h263mi_backend_cfg *cfg, const uint32_t *d_cells, uint64_t cells_bytes, const h263mi_change_summary *d_summary,
+                      uint32_t n_pictures, uint32_t width, uint32_t height, const h263mi_regions *r, void *d_work, uint64_t work_bytes,
+                      h263mi_roi *d_rois, uint32_t max_rois, h263mi_region_stat *d_stats, h263mi_region_info *d_info, uint32_t *d_count)
+{
+    RegionsArgs a;
+    RegionsPackArgs pack;
+    RC_TRY(regions_args(d_cells, cells_bytes, d_summary, n_pictures, width, height, r, d_work, work_bytes, d_rois, max_rois, d_stats, d_info,
+                        d_count, &a, &pack));
+    const int dev = cfg ? cfg->device_id : 0;
+    RC_TRY(check_device(dev));
+    DeviceGuard g(dev);
+    if (!g.ok) return H263MI_ERR_NO_DEVICE;
+    return regions_launch(a, pack, cfg ? (hipStream_t)cfg->stream : nullptr);
+}
+
+int h263mi_batch_regions(h263mi_batch *b, const uint32_t *d_cells, uint64_t cells_bytes, const h263mi_change_summary *d_summary,
+                         const h263mi_regions *r, void *d_work, uint64_t work_bytes, h263mi_roi *d_rois, uint32_t max_rois,
+                         h263mi_region_stat *d_stats, h263mi_region_info *d_info, uint32_t *d_count)
+{
+    if (!b) return H263MI_ERR_INVALID_ARGUMENT;
+    RegionsArgs a;
+    RegionsPackArgs pack;
+    RC_TRY(regions_args(d_cells, cells_bytes, d_summary, b->n, b->L.width, b->L.height, r, d_work, work_bytes, d_rois, max_rois, d_stats,
+                        d_info, d_count, &a, &pack));
+    DeviceGuard g(b->device);
+    RC_TRY(b->sync());                           // (the deferred rendering of a pipelined batch, the second stream of an overlapped one)
+    return regions_launch(a, pack, b->stream);
+}
+
 int h263mi_batch_timing_begin(h263mi_batch *b)
 {
     if (!b) return H263MI_ERR_INVALID_ARGUMENT;

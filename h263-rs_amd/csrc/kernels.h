@@ -11,6 +11,7 @@
 #include "hist_kernel.inl"
 #include "plane_filter_kernel.inl"
 #include "plane_resize_kernel.inl"
+#include "regions_kernel.inl"
 #include "resize_kernel.inl"
 #include "roi_kernel.inl"
 #include "tensor_resize_kernel.inl"
@@ -92,6 +93,10 @@ hipError_t launch_digest(const DigestArgs &args, const DigestFinalArgs &fin, hip
 // sel, k_hist_select over the statistics.  The caller has cleared the histograms on the stream.  Weak like launch_rgba_resize; the
 // histogram entry points refuse to run without it.
 hipError_t launch_hist(const HistArgs &args, const HistFinalArgs &fin, const HistSelectArgs *sel, hipStream_t stream) __attribute__((weak));
+// k_regions, one workgroup per picture of args.n_pictures grids (regions_kernel.inl), then k_regions_pack, one wave, over the
+// pictures' staged entries: the launch pair of one regions call; without pictures the pack alone, which still fills the table.
+// Weak like launch_rgba_resize; the regions entry points refuse to run without it.
+hipError_t launch_regions(const RegionsArgs &args, const RegionsPackArgs &pack, hipStream_t stream) __attribute__((weak));
 hipError_t launch_synth_headers(const SynthArgs &args, hipStream_t stream);
 hipError_t launch_synth_coeffs(const SynthArgs &args, hipStream_t stream);
 // streaming probes: mode 0 copy in -> out, 1 read in (out = 16-byte sink), 2 write out; bytes is a multiple of 16;

@@ -43,6 +43,11 @@
 //                                            missing pixels are counted as zeros
 //   -DH263MI_MUTATE_HIST_PERCENTILE_STRICT   hist_reached compares 1000 * C(v) > q * P where the contract says >=: a percentile
 //                                            that is reached exactly moves to the next value with a count
+// ... and two of the motion regions (regions_kernel.inl), which the CPU checker alone is built with (tests/test_sim_regions.py):
+//   -DH263MI_MUTATE_REGIONS_DIAGONAL         under connectivity 8 a cell is not joined with its down-left neighbour (the cell below
+//                                            never looks up and to the right)
+//   -DH263MI_MUTATE_REGIONS_BOX_CLIP         a box's right and bottom edges are not clipped to W and H: a box that holds partial
+//                                            edge cells reaches behind the picture
 // Two parts.  The switches need nothing and are included by post_kernel.inl and recon_kernel.inl; the IDCT helper is included
 // by recon_kernel.inl (which defines H263MI_MUTANTS_WITH_IDCT) behind the definitions it uses (f32x2, splat2, BasisPtr,
 // basis_pair).
@@ -136,6 +141,16 @@ constexpr bool kHistCutChunkFull = false;
 constexpr bool kHistPercentileStrict = true;
 #else
 constexpr bool kHistPercentileStrict = false;
+#endif
+#if defined(H263MI_MUTATE_REGIONS_DIAGONAL)
+constexpr bool kRegionsDiagonal = true;
+#else
+constexpr bool kRegionsDiagonal = false;
+#endif
+#if defined(H263MI_MUTATE_REGIONS_BOX_CLIP)
+constexpr bool kRegionsBoxClip = true;
+#else
+constexpr bool kRegionsBoxClip = false;
 #endif
 
 }  // namespace mutants

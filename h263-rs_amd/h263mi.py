@@ -112,6 +112,8 @@ EXPORTS = [
     "h263mi_change_extent", "h263mi_change_map_on", "h263mi_batch_change_map", "h263mi_batch_change_last", "h263mi_change_last",
     # ABI 7, additive: plane histograms -- 256 counts per picture, statistics and percentiles, the list of scene cuts
     "h263mi_hist_extent", "h263mi_hist_on", "h263mi_batch_hist", "h263mi_batch_hist_last", "h263mi_hist_last",
+    # ABI 7, additive: motion regions -- the changed cells of a change map's grids as a device table of ROI boxes
+    "h263mi_regions_extent", "h263mi_regions_on", "h263mi_batch_regions",
 ]
 FILTER_AREA, FILTER_BILINEAR, FILTER_BICUBIC = 0, 1, 2
 FRAME_STRETCH, FRAME_LETTERBOX, FRAME_COVER, FRAME_WINDOW = 0, 1, 2, 3
@@ -526,6 +528,54 @@ def hist(plane_set, n_pictures, width, height, hist, d_hist, hist_bytes, d_stats
                                 prev_bytes, d_stats, d_selected, d_count), "hist")
 
 
+REGIONS_MAX_CELLS = 32768
+
+
+class Regions(C.Structure):
+    """h263mi_regions: the grid's cell_log2 (3..6); connectivity 4 or 8; every box grows by margin_cells (0..8); a cell is changed by
+    the rule of Change with cell_threshold; components of fewer than min_cells (>= 1) cells are dropped; at most max_per_picture
+    (1..256) boxes a picture, the first in label order"""
+    _fields_ = [("cell_log2", C.c_uint8), ("connectivity", C.c_uint8), ("margin_cells", C.c_uint8), ("reserved", C.c_uint8),
+                ("cell_threshold", C.c_uint32), ("min_cells", C.c_uint32), ("max_per_picture", C.c_uint32)]
+
+
+class RegionInfo(C.Structure):
+    _fields_ = [("components", C.c_uint32), ("kept", C.c_uint32), ("first", C.c_uint32), ("written", C.c_uint32)]
+
+
+class RegionStat(C.Structure):
+    _fields_ = [("sad", C.c_uint64), ("cells", C.c_uint32), ("label", C.c_uint32)]
+
+
+REGION_INFO_DTYPE = np.dtype([("components", np.uint32), ("kept", np.uint32), ("first", np.uint32), ("written", np.uint32)])
+REGION_STAT_DTYPE = np.dtype([("sad", np.uint64), ("cells", np.uint32), ("label", np.uint32)])
+ROI_DTYPE = np.dtype([("picture", np.uint32), ("x", np.uint16), ("y", np.uint16), ("w", np.uint16), ("h", np.uint16),
+                      ("reserved", np.uint32)])
+
+
+def make_regions(cell_log2=4, cell_threshold=0, connectivity=8, margin_cells=0, min_cells=1, max_per_picture=16):
+    return Regions(cell_log2, connectivity, margin_cells, 0, cell_threshold, min_cells, max_per_picture)
+
+
+def regions_extent(n_pictures, width, height, regions):
+    """h263mi_regions_extent -> (gw, gh, cells_bytes, work_bytes)"""
+    gw, gh, nb, wb = C.c_uint32(0), C.c_uint32(0), C.c_uint64(0), C.c_uint64(0)
+    _check(lib().h263mi_regions_extent(n_pictures, width, height, _opt(regions), C.byref(gw), C.byref(gh), C.byref(nb), C.byref(wb)),
+           "regions_extent")
+    return gw.value, gh.value, nb.value, wb.value
+
+
+def regions(d_cells, cells_bytes, n_pictures, width, height, regions, d_work, work_bytes, d_rois, max_rois, d_info, d_count, d_stats=None,
+            d_summary=None, device_id=0, stream=None):
+    """h263mi_regions_on: queues the launches that turn the changed cells of the n_pictures grids at d_cells (as change_map writes
+    them) into the table of Roi boxes at d_rois (max_rois entries, the unused ones invalid), a RegionStat per box at d_stats (or
+    None), a RegionInfo per picture at d_info and the two count words at d_count; pictures whose ChangeSummary at d_summary (or
+    None) has no changed cell are not read; d_work: work_bytes of staging (regions_extent); does not wait."""
+    cfg = BackendCfg(device_id, 0, stream)
+    _check(lib().h263mi_regions_on(C.byref(cfg), d_cells, cells_bytes, d_summary, n_pictures, width, height, _opt(regions), d_work,
+                                   work_bytes, d_rois, max_rois, d_stats, d_info, d_count), "regions")
+
+
 def _back_to_back(n_streams, picture_bytes):
     return [s * picture_bytes for s in range(n_streams)]
 
@@ -739,6 +789,9 @@ def lib():
         L.h263mi_roi_tensor_on.argtypes = [vp, vp, C.c_uint64, u32, u16, u16, vp, u32, vp, vp, C.c_uint64, vp]
         L.h263mi_batch_roi_tensor.argtypes = [vp, vp, C.c_uint64, vp, u32, vp, vp, C.c_uint64, vp]
         L.h263mi_change_extent.argtypes = [u32, u32, u32, vp, vp, vp, vp]
+        L.h263mi_regions_extent.argtypes = [u32, u32, u32, vp, vp, vp, vp, vp]
+        L.h263mi_regions_on.argtypes = [vp, vp, C.c_uint64, vp, u32, u32, u32, vp, vp, C.c_uint64, vp, u32, vp, vp, vp]
+        L.h263mi_batch_regions.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint64, vp, u32, vp, vp, vp]
         L.h263mi_change_map_on.argtypes = [vp, vp, vp, u32, u32, u32, vp, vp, C.c_uint64, vp, vp, vp]
         L.h263mi_batch_change_map.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, vp, vp, vp]
         L.h263mi_batch_change_last.argtypes = [vp, vp, vp, vp, C.c_uint64, vp, vp, vp, vp]
@@ -1436,6 +1489,12 @@ class Batch:
         _check(lib().h263mi_batch_hist_last(self._h, plane, _opt(hist), d_hist, hist_bytes, d_prev_hist, prev_bytes, d_stats,
                                             d_selected, d_count, rcs), "batch_hist_last")
         return list(rcs) if rcs is not None else None
+
+    def regions(self, d_cells, cells_bytes, regions, d_work, work_bytes, d_rois, max_rois, d_info, d_count, d_stats=None, d_summary=None):
+        """h263mi_batch_regions: sync, then regions() on the batch's device and stream with its picture size and stream count -- the
+        step between change_last (same d_cells, d_summary) and roi_tensor (d_rois, n_rois = max_rois)"""
+        _check(lib().h263mi_batch_regions(self._h, d_cells, cells_bytes, d_summary, _opt(regions), d_work, work_bytes, d_rois, max_rois,
+                                          d_stats, d_info, d_count), "batch_regions")
 
     def timing_begin(self):
         _check(lib().h263mi_batch_timing_begin(self._h), "timing_begin")

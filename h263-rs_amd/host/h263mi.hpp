@@ -541,6 +541,39 @@ inline std::vector<int> batch_change_last(h263mi_batch *b, uint32_t n_streams, c
     return rc;
 }
 
+// The grid of a regions call, the bytes of n_pictures grids and the bytes of its staging area (h263mi_regions_extent); throws for a
+// description it refuses, a grid above H263MI_REGIONS_MAX_CELLS included
+struct RegionsExtent {
+    uint32_t gw, gh;
+    uint64_t cells_bytes, work_bytes;
+};
+inline RegionsExtent regions_extent(uint32_t n_pictures, uint32_t width, uint32_t height, const h263mi_regions &r)
+{
+    RegionsExtent e{};
+    check(h263mi_regions_extent(n_pictures, width, height, &r, &e.gw, &e.gh, &e.cells_bytes, &e.work_bytes));
+    return e;
+}
+// Queues the launches that turn the changed cells of the grids at d_cells (as change_map writes them) into the table of boxes at
+// d_rois (h263mi_regions_on): max_rois entries, the unused ones invalid, a stat per box to d_stats (device, or nullptr), an info per
+// picture to d_info, the two count words to d_count; a picture whose summary (device, or nullptr) has no changed cell is not read;
+// it does not wait.
+inline void regions(const uint32_t *d_cells, uint64_t cells_bytes, uint32_t n_pictures, uint32_t width, uint32_t height, const h263mi_regions &r,
+                    void *d_work, uint64_t work_bytes, h263mi_roi *d_rois, uint32_t max_rois, h263mi_region_info *d_info, uint32_t *d_count,
+                    h263mi_region_stat *d_stats = nullptr, const h263mi_change_summary *d_summary = nullptr,
+                    const h263mi_backend_cfg *cfg = nullptr)
+{
+    check(h263mi_regions_on(cfg, d_cells, cells_bytes, d_summary, n_pictures, width, height, &r, d_work, work_bytes, d_rois, max_rois, d_stats,
+                            d_info, d_count));
+}
+// ... behind batch_change_last and in front of batch_roi_tensor: h263mi_batch_sync, then the call above with the batch's device,
+// stream, size and streams
+inline void batch_regions(h263mi_batch *b, const uint32_t *d_cells, uint64_t cells_bytes, const h263mi_regions &r, void *d_work,
+                          uint64_t work_bytes, h263mi_roi *d_rois, uint32_t max_rois, h263mi_region_info *d_info, uint32_t *d_count,
+                          h263mi_region_stat *d_stats = nullptr, const h263mi_change_summary *d_summary = nullptr)
+{
+    check(h263mi_batch_regions(b, d_cells, cells_bytes, d_summary, &r, d_work, work_bytes, d_rois, max_rois, d_stats, d_info, d_count));
+}
+
 // The bytes of n_pictures histograms (h263mi_hist_extent); throws for a description it refuses
 inline uint64_t hist_extent(uint32_t n_pictures, uint32_t width, uint32_t height, const h263mi_hist &h)
 {

@@ -1179,6 +1179,95 @@ int h263mi_batch_hist_last(h263mi_batch *b, uint32_t plane, const h263mi_hist *h
 int h263mi_hist_last(const h263mi_state *s, uint32_t plane, const h263mi_hist *h, uint32_t *d_hist, uint64_t hist_bytes,
                      uint32_t *d_prev_hist, uint64_t prev_bytes, h263mi_hist_stats *d_stats, uint32_t *d_selected, uint32_t *d_count);
 
+/*
+ * MOTION REGIONS (additive, ABI 7): from the cells that changed to a DEVICE table of ROI boxes -- the link between a change map and
+ * h263mi_roi_tensor_on, so that decode -> h263mi_batch_change_last -> regions -> h263mi_batch_roi_tensor -> network runs as
+ * stream-ordered launches with no host read in between.  Integers only: every result is exact.
+ *   Input.     d_cells holds n_pictures grids of uint32 cell SADs, laid out exactly as h263mi_change_map_on writes them: picture
+ *              p's at d_cells + p*gw*gh, row-major, for W x H pictures and cells of c = 1 << cell_log2 pixels, gw = ceil(W/c),
+ *              gh = ceil(H/c).  n_pictures <= 65535; W and H in 1..65535, W*H < 2^30; gw*gh <= H263MI_REGIONS_MAX_CELLS (the grid
+ *              is labelled in the 160 KiB of one compute unit's LDS, 16 bits a cell): 1080p at c = 8 is 240 x 135 = 32 400 cells,
+ *              4K at c = 16 the same grid.
+ *   Changed.   Cell (cy, cx) is changed by the rule of the change maps above, with this call's cell_threshold.
+ *   Component. A maximal set of changed cells connected under `connectivity`: 4 = a shared edge, 8 = a shared edge or corner.  Its
+ *              label is the smallest raster index cy*gw + cx among its cells, its cells their count, its sad the sum of their
+ *              SADs in 64 bits.
+ *   Kept.      A component with cells >= min_cells.
+ *   Emitted.   A picture's first min(kept, max_per_picture) kept components in ascending label order.
+ *   Box.       The component's cell bounding box [cx0..cx1] x [cy0..cy1], grown by margin_cells on each side and clipped to the
+ *              grid, in pixels: x = cx0*c, y = cy0*c, w = min(W, (cx1+1)*c) - x, h = min(H, (cy1+1)*c) - y, written as
+ *              h263mi_roi{picture = p, x, y, w, h, reserved = 0} -- always a valid ROI for h263mi_roi_tensor_on over W x H
+ *              pictures.  Boxes of different components may overlap; they are not merged.
+ *   Table.     d_rois has room for max_rois entries (1..65535) and holds the emitted boxes of all pictures, pictures ascending and
+ *              labels ascending inside a picture, until it is full.  d_count[0] = the entries written; d_count[1] = the number a
+ *              large enough table would hold, the sum of min(kept, max_per_picture) over the pictures.  Every entry from
+ *              d_count[0] to max_rois - 1 is written as {0xFFFFFFFF, 0, 0, 0, 0, reserved = 1}, which h263mi_roi_tensor_on skips
+ *              on the device: run it over all max_rois entries, no stale box survives a call.  d_stats, when given, runs parallel
+ *              to d_rois; its entries behind the count are all zero.
+ *   Info.      Per picture: components = all its components; kept = the kept ones; first = the index of its first entry, the sum
+ *              of min(kept, max_per_picture) over the pictures before it, capped at max_rois; written = min(min(kept,
+ *              max_per_picture), max_rois - first).
+ *   Skip.      With d_summary (h263mi_change_summary records, optional) a picture with d_summary[p].changed_cells == 0 is not read
+ *              at all: its info is all zero (first too) and it emits nothing -- whatever threshold produced the summary.  This is
+ *              how the streams that h263mi_batch_change_last left without a picture are handled (their cells were never
+ *              written), and the fast path of still pictures.
+ * Out of scope: merging overlapping boxes; tracking regions over time; choosing the LARGEST components when a picture has more than
+ * max_per_picture (the first in label order are taken); grids above the cap; sets of mixed sizes.
+ */
+#define H263MI_REGIONS_MAX_CELLS 32768u
+
+typedef struct h263mi_regions {
+    uint8_t  cell_log2;        /* 3..6: the grid's */
+    uint8_t  connectivity;     /* 4 (shared edge) or 8 (shared edge or corner) */
+    uint8_t  margin_cells;     /* 0..8: every box grows by this many cells on each side */
+    uint8_t  reserved;         /* 0 */
+    uint32_t cell_threshold;   /* the rule of h263mi_change */
+    uint32_t min_cells;        /* >= 1: components of fewer changed cells are dropped */
+    uint32_t max_per_picture;  /* 1..256 */
+} h263mi_regions;              /* 16 bytes */
+
+typedef struct h263mi_region_info {
+    uint32_t components, kept, first, written;
+} h263mi_region_info;          /* 16 bytes */
+
+typedef struct h263mi_region_stat {
+    uint64_t sad;
+    uint32_t cells;
+    uint32_t label;
+} h263mi_region_stat;          /* 16 bytes */
+
+/* The grid, the bytes of n_pictures grids (n_pictures * gw * gh * 4) and the bytes of the staging area,
+ * work_bytes = n_pictures * max_per_picture * 32: the pictures' boxes and stats in front of the compaction, which the caller owns so
+ * that a stream-ordered call allocates nothing.  Each output pointer may be NULL.  No device.  Also the validator of r:
+ * H263MI_ERR_INVALID_ARGUMENT for r NULL, the reserved byte set, cell_log2 outside 3..6, a connectivity other than 4 and 8,
+ * margin_cells > 8, min_cells == 0, max_per_picture outside 1..256, a zero size, a side above 65535, width*height >= 2^30,
+ * n_pictures > 65535 or gw*gh > H263MI_REGIONS_MAX_CELLS. */
+int h263mi_regions_extent(uint32_t n_pictures, uint32_t width, uint32_t height, const h263mi_regions *r,
+                          uint32_t *gw, uint32_t *gh, uint64_t *cells_bytes, uint64_t *work_bytes);
+/* Queues its launches (k_regions, one workgroup per picture, then k_regions_pack) on cfg's device and stream (NULL: device 0, the
+ * null stream) and returns; it does not wait.  d_cells, d_summary (n_pictures records, or NULL), d_work, d_rois, d_stats (max_rois
+ * records, or NULL), d_info (n_pictures records) and d_count (two words) are DEVICE pointers.
+ * H263MI_ERR_INVALID_ARGUMENT, decided on the host before any device call: anything h263mi_regions_extent refuses; d_rois or
+ * d_count NULL; d_cells, d_work or d_info NULL while n_pictures > 0; cells_bytes or work_bytes below its extent; max_rois 0 or
+ * above 65535; d_cells, d_rois, d_info or d_count not a multiple of 4, d_work, d_stats or d_summary not a multiple of 8; the byte
+ * range of an output (d_rois, d_stats, d_info, d_count, d_work) that intersects that of d_cells, of d_summary or of another output.
+ * n_pictures == 0 is H263MI_OK with no launch over the grids, but the table is still filled with invalid entries and both count
+ * words become 0.  Without a device: H263MI_ERR_NO_DEVICE, after the argument checks.  A failure of the HIP runtime is
+ * H263MI_ERR_HIP; the same call then succeeds. */
+int h263mi_regions_on(const h263mi_backend_cfg *cfg, const uint32_t *d_cells, uint64_t cells_bytes,
+                      const h263mi_change_summary *d_summary, uint32_t n_pictures, uint32_t width, uint32_t height,
+                      const h263mi_regions *r, void *d_work, uint64_t work_bytes,
+                      h263mi_roi *d_rois, uint32_t max_rois, h263mi_region_stat *d_stats,
+                      h263mi_region_info *d_info, uint32_t *d_count);
+/* h263mi_batch_sync(b) -- which delivers a deferred rendering of H263MI_CFG_PIPELINE_POST and waits for the second stream of
+ * H263MI_CFG_OVERLAP_POST --, then the call above with the batch's device, stream and picture size and n_pictures = the batch's
+ * streams: the step behind h263mi_batch_change_last (same d_cells and d_summary, same cell_log2) and in front of
+ * h263mi_batch_roi_tensor (d_rois, n_rois = max_rois).  An error of the sync is returned and nothing is queued. */
+int h263mi_batch_regions(h263mi_batch *b, const uint32_t *d_cells, uint64_t cells_bytes, const h263mi_change_summary *d_summary,
+                         const h263mi_regions *r, void *d_work, uint64_t work_bytes,
+                         h263mi_roi *d_rois, uint32_t max_rois, h263mi_region_stat *d_stats,
+                         h263mi_region_info *d_info, uint32_t *d_count);
+
 /* ======================================================================= */
 /* Device memory + synthetic macroblock records (bench / test support)      */
 /* ======================================================================= */
