@@ -1,4 +1,4 @@
-// analysis_kernels.hip -- digests, change maps, histograms and motion regions of pictures in device memory: __global__ wrappers and launchers.
+// analysis_kernels.hip -- digests, change maps, histograms, motion regions and region tracks of pictures in device memory: __global__ wrappers and launchers.
 // Built with the flags of decode_kernels.hip.
 #include "kernels.h"
 
@@ -6,6 +6,7 @@
 #include "digest_kernel.inl"
 #include "hist_kernel.inl"
 #include "regions_kernel.inl"
+#include "tracks_kernel.inl"
 
 namespace h263mi {
 
@@ -178,6 +179,44 @@ hipError_t launch_regions(const RegionsArgs &args, const RegionsPackArgs &pack, 
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(k_regions_pack, dim3(1), dim3(64), 0, stream, pack);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
+// k_tracks, k_tracks_pack: the tracks of every picture, updated from a table of ROI boxes, and the table of the emitted tracks
+// (h263mi_tracks_on, h263mi_batch_tracks; tracks_kernel.inl).  k_tracks: blockIdx.x = picture, TRACKS_THREADS threads,
+// sizeof(TracksLds) bytes of static LDS.  The pack kernel is one wave.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(TRACKS_THREADS) void k_tracks(TracksArgs a)
+{
+    __shared__ __attribute__((aligned(16))) TracksLds lds;
+    const int tid = threadIdx.x;
+    TracksLane t;
+    tracks_picture(a, lds, blockIdx.x, [&](auto f) { f(tid, t); });
+}
+
+__global__ __launch_bounds__(64) void k_tracks_pack(TracksPackArgs f)
+{
+    __shared__ __attribute__((aligned(16))) TracksPackLds lds;
+    const int lane = threadIdx.x & 63;
+    TracksPackLane t;
+    tracks_pack(f, lds, [&](auto g) { g(lane, t); });
+}
+
+hipError_t launch_tracks(const TracksArgs &args, const TracksPackArgs &pack, hipStream_t stream)
+{
+    if (!pack.rois || !pack.count || !pack.max_out || pack.max_out > TRACKS_MAX_OUT || pack.n_pictures != args.n_pictures)
+        return hipErrorInvalidValue;
+    if (args.n_pictures) {
+        if (!args.info_in || !args.state || !args.info || (args.n_rois && !args.rois) || args.n_rois > TRACKS_MAX_ROIS ||
+            !args.cut != !args.cut_count || pack.state != args.state || pack.info != args.info || !args.max_tracks ||
+            args.max_tracks > TRACKS_MAX || pack.max_tracks != args.max_tracks || args.n_pictures > TRACKS_MAX_PICTURES)
+            return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_tracks, dim3(args.n_pictures), dim3(TRACKS_THREADS), 0, stream, args);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_tracks_pack, dim3(1), dim3(64), 0, stream, pack);
     return hipGetLastError();
 }
 

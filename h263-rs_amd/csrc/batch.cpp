@@ -1652,6 +1652,110 @@ int h263mi_batch_regions(h263mi_batch *b, const uint32_t *d_cells, uint64_t cell
     return regions_launch(a, pack, b->stream);
 }
 
+// =========================================================================================
+// region tracks (tracks_kernel.inl)
+// =========================================================================================
+int h263mi_tracks_extent(uint32_t n_pictures, uint32_t width, uint32_t height, const h263mi_tracks *t, uint64_t *state_bytes)
+{
+    static_assert(sizeof(h263mi_tracks) == 16 && sizeof(h263mi_track) == 32 && sizeof(h263mi_track_head) == 32 &&
+                      sizeof(h263mi_track_info) == 32 && sizeof(h263mi_track_ref) == 16,
+                  "the structures are part of the ABI");
+    if (!t || t->reserved || !t->max_tracks || t->max_tracks > TRACKS_MAX || t->iou_permille > 1000 || t->max_missed == 65535 || !t->min_hits)
+        return H263MI_ERR_INVALID_ARGUMENT;
+    if (!width || !height || width > 65535 || height > 65535 || (uint64_t)width * height >= (1ull << 30)) return H263MI_ERR_INVALID_ARGUMENT;
+    if (n_pictures > TRACKS_MAX_PICTURES) return H263MI_ERR_INVALID_ARGUMENT;
+    if (state_bytes) *state_bytes = (uint64_t)n_pictures * tracks_stride(t->max_tracks);
+    return H263MI_OK;
+}
+
+// The arguments of a tracks call, decided on the host in the order include/h263mi.h lists; *out, *pack: the launches they come to.
+static int tracks_args(const h263mi_roi *d_rois, uint32_t n_rois, const h263mi_region_info *d_info_in, uint32_t n, uint32_t w, uint32_t h,
+                       const h263mi_tracks *t, void *d_state, uint64_t state_bytes, const uint32_t *d_cut, const uint32_t *d_cut_count,
+                       h263mi_roi *d_out_rois, uint32_t max_out, h263mi_track_ref *d_out_refs, h263mi_track_info *d_info, uint32_t *d_count,
+                       TracksArgs *out, TracksPackArgs *pack)
+{
+    uint64_t extent = 0;
+    RC_TRY(h263mi_tracks_extent(n, w, h, t, &extent));
+    if (!d_out_rois || !d_count) return H263MI_ERR_INVALID_ARGUMENT;
+    if (n && (!d_info_in || !d_state || !d_info || (n_rois && !d_rois))) return H263MI_ERR_INVALID_ARGUMENT;
+    if (n_rois > TRACKS_MAX_ROIS) return H263MI_ERR_INVALID_ARGUMENT;
+    if (!max_out || max_out > TRACKS_MAX_OUT) return H263MI_ERR_INVALID_ARGUMENT;
+    if (state_bytes < extent) return H263MI_ERR_INVALID_ARGUMENT;
+    if (!d_cut != !d_cut_count) return H263MI_ERR_INVALID_ARGUMENT;
+    if ((uintptr_t)d_rois % 4 || (uintptr_t)d_info_in % 4 || (uintptr_t)d_cut % 4 || (uintptr_t)d_cut_count % 4 || (uintptr_t)d_out_rois % 4 ||
+        (uintptr_t)d_out_refs % 4 || (uintptr_t)d_info % 4 || (uintptr_t)d_count % 4 || (uintptr_t)d_state % 8)
+        return H263MI_ERR_INVALID_ARGUMENT;
+    // the byte ranges: the five outputs first, then the four inputs; an absent or empty one intersects nothing
+    const struct {
+        uintptr_t at;
+        uint64_t bytes;
+    } range[9] = {{(uintptr_t)d_state, extent},
+                  {(uintptr_t)d_out_rois, (uint64_t)max_out * sizeof(h263mi_roi)},
+                  {(uintptr_t)d_out_refs, d_out_refs ? (uint64_t)max_out * sizeof(h263mi_track_ref) : 0u},
+                  {(uintptr_t)d_info, (uint64_t)n * sizeof(h263mi_track_info)},
+                  {(uintptr_t)d_count, 8u},
+                  {(uintptr_t)d_rois, d_rois ? (uint64_t)n_rois * sizeof(h263mi_roi) : 0u},
+                  {(uintptr_t)d_info_in, (uint64_t)n * sizeof(h263mi_region_info)},
+                  {(uintptr_t)d_cut, d_cut ? (uint64_t)n * 4u : 0u},
+                  {(uintptr_t)d_cut_count, d_cut_count ? 4u : 0u}};
+    for (int i = 0; i < 5; i++)
+        for (int j = i + 1; j < 9; j++)
+            if (range[i].bytes && range[j].bytes && range[i].at < range[j].at + range[j].bytes && range[j].at < range[i].at + range[i].bytes)
+                return H263MI_ERR_INVALID_ARGUMENT;
+    TracksArgs a{};
+    a.rois = d_rois, a.info_in = d_info_in;
+    a.state = static_cast<uint8_t *>(d_state);
+    a.cut = d_cut, a.cut_count = d_cut_count;
+    a.info = d_info;
+    a.n_rois = n_rois, a.n_pictures = n, a.w = w, a.h = h;
+    a.max_tracks = t->max_tracks, a.iou_permille = t->iou_permille, a.max_missed = t->max_missed, a.min_hits = t->min_hits;
+    a.emit_period = t->emit_period;
+    *out = a;
+    *pack = TracksPackArgs{a.state, d_out_rois, d_out_refs, d_info, d_count, n, t->max_tracks, max_out, 0};
+    return H263MI_OK;
+}
+
+// k_tracks over the pictures and k_tracks_pack, queued on `stream` of the current device
+static int tracks_launch(const TracksArgs &a, const TracksPackArgs &pack, hipStream_t stream)
+{
+    if (!launch_tracks) return H263MI_ERR_HIP;             // (kernels.h: only a stub runtime lacks it)
+    auto queue = [&]() -> int {
+        HIP_TRY(launch_tracks(a, pack, stream));
+        return H263MI_OK;
+    };
+    return digest_rc(queue());                             // (whatever the runtime refuses is H263MI_ERR_HIP)
+}
+
+int h263mi_tracks_on(const h263mi_backend_cfg *cfg, const h263mi_roi *d_rois, uint32_t n_rois, const h263mi_region_info *d_info_in,
+                     uint32_t n_pictures, uint32_t width, uint32_t height, const h263mi_tracks *t, void *d_state, uint64_t state_bytes,
+                     const uint32_t *d_cut, const uint32_t *d_cut_count, h263mi_roi *d_out_rois, uint32_t max_out,
+                     h263mi_track_ref *d_out_refs, h263mi_track_info *d_info, uint32_t *d_count)
+{
+    TracksArgs a;
+    TracksPackArgs pack;
+    RC_TRY(tracks_args(d_rois, n_rois, d_info_in, n_pictures, width, height, t, d_state, state_bytes, d_cut, d_cut_count, d_out_rois, max_out,
+                       d_out_refs, d_info, d_count, &a, &pack));
+    const int dev = cfg ? cfg->device_id : 0;
+    RC_TRY(check_device(dev));
+    DeviceGuard g(dev);
+    if (!g.ok) return H263MI_ERR_NO_DEVICE;
+    return tracks_launch(a, pack, cfg ? (hipStream_t)cfg->stream : nullptr);
+}
+
+int h263mi_batch_tracks(h263mi_batch *b, const h263mi_roi *d_rois, uint32_t n_rois, const h263mi_region_info *d_info_in,
+                        const h263mi_tracks *t, void *d_state, uint64_t state_bytes, const uint32_t *d_cut, const uint32_t *d_cut_count,
+                        h263mi_roi *d_out_rois, uint32_t max_out, h263mi_track_ref *d_out_refs, h263mi_track_info *d_info, uint32_t *d_count)
+{
+    if (!b) return H263MI_ERR_INVALID_ARGUMENT;
+    TracksArgs a;
+    TracksPackArgs pack;
+    RC_TRY(tracks_args(d_rois, n_rois, d_info_in, b->n, b->L.width, b->L.height, t, d_state, state_bytes, d_cut, d_cut_count, d_out_rois,
+                       max_out, d_out_refs, d_info, d_count, &a, &pack));
+    DeviceGuard g(b->device);
+    RC_TRY(b->sync());                           // (the deferred rendering of a pipelined batch, the second stream of an overlapped one)
+    return tracks_launch(a, pack, b->stream);
+}
+
 int h263mi_batch_timing_begin(h263mi_batch *b)
 {
     if (!b) return H263MI_ERR_INVALID_ARGUMENT;

@@ -15,6 +15,7 @@
 #include "resize_kernel.inl"
 #include "roi_kernel.inl"
 #include "tensor_resize_kernel.inl"
+#include "tracks_kernel.inl"
 
 namespace h263mi {
 
@@ -97,6 +98,10 @@ hipError_t launch_hist(const HistArgs &args, const HistFinalArgs &fin, const His
 // pictures' staged entries: the launch pair of one regions call; without pictures the pack alone, which still fills the table.
 // Weak like launch_rgba_resize; the regions entry points refuse to run without it.
 hipError_t launch_regions(const RegionsArgs &args, const RegionsPackArgs &pack, hipStream_t stream) __attribute__((weak));
+// k_tracks, one workgroup per picture of args.n_pictures states (tracks_kernel.inl), then k_tracks_pack, one wave, over the
+// pictures' emitted slots: the launch pair of one tracks call; without pictures the pack alone, which still fills the table.
+// Weak like launch_rgba_resize; the tracks entry points refuse to run without it.
+hipError_t launch_tracks(const TracksArgs &args, const TracksPackArgs &pack, hipStream_t stream) __attribute__((weak));
 hipError_t launch_synth_headers(const SynthArgs &args, hipStream_t stream);
 hipError_t launch_synth_coeffs(const SynthArgs &args, hipStream_t stream);
 // streaming probes: mode 0 copy in -> out, 1 read in (out = 16-byte sink), 2 write out; bytes is a multiple of 16;

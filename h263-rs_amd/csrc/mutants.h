@@ -48,6 +48,12 @@
 //                                            never looks up and to the right)
 //   -DH263MI_MUTATE_REGIONS_BOX_CLIP         a box's right and bottom edges are not clipped to W and H: a box that holds partial
 //                                            edge cells reaches behind the picture
+// ... and three of the region tracks (tracks_kernel.inl), which the CPU checker alone is built with (tests/test_sim_tracks.py):
+//   -DH263MI_MUTATE_TRACKS_FLOAT_IOU         two pairs are compared by their float32 quotients inter / union, not by the cross
+//                                            products in integers
+//   -DH263MI_MUTATE_TRACKS_ARGMAX            one round only: every track takes its best eligible detection, chosen by another
+//                                            track or not
+//   -DH263MI_MUTATE_TRACKS_BIRTH_BEFORE_DEATH  the births do not see the slots that a cut or a death freed in the same call
 // Two parts.  The switches need nothing and are included by post_kernel.inl and recon_kernel.inl; the IDCT helper is included
 // by recon_kernel.inl (which defines H263MI_MUTANTS_WITH_IDCT) behind the definitions it uses (f32x2, splat2, BasisPtr,
 // basis_pair).
@@ -151,6 +157,21 @@ constexpr bool kRegionsDiagonal = false;
 constexpr bool kRegionsBoxClip = true;
 #else
 constexpr bool kRegionsBoxClip = false;
+#endif
+#if defined(H263MI_MUTATE_TRACKS_FLOAT_IOU)
+constexpr bool kTracksFloatIou = true;
+#else
+constexpr bool kTracksFloatIou = false;
+#endif
+#if defined(H263MI_MUTATE_TRACKS_ARGMAX)
+constexpr bool kTracksArgmax = true;
+#else
+constexpr bool kTracksArgmax = false;
+#endif
+#if defined(H263MI_MUTATE_TRACKS_BIRTH_BEFORE_DEATH)
+constexpr bool kTracksBirthBeforeDeath = true;
+#else
+constexpr bool kTracksBirthBeforeDeath = false;
 #endif
 
 }  // namespace mutants

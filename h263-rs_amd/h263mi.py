@@ -114,6 +114,8 @@ EXPORTS = [
     "h263mi_hist_extent", "h263mi_hist_on", "h263mi_batch_hist", "h263mi_batch_hist_last", "h263mi_hist_last",
     # ABI 7, additive: motion regions -- the changed cells of a change map's grids as a device table of ROI boxes
     "h263mi_regions_extent", "h263mi_regions_on", "h263mi_batch_regions",
+    # ABI 7, additive: region tracks -- a table of ROI boxes matched from picture to picture, the tracks worth cropping as a table
+    "h263mi_tracks_extent", "h263mi_tracks_on", "h263mi_batch_tracks",
 ]
 FILTER_AREA, FILTER_BILINEAR, FILTER_BICUBIC = 0, 1, 2
 FRAME_STRETCH, FRAME_LETTERBOX, FRAME_COVER, FRAME_WINDOW = 0, 1, 2, 3
@@ -576,6 +578,63 @@ def regions(d_cells, cells_bytes, n_pictures, width, height, regions, d_work, wo
                                    work_bytes, d_rois, max_rois, d_stats, d_info, d_count), "regions")
 
 
+class Tracks(C.Structure):
+    """h263mi_tracks: max_tracks (1..256) slots a picture; a pair is eligible from iou_permille (0..1000) on; a track dies behind
+    max_missed (0..65534) consecutive misses; it is emitted from min_hits (>= 1) hits on: once (emit_period 0) or every
+    emit_period-th hit"""
+    _fields_ = [("max_tracks", C.c_uint16), ("iou_permille", C.c_uint16), ("max_missed", C.c_uint16), ("min_hits", C.c_uint16),
+                ("emit_period", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class Track(C.Structure):
+    _fields_ = [("id", C.c_uint32), ("x", C.c_uint16), ("y", C.c_uint16), ("w", C.c_uint16), ("h", C.c_uint16), ("age", C.c_uint32),
+                ("hits", C.c_uint32), ("missed", C.c_uint16), ("flags", C.c_uint16), ("det", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class TrackHead(C.Structure):
+    _fields_ = [("next_id", C.c_uint32), ("live", C.c_uint32), ("calls", C.c_uint32), ("reserved", C.c_uint32 * 5)]
+
+
+class TrackInfo(C.Structure):
+    _fields_ = [("detections", C.c_uint32), ("ignored", C.c_uint32), ("matched", C.c_uint32), ("born", C.c_uint32), ("died", C.c_uint32),
+                ("dropped", C.c_uint32), ("first", C.c_uint32), ("written", C.c_uint32)]
+
+
+class TrackRef(C.Structure):
+    _fields_ = [("id", C.c_uint32), ("picture", C.c_uint32), ("hits", C.c_uint32), ("slot", C.c_uint16), ("flags", C.c_uint16)]
+
+
+TRACK_DTYPE = np.dtype([("id", np.uint32), ("x", np.uint16), ("y", np.uint16), ("w", np.uint16), ("h", np.uint16), ("age", np.uint32),
+                        ("hits", np.uint32), ("missed", np.uint16), ("flags", np.uint16), ("det", np.uint32), ("reserved", np.uint32)])
+TRACK_HEAD_DTYPE = np.dtype([("next_id", np.uint32), ("live", np.uint32), ("calls", np.uint32), ("reserved", np.uint32, (5,))])
+TRACK_INFO_DTYPE = np.dtype([(f, np.uint32) for f in ("detections", "ignored", "matched", "born", "died", "dropped", "first", "written")])
+TRACK_REF_DTYPE = np.dtype([("id", np.uint32), ("picture", np.uint32), ("hits", np.uint32), ("slot", np.uint16), ("flags", np.uint16)])
+TRACK_BORN, TRACK_MATCHED, TRACK_EMITTED = 1, 2, 4
+
+
+def make_tracks(max_tracks=16, iou_permille=300, max_missed=2, min_hits=2, emit_period=0):
+    return Tracks(max_tracks, iou_permille, max_missed, min_hits, emit_period, 0)
+
+
+def tracks_extent(n_pictures, width, height, tracks):
+    """h263mi_tracks_extent -> state_bytes"""
+    nb = C.c_uint64(0)
+    _check(lib().h263mi_tracks_extent(n_pictures, width, height, _opt(tracks), C.byref(nb)), "tracks_extent")
+    return nb.value
+
+
+def tracks(d_rois, n_rois, d_info_in, n_pictures, width, height, tracks, d_state, state_bytes, d_out_rois, max_out, d_info, d_count,
+           d_out_refs=None, d_cut=None, d_cut_count=None, device_id=0, stream=None):
+    """h263mi_tracks_on: queues the launches that update the n_pictures track states at d_state (tracks_extent; zeros: empty) from
+    the table of Roi boxes at d_rois and its RegionInfo records at d_info_in (as regions writes them), and write the emitted tracks
+    as Roi boxes to d_out_rois (max_out entries, the unused ones invalid), a TrackRef per box to d_out_refs (or None), a TrackInfo
+    per picture to d_info and the two count words to d_count; the pictures listed at d_cut / d_cut_count (as hist writes d_selected
+    / d_count; both or None) lose their tracks first; does not wait."""
+    cfg = BackendCfg(device_id, 0, stream)
+    _check(lib().h263mi_tracks_on(C.byref(cfg), d_rois, n_rois, d_info_in, n_pictures, width, height, _opt(tracks), d_state, state_bytes,
+                                  d_cut, d_cut_count, d_out_rois, max_out, d_out_refs, d_info, d_count), "tracks")
+
+
 def _back_to_back(n_streams, picture_bytes):
     return [s * picture_bytes for s in range(n_streams)]
 
@@ -792,6 +851,9 @@ def lib():
         L.h263mi_regions_extent.argtypes = [u32, u32, u32, vp, vp, vp, vp, vp]
         L.h263mi_regions_on.argtypes = [vp, vp, C.c_uint64, vp, u32, u32, u32, vp, vp, C.c_uint64, vp, u32, vp, vp, vp]
         L.h263mi_batch_regions.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint64, vp, u32, vp, vp, vp]
+        L.h263mi_tracks_extent.argtypes = [u32, u32, u32, vp, vp]
+        L.h263mi_tracks_on.argtypes = [vp, vp, u32, vp, u32, u32, u32, vp, vp, C.c_uint64, vp, vp, vp, u32, vp, vp, vp]
+        L.h263mi_batch_tracks.argtypes = [vp, vp, u32, vp, vp, vp, C.c_uint64, vp, vp, vp, u32, vp, vp, vp]
         L.h263mi_change_map_on.argtypes = [vp, vp, vp, u32, u32, u32, vp, vp, C.c_uint64, vp, vp, vp]
         L.h263mi_batch_change_map.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, vp, vp, vp]
         L.h263mi_batch_change_last.argtypes = [vp, vp, vp, vp, C.c_uint64, vp, vp, vp, vp]
@@ -1495,6 +1557,13 @@ class Batch:
         step between change_last (same d_cells, d_summary) and roi_tensor (d_rois, n_rois = max_rois)"""
         _check(lib().h263mi_batch_regions(self._h, d_cells, cells_bytes, d_summary, _opt(regions), d_work, work_bytes, d_rois, max_rois,
                                           d_stats, d_info, d_count), "batch_regions")
+
+    def tracks(self, d_rois, n_rois, d_info_in, tracks, d_state, state_bytes, d_out_rois, max_out, d_info, d_count, d_out_refs=None,
+               d_cut=None, d_cut_count=None):
+        """h263mi_batch_tracks: sync, then tracks() on the batch's device and stream with its picture size and stream count -- the
+        step between regions (its d_rois, max_rois and d_info) and roi_tensor (d_out_rois, n_rois = max_out)"""
+        _check(lib().h263mi_batch_tracks(self._h, d_rois, n_rois, d_info_in, _opt(tracks), d_state, state_bytes, d_cut, d_cut_count,
+                                         d_out_rois, max_out, d_out_refs, d_info, d_count), "batch_tracks")
 
     def timing_begin(self):
         _check(lib().h263mi_batch_timing_begin(self._h), "timing_begin")

@@ -574,6 +574,36 @@ inline void batch_regions(h263mi_batch *b, const uint32_t *d_cells, uint64_t cel
     check(h263mi_batch_regions(b, d_cells, cells_bytes, d_summary, &r, d_work, work_bytes, d_rois, max_rois, d_stats, d_info, d_count));
 }
 
+// The bytes of n_pictures track states (h263mi_tracks_extent); throws for a description it refuses
+inline uint64_t tracks_extent(uint32_t n_pictures, uint32_t width, uint32_t height, const h263mi_tracks &t)
+{
+    uint64_t bytes = 0;
+    check(h263mi_tracks_extent(n_pictures, width, height, &t, &bytes));
+    return bytes;
+}
+// Queues the launches that update the track states at d_state from the table of boxes at d_rois and its infos at d_info_in (as
+// regions writes them) and write the emitted tracks to d_out_rois (h263mi_tracks_on): max_out entries, the unused ones invalid, a
+// ref per box to d_out_refs (device, or nullptr), an info per picture to d_info, the two count words to d_count; the pictures listed
+// at d_cut / d_cut_count (device, both or nullptr) lose their tracks first; it does not wait.
+inline void tracks(const h263mi_roi *d_rois, uint32_t n_rois, const h263mi_region_info *d_info_in, uint32_t n_pictures, uint32_t width,
+                   uint32_t height, const h263mi_tracks &t, void *d_state, uint64_t state_bytes, h263mi_roi *d_out_rois, uint32_t max_out,
+                   h263mi_track_info *d_info, uint32_t *d_count, h263mi_track_ref *d_out_refs = nullptr, const uint32_t *d_cut = nullptr,
+                   const uint32_t *d_cut_count = nullptr, const h263mi_backend_cfg *cfg = nullptr)
+{
+    check(h263mi_tracks_on(cfg, d_rois, n_rois, d_info_in, n_pictures, width, height, &t, d_state, state_bytes, d_cut, d_cut_count, d_out_rois,
+                           max_out, d_out_refs, d_info, d_count));
+}
+// ... behind batch_regions and in front of batch_roi_tensor: h263mi_batch_sync, then the call above with the batch's device,
+// stream, size and streams
+inline void batch_tracks(h263mi_batch *b, const h263mi_roi *d_rois, uint32_t n_rois, const h263mi_region_info *d_info_in,
+                         const h263mi_tracks &t, void *d_state, uint64_t state_bytes, h263mi_roi *d_out_rois, uint32_t max_out,
+                         h263mi_track_info *d_info, uint32_t *d_count, h263mi_track_ref *d_out_refs = nullptr,
+                         const uint32_t *d_cut = nullptr, const uint32_t *d_cut_count = nullptr)
+{
+    check(h263mi_batch_tracks(b, d_rois, n_rois, d_info_in, &t, d_state, state_bytes, d_cut, d_cut_count, d_out_rois, max_out, d_out_refs,
+                              d_info, d_count));
+}
+
 // The bytes of n_pictures histograms (h263mi_hist_extent); throws for a description it refuses
 inline uint64_t hist_extent(uint32_t n_pictures, uint32_t width, uint32_t height, const h263mi_hist &h)
 {

@@ -1211,7 +1211,7 @@ int h263mi_hist_last(const h263mi_state *s, uint32_t plane, const h263mi_hist *h
  *              at all: its info is all zero (first too) and it emits nothing -- whatever threshold produced the summary.  This is
  *              how the streams that h263mi_batch_change_last left without a picture are handled (their cells were never
  *              written), and the fast path of still pictures.
- * Out of scope: merging overlapping boxes; tracking regions over time; choosing the LARGEST components when a picture has more than
+ * Out of scope: merging overlapping boxes; tracking regions over time (REGION TRACKS below does); choosing the LARGEST components when a picture has more than
  * max_per_picture (the first in label order are taken); grids above the cap; sets of mixed sizes.
  */
 #define H263MI_REGIONS_MAX_CELLS 32768u
@@ -1267,6 +1267,113 @@ int h263mi_batch_regions(h263mi_batch *b, const uint32_t *d_cells, uint64_t cell
                          const h263mi_regions *r, void *d_work, uint64_t work_bytes,
                          h263mi_roi *d_rois, uint32_t max_rois, h263mi_region_stat *d_stats,
                          h263mi_region_info *d_info, uint32_t *d_count);
+
+/*
+ * REGION TRACKS (additive, ABI 7): the boxes of h263mi_regions_on -- or of any detector that writes the same records -- matched
+ * from picture to picture, so that a moving object keeps ONE identity and the network behind is asked once per object, not once per
+ * box and picture: decode -> h263mi_batch_change_last -> h263mi_batch_regions -> h263mi_batch_tracks -> h263mi_batch_roi_tensor are
+ * five stream-ordered calls with no host read in between.  Integers only: every result is exact and independent of thread order.
+ *   State.     The caller owns it; it lives in DEVICE memory and persists between calls.  Picture p's state is a
+ *              h263mi_track_head followed by max_tracks h263mi_track slots, at d_state + p * (32 + 32 * max_tracks).  All-zero
+ *              memory is a valid empty state, and any garbage is safe: a slot is LIVE when id != 0 and its box is a valid
+ *              rectangle of the W x H picture (w, h >= 1, x + w <= W, y + h <= H, the sums taken in 32 bits); every other slot is
+ *              FREE and is written back as zeros; next_id == 0 is read as 1.  The head's reserved words are written as 0.
+ *   One call, per picture p, in this order:
+ *   1. Cut.        With d_cut and d_cut_count (the layout of d_selected / d_count of h263mi_hist_on), p is cut when any of
+ *                  d_cut[0 .. min(d_cut_count[0], n_pictures)) equals p; entries >= n_pictures match nothing.  Every live track of a
+ *                  cut picture dies (counted in `died`); next_id is kept.
+ *   2. Detections. d_info_in[p] is a h263mi_region_info as h263mi_regions_on writes it and names the slice
+ *                  d_rois[first .. first + written).  When first + written, taken in 64 bits, exceeds n_rois, the slice is empty
+ *                  and ignored = written.  An entry is valid by the rule of h263mi_roi_tensor_on and when picture == p.  The first
+ *                  256 valid entries in table order are the detections 0 .. D-1; every other entry of the slice counts in
+ *                  `ignored`.  The host never reads d_rois or d_info_in.
+ *   3. Match.      inter(i, j) is the area of the intersection of track i's box and detection j's, union = area_i + area_j - inter.
+ *                  A pair is ELIGIBLE when inter >= 1 and (uint64)inter * 1000 >= (uint64)iou_permille * union.  Pair (i, j) is
+ *                  BETTER than (i', j') when (uint64)inter * union' > (uint64)inter' * union; ties go to the smaller slot i, then to
+ *                  the smaller j -- a strict total order.  The matching is the GREEDY one: take the best eligible pair, remove its
+ *                  track and its detection, repeat.  Nothing wraps: areas are below 2^30, products below 2^61.
+ *   4. Update.     A matched track takes the detection's box, hits + 1, missed = 0, age + 1.  An unmatched live track keeps its
+ *                  box and gets missed + 1, age + 1; with missed > max_missed it dies: its slot is zeroed, died + 1.
+ *   5. Births.     The unmatched detections, ascending j, take the free slots, ascending -- those freed in steps 1 and 4 included.
+ *                  A born track gets id = next_id, hits = 1, age = 1, missed = 0; next_id goes to next_id + 1, and from 0xFFFFFFFF
+ *                  to 1.  A detection that finds no free slot counts in `dropped`.
+ *   6. Emitted.    A track born or matched in this call is emitted when hits >= min_hits and either emit_period == 0 and
+ *                  hits == min_hits ("once, when confirmed"), or emit_period >= 1 and (hits - min_hits) % emit_period == 0.  flags
+ *                  and det describe this call.  head.live = the live slots; head.calls increases by 1, wrapping.
+ *   Table.     d_out_rois has room for max_out entries (1..65535), d_out_refs (optional) runs parallel to it.  The emitted tracks
+ *              of all pictures are written pictures ascending, slots ascending inside a picture, as
+ *              h263mi_roi{picture = p, x, y, w, h, 0}, until the table is full.  d_count[0] = the entries written; d_count[1] = the
+ *              number a large enough table would hold.  Every entry from d_count[0] to max_out - 1 is the invalid entry that
+ *              regions writes, {0xFFFFFFFF, 0, 0, 0, 0, reserved = 1}; the refs there are zero.  d_info[p].first and .written
+ *              follow the regions definition, over the emitted counts.
+ *   A picture without detections is not special -- still, a stream without a picture, a zero d_info_in: its tracks miss.  An
+ *   object that stops moving leaves the change map, so behind regions its track dies after max_missed calls.
+ * Out of scope: motion prediction of a missed track's box; the optimal (Hungarian) assignment; merging boxes; re-identification
+ * after death; sets of mixed sizes; more than 256 tracks or detections per picture.
+ */
+typedef struct h263mi_tracks {
+    uint16_t max_tracks;     /* 1..256: slots per picture */
+    uint16_t iou_permille;   /* 0..1000 */
+    uint16_t max_missed;     /* 0..65534 */
+    uint16_t min_hits;       /* 1..65535 */
+    uint32_t emit_period;    /* see Emitted */
+    uint32_t reserved;       /* 0 */
+} h263mi_tracks;             /* 16 bytes */
+
+typedef struct h263mi_track {
+    uint32_t id;             /* 0: free slot (then the whole record is zero) */
+    uint16_t x, y, w, h;     /* the box it was last seen in */
+    uint32_t age;            /* calls since birth, the birth call included; saturates */
+    uint32_t hits;           /* calls in which it was born or matched; saturates */
+    uint16_t missed;         /* consecutive calls without a match */
+    uint16_t flags;          /* this call: 1 born, 2 matched, 4 emitted */
+    uint32_t det;            /* index in d_rois of this call's detection, else 0xFFFFFFFF */
+    uint32_t reserved;       /* written as 0 */
+} h263mi_track;              /* 32 bytes */
+
+typedef struct h263mi_track_head {
+    uint32_t next_id, live, calls, reserved[5];
+} h263mi_track_head;         /* 32 bytes */
+
+typedef struct h263mi_track_info {
+    uint32_t detections, ignored, matched, born, died, dropped, first, written;
+} h263mi_track_info;         /* 32 bytes */
+
+typedef struct h263mi_track_ref {
+    uint32_t id, picture, hits;
+    uint16_t slot, flags;
+} h263mi_track_ref;          /* 16 bytes */
+
+/* The bytes of n_pictures states, n_pictures * (32 + 32 * max_tracks); state_bytes may be NULL.  No device.  Also the validator of
+ * t: H263MI_ERR_INVALID_ARGUMENT for t NULL, reserved != 0, max_tracks outside 1..256, iou_permille > 1000, max_missed == 65535,
+ * min_hits == 0, a zero size, a side above 65535, width*height >= 2^30 or n_pictures > 65535. */
+int h263mi_tracks_extent(uint32_t n_pictures, uint32_t width, uint32_t height, const h263mi_tracks *t, uint64_t *state_bytes);
+/* Queues its launches (k_tracks, one workgroup per picture, then k_tracks_pack) on cfg's device and stream (NULL: device 0, the
+ * null stream) and returns; it does not wait.  d_rois (n_rois entries), d_info_in (n_pictures records), d_state, d_cut
+ * (n_pictures words are read at most) and d_cut_count (one word), d_out_rois and d_out_refs (max_out records; d_out_refs may be
+ * NULL), d_info (n_pictures records) and d_count (two words) are DEVICE pointers.
+ * H263MI_ERR_INVALID_ARGUMENT, decided on the host before any device call: anything h263mi_tracks_extent refuses; d_out_rois or
+ * d_count NULL; d_info_in, d_state or d_info NULL while n_pictures > 0, d_rois NULL while n_pictures > 0 and n_rois > 0;
+ * n_rois > 65535; max_out 0 or above 65535; state_bytes below the extent; d_cut and d_cut_count not both set or both NULL; a
+ * pointer that is not a multiple of 4, d_state not a multiple of 8; the byte range of an output (d_state, d_out_rois, d_out_refs,
+ * d_info, d_count) that intersects that of an input (d_rois, d_info_in, d_cut, d_cut_count) or of another output.
+ * n_pictures == 0 is H263MI_OK: the table is still filled with invalid entries and both count words become 0.  Without a device:
+ * H263MI_ERR_NO_DEVICE, after the argument checks.  A failure of the HIP runtime is H263MI_ERR_HIP; the same call then succeeds. */
+int h263mi_tracks_on(const h263mi_backend_cfg *cfg, const h263mi_roi *d_rois, uint32_t n_rois,
+                     const h263mi_region_info *d_info_in, uint32_t n_pictures, uint32_t width, uint32_t height,
+                     const h263mi_tracks *t, void *d_state, uint64_t state_bytes,
+                     const uint32_t *d_cut, const uint32_t *d_cut_count,
+                     h263mi_roi *d_out_rois, uint32_t max_out, h263mi_track_ref *d_out_refs,
+                     h263mi_track_info *d_info, uint32_t *d_count);
+/* h263mi_batch_sync(b) -- which delivers a deferred rendering of H263MI_CFG_PIPELINE_POST and waits for the second stream of
+ * H263MI_CFG_OVERLAP_POST --, then the call above with the batch's device, stream and picture size and n_pictures = the batch's
+ * streams: the step behind h263mi_batch_regions (its d_rois with n_rois = its max_rois, its d_info) and in front of
+ * h263mi_batch_roi_tensor (d_out_rois, n_rois = max_out).  An error of the sync is returned and nothing is queued. */
+int h263mi_batch_tracks(h263mi_batch *b, const h263mi_roi *d_rois, uint32_t n_rois, const h263mi_region_info *d_info_in,
+                        const h263mi_tracks *t, void *d_state, uint64_t state_bytes,
+                        const uint32_t *d_cut, const uint32_t *d_cut_count,
+                        h263mi_roi *d_out_rois, uint32_t max_out, h263mi_track_ref *d_out_refs,
+                        h263mi_track_info *d_info, uint32_t *d_count);
 
 /* ======================================================================= */
 /* Device memory + synthetic macroblock records (bench / test support)      */
