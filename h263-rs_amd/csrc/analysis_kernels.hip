@@ -1,7 +1,8 @@
-// analysis_kernels.hip -- digests, change maps, histograms, motion regions and region tracks of pictures in device memory: __global__ wrappers and launchers.
+// analysis_kernels.hip -- digests, change maps, histograms, motion regions, region tracks and background models of pictures in device memory: __global__ wrappers and launchers.
 // Built with the flags of decode_kernels.hip.
 #include "kernels.h"
 
+#include "background_kernel.inl"
 #include "change_kernel.inl"
 #include "digest_kernel.inl"
 #include "hist_kernel.inl"
@@ -218,6 +219,50 @@ hipError_t launch_tracks(const TracksArgs &args, const TracksPackArgs &pack, hip
     }
     hipLaunchKernelGGL(k_tracks_pack, dim3(1), dim3(64), 0, stream, pack);
     return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
+// k_bg_begin, k_bg: the background model of 8-bit planes (h263mi_background_on, h263mi_batch_background_last;
+// background_kernel.inl).  k_bg_begin: one lane per picture.  k_bg: one wave per workgroup, no barrier, the grid of k_change --
+// blockIdx.x = the wave's run of items_per_wave work items, blockIdx.y = picture (from args.p0); a launch holds at most BG_GRID_MAX
+// workgroups, whole pictures.  The list is k_change_select's.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_bg_begin(BgArgs a)
+{
+    const uint32_t p = blockIdx.x * 64u + threadIdx.x;
+    if (p < a.n_pictures) bg_begin(a, p);
+}
+
+__global__ __launch_bounds__(64) void k_bg(BgArgs a)
+{
+    __shared__ __attribute__((aligned(16))) ChangeLds lds;
+    const int lane = threadIdx.x & 63;
+    ChangeLane t;
+    bg_wave(a, lds, a.p0 + blockIdx.y, blockIdx.x * a.items_per_wave, [&](auto f) { f(lane, t); });
+}
+
+hipError_t launch_background(const BgArgs &args, const ChangeSelectArgs *sel, hipStream_t stream)
+{
+    if (args.n_pictures) {
+        BgArgs a = args;
+        BgLaunch l;
+        if (!bg_plan(a, l)) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_bg_begin, dim3((a.n_pictures + 63u) / 64u), dim3(64), 0, stream, a);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        for (a.p0 = 0; a.p0 < a.n_pictures; a.p0 += l.pictures) {
+            const uint32_t n = a.n_pictures - a.p0 < l.pictures ? a.n_pictures - a.p0 : l.pictures;
+            hipLaunchKernelGGL(k_bg, dim3(l.waves, n), dim3(64), 0, stream, a);
+            e = hipGetLastError();
+            if (e != hipSuccess) return e;
+        }
+    }
+    if (sel) {
+        if (!sel->selected || !sel->count || (sel->n_pictures && !sel->summary)) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_change_select, dim3(1), dim3(64), 0, stream, *sel);
+        return hipGetLastError();
+    }
+    return hipSuccess;
 }
 
 }  // namespace h263mi

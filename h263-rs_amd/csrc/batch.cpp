@@ -1414,6 +1414,182 @@ int h263mi_batch_change_last(h263mi_batch *b, const h263mi_plane_set *prev, cons
 }
 
 // =========================================================================================
+// background model (background_kernel.inl)
+// =========================================================================================
+int h263mi_background_extent(uint32_t n_pictures, uint32_t width, uint32_t height, const h263mi_background *bg, uint32_t *gw, uint32_t *gh,
+                             uint64_t *cells_bytes, uint64_t *state_bytes)
+{
+    static_assert(sizeof(h263mi_background) == 16 && sizeof(h263mi_background_head) == 64, "the structures are part of the ABI");
+    if (!bg || bg->reserved || bg->cell_log2 < 3 || bg->cell_log2 > 6 || bg->learn_shift > 7 ||
+        (bg->fg_learn_shift > 7 && bg->fg_learn_shift != BG_KEEP))
+        return H263MI_ERR_INVALID_ARGUMENT;
+    if (!width || !height || width > 65535 || height > 65535 || (uint64_t)width * height >= (1ull << 30)) return H263MI_ERR_INVALID_ARGUMENT;
+    if (n_pictures > CHANGE_MAX_PICTURES) return H263MI_ERR_INVALID_ARGUMENT;
+    const uint32_t w = ((width - 1u) >> bg->cell_log2) + 1u, h = ((height - 1u) >> bg->cell_log2) + 1u;
+    if (gw) *gw = w;
+    if (gh) *gh = h;
+    if (cells_bytes) *cells_bytes = (uint64_t)n_pictures * w * h * 4u;        // (below 2^16 * 2^24 * 4)
+    if (state_bytes) *state_bytes = (uint64_t)n_pictures * bg_stride(width, height);     // (below 2^16 * 2^32)
+    return H263MI_OK;
+}
+
+// The arguments of a background call, decided on the host in the order include/h263mi.h lists; *out, *sel: the launches they come
+// to.  cur_span: the bytes behind cur->d_base that no output may touch (0: the n pictures of cur).
+static int background_args(const h263mi_plane_set *cur, uint32_t n, uint32_t w, uint32_t h, const h263mi_background *bg, void *d_state,
+                           uint64_t state_bytes, const uint32_t *d_cut, const uint32_t *d_cut_count, const h263mi_plane_set *mask,
+                           uint32_t *d_cells, uint64_t cells_bytes, h263mi_change_summary *d_summary, uint32_t *d_selected, uint32_t *d_count,
+                           uint64_t cur_span, BgArgs *out, ChangeSelectArgs *sel)
+{
+    uint32_t gw = 0, gh = 0;
+    uint64_t cells_extent = 0, state_extent = 0;
+    RC_TRY(h263mi_background_extent(n, w, h, bg, &gw, &gh, &cells_extent, &state_extent));
+    BgArgs a{};
+    if (n) {
+        if (!cur || !d_state || !d_summary || !cur->d_base || (mask && !mask->d_base)) return H263MI_ERR_INVALID_ARGUMENT;
+        if (h > 1 && (cur->pitch < w || (mask && mask->pitch < w))) return H263MI_ERR_INVALID_ARGUMENT;
+        uint64_t cur_end, mask_end = 0;
+        if (!plane_set_end(*cur, n, w, h, &cur_end) || cur_end > cur->bytes) return H263MI_ERR_INVALID_ARGUMENT;
+        if (mask && (!plane_set_end(*mask, n, w, h, &mask_end) || mask_end > mask->bytes)) return H263MI_ERR_INVALID_ARGUMENT;
+        if (state_bytes < state_extent || (d_cells && cells_bytes < cells_extent)) return H263MI_ERR_INVALID_ARGUMENT;
+        if ((uintptr_t)d_state % 32) return H263MI_ERR_INVALID_ARGUMENT;
+        if (!d_cut != !d_cut_count || !d_selected != !d_count) return H263MI_ERR_INVALID_ARGUMENT;
+        if (mask) {
+            uint64_t one = 0;
+            plane_set_end(*mask, 1, w, h, &one);                             // (no more than mask_end)
+            if (n > 1 && mask->picture_stride < one) return H263MI_ERR_INVALID_ARGUMENT;
+        }
+        // the byte ranges: the six outputs first, then the three inputs; an absent or empty one intersects nothing
+        const struct {
+            uintptr_t at;
+            uint64_t bytes;
+        } range[9] = {{(uintptr_t)d_state, state_extent},
+                      {(uintptr_t)(mask ? mask->d_base : nullptr), mask_end},
+                      {(uintptr_t)d_cells, d_cells ? cells_extent : 0u},
+                      {(uintptr_t)d_summary, (uint64_t)n * sizeof(h263mi_change_summary)},
+                      {(uintptr_t)d_selected, d_selected ? (uint64_t)n * 4u : 0u},
+                      {(uintptr_t)d_count, d_count ? 4u : 0u},
+                      {(uintptr_t)cur->d_base, cur_span ? cur_span : cur_end},
+                      {(uintptr_t)d_cut, d_cut ? (uint64_t)n * 4u : 0u},
+                      {(uintptr_t)d_cut_count, d_cut_count ? 4u : 0u}};
+        for (int i = 0; i < 6; i++)
+            for (int j = i + 1; j < 9; j++)
+                if (range[i].bytes && range[j].bytes && range[i].at < range[j].at + range[j].bytes && range[j].at < range[i].at + range[i].bytes)
+                    return H263MI_ERR_INVALID_ARGUMENT;
+        a.cur = cur->d_base;
+        a.cur_pitch = cur->pitch, a.cur_stride = cur->picture_stride;
+        a.cur_align = change_align(cur->d_base, cur->pitch, cur->picture_stride);
+        if (mask) {
+            a.mask = mask->d_base;
+            a.mask_pitch = mask->pitch, a.mask_stride = mask->picture_stride;
+            a.mask_align = change_align(mask->d_base, mask->pitch, mask->picture_stride);
+        }
+    } else if (!d_cut != !d_cut_count || !d_selected != !d_count) {
+        return H263MI_ERR_INVALID_ARGUMENT;
+    }
+    a.state = static_cast<uint8_t *>(d_state);
+    a.state_stride = bg_stride(w, h);
+    a.bpitch = bg_pitch(w);
+    a.cut = d_cut, a.cut_count = d_cut_count;
+    a.cells = d_cells;
+    a.summary = d_summary;
+    a.w = w, a.h = h, a.gw = gw, a.gh = gh;
+    a.cell_log2 = bg->cell_log2, a.threshold = bg->cell_threshold;
+    a.learn_shift = bg->learn_shift, a.fg_learn_shift = bg->fg_learn_shift, a.pixel_threshold = bg->pixel_threshold, a.warmup = bg->warmup;
+    a.n_pictures = n;
+    a.segs = (w + CHANGE_SEG - 1u) / CHANGE_SEG;
+    *out = a;
+    *sel = ChangeSelectArgs{d_summary, nullptr, d_selected, d_count, n, bg->min_changed_cells};
+    return H263MI_OK;
+}
+
+// k_bg_begin, k_bg, and k_change_select when a list is wanted, queued on `stream` of the current device
+static int background_launch(const BgArgs &a, const ChangeSelectArgs &sel, hipStream_t stream)
+{
+    if (!a.n_pictures && !sel.count) return H263MI_OK;
+    if (!launch_background) return H263MI_ERR_HIP;        // (kernels.h: only a stub runtime lacks it)
+    auto queue = [&]() -> int {
+        HIP_TRY(launch_background(a, sel.count ? &sel : nullptr, stream));
+        return H263MI_OK;
+    };
+    return digest_rc(queue());                             // (whatever the runtime refuses is H263MI_ERR_HIP)
+}
+
+int h263mi_batch::background_last(const h263mi_background *bg, void *d_state, uint64_t state_bytes, const uint32_t *d_cut,
+                                  const uint32_t *d_cut_count, const h263mi_plane_set *mask, uint32_t *d_cells, uint64_t cells_bytes,
+                                  h263mi_change_summary *d_summary, uint32_t *d_selected, uint32_t *d_count, int *stream_rc)
+{
+    // the luma planes of the frame store, as change_last reads them: set 0 at frames[0], set 1 behind it
+    const uint64_t set_bytes = (uint64_t)(frames[1] - frames[0]);
+    const h263mi_plane_set store{frames[0], 2 * set_bytes, L.pitch_y, L.frame_bytes};
+    BgArgs a;
+    ChangeSelectArgs sel;
+    RC_TRY(background_args(&store, n, L.width, L.height, bg, d_state, state_bytes, d_cut, d_cut_count, mask, d_cells, cells_bytes, d_summary,
+                           d_selected, d_count, store.bytes, &a, &sel));
+    RC_TRY(time_close());                        // a background call is not part of any kernel's time
+    std::vector<uint32_t> words(n);
+    bool missing = false, same = true;
+    for (uint32_t i = 0; i < n; i++) {
+        words[i] = ss[i].cur < 0 ? 0u : (CHANGE_VALID | (ss[i].cur == 1 ? CHANGE_SET1 : 0u));
+        missing |= ss[i].cur < 0;
+        same &= words[i] == words[0];
+    }
+    a.cur_set1 = set_bytes;
+    a.cur_align = change_align(store.d_base, store.pitch, store.picture_stride, set_bytes);
+    if (same && !missing) {
+        a.cur = frames[ss[0].cur];               // every stream's picture lies in one set: no words
+    } else {
+        const uint32_t *d_words = nullptr;
+        RC_TRY(digest_rc(upload(word_ring, words.data(), &d_words, stream)));
+        a.words = sel.words = d_words;
+    }
+    RC_TRY(background_launch(a, sel, stream));
+    if (stream_rc)
+        for (uint32_t i = 0; i < n; i++) stream_rc[i] = ss[i].cur < 0 ? H263MI_ERR_NO_PICTURE : H263MI_OK;
+    return missing && !stream_rc ? H263MI_ERR_NO_PICTURE : H263MI_OK;
+}
+
+int h263mi_background_on(const h263mi_backend_cfg *cfg, const h263mi_plane_set *cur, uint32_t n_pictures, uint32_t width, uint32_t height,
+                         const h263mi_background *bg, void *d_state, uint64_t state_bytes, const uint32_t *d_cut, const uint32_t *d_cut_count,
+                         const h263mi_plane_set *mask, uint32_t *d_cells, uint64_t cells_bytes, h263mi_change_summary *d_summary,
+                         uint32_t *d_selected, uint32_t *d_count)
+{
+    BgArgs a;
+    ChangeSelectArgs sel;
+    RC_TRY(background_args(cur, n_pictures, width, height, bg, d_state, state_bytes, d_cut, d_cut_count, mask, d_cells, cells_bytes, d_summary,
+                           d_selected, d_count, 0, &a, &sel));
+    if (!n_pictures && !d_count) return H263MI_OK;
+    const int dev = cfg ? cfg->device_id : 0;
+    RC_TRY(check_device(dev));
+    DeviceGuard g(dev);
+    if (!g.ok) return H263MI_ERR_NO_DEVICE;
+    return background_launch(a, sel, cfg ? (hipStream_t)cfg->stream : nullptr);
+}
+
+int h263mi_batch_background(h263mi_batch *b, const h263mi_plane_set *cur, const h263mi_background *bg, void *d_state, uint64_t state_bytes,
+                            const uint32_t *d_cut, const uint32_t *d_cut_count, const h263mi_plane_set *mask, uint32_t *d_cells,
+                            uint64_t cells_bytes, h263mi_change_summary *d_summary, uint32_t *d_selected, uint32_t *d_count)
+{
+    if (!b) return H263MI_ERR_INVALID_ARGUMENT;
+    BgArgs a;
+    ChangeSelectArgs sel;
+    RC_TRY(background_args(cur, b->n, b->L.width, b->L.height, bg, d_state, state_bytes, d_cut, d_cut_count, mask, d_cells, cells_bytes,
+                           d_summary, d_selected, d_count, 0, &a, &sel));
+    DeviceGuard g(b->device);
+    RC_TRY(b->sync());                           // (the deferred rendering of a pipelined batch, the second stream of an overlapped one)
+    return background_launch(a, sel, b->stream);
+}
+
+int h263mi_batch_background_last(h263mi_batch *b, const h263mi_background *bg, void *d_state, uint64_t state_bytes, const uint32_t *d_cut,
+                                 const uint32_t *d_cut_count, const h263mi_plane_set *mask, uint32_t *d_cells, uint64_t cells_bytes,
+                                 h263mi_change_summary *d_summary, uint32_t *d_selected, uint32_t *d_count, int *stream_rc)
+{
+    if (!b) return H263MI_ERR_INVALID_ARGUMENT;
+    DeviceGuard g(b->device);
+    return b->background_last(bg, d_state, state_bytes, d_cut, d_cut_count, mask, d_cells, cells_bytes, d_summary, d_selected, d_count,
+                              stream_rc);
+}
+
+// =========================================================================================
 // plane histograms (hist_kernel.inl)
 // =========================================================================================
 int h263mi_hist_extent(uint32_t n_pictures, uint32_t width, uint32_t height, const h263mi_hist *h, uint64_t *hist_bytes)

@@ -255,6 +255,11 @@ struct h263mi_batch {
     // launches on `stream` and returns; a stream without a picture is left out as digest_yuv reports it
     int change_last(const h263mi_plane_set *prev, const h263mi_change *c, uint32_t *d_cells, uint64_t cells_bytes,
                     h263mi_change_summary *d_summary, uint32_t *d_selected, uint32_t *d_count, int *stream_rc);
+    // ---- background model (h263mi_batch_background_last): cur as change_last's, the streams' words too; a stream without a
+    // picture is left out in the same way
+    int background_last(const h263mi_background *bg, void *d_state, uint64_t state_bytes, const uint32_t *d_cut, const uint32_t *d_cut_count,
+                        const h263mi_plane_set *mask, uint32_t *d_cells, uint64_t cells_bytes, h263mi_change_summary *d_summary,
+                        uint32_t *d_selected, uint32_t *d_count, int *stream_rc);
     // ---- histograms (h263mi_batch_hist_last): plane `plane` (0 Y, 1 Cb, 2 Cr) of every stream's last picture, read in place; the
     // streams' HIST_* words travel as change_last's do; a stream without a picture is left out in the same way
     int hist_last(uint32_t plane, const h263mi_hist *h, uint32_t *d_hist, uint64_t hist_bytes, uint32_t *d_prev_hist, uint64_t prev_bytes,

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "dev_common.h"
+#include "background_kernel.inl"
 #include "change_kernel.inl"
 #include "digest_kernel.inl"
 #include "filter_kernel.inl"
@@ -102,6 +103,10 @@ hipError_t launch_regions(const RegionsArgs &args, const RegionsPackArgs &pack, 
 // pictures' emitted slots: the launch pair of one tracks call; without pictures the pack alone, which still fills the table.
 // Weak like launch_rgba_resize; the tracks entry points refuse to run without it.
 hipError_t launch_tracks(const TracksArgs &args, const TracksPackArgs &pack, hipStream_t stream) __attribute__((weak));
+// k_bg_begin over the pictures, k_bg over the args.n_pictures x gh x segs work items of a background call (background_kernel.inl; p0
+// and items_per_wave are set here: bg_plan), then, with sel, k_change_select over the summaries.  k_bg_begin clears the summaries:
+// the caller queues nothing in front.  Weak like launch_rgba_resize; the background entry points refuse to run without it.
+hipError_t launch_background(const BgArgs &args, const ChangeSelectArgs *sel, hipStream_t stream) __attribute__((weak));
 hipError_t launch_synth_headers(const SynthArgs &args, hipStream_t stream);
 hipError_t launch_synth_coeffs(const SynthArgs &args, hipStream_t stream);
 // streaming probes: mode 0 copy in -> out, 1 read in (out = 16-byte sink), 2 write out; bytes is a multiple of 16;

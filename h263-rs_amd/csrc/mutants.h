@@ -54,6 +54,9 @@
 //   -DH263MI_MUTATE_TRACKS_ARGMAX            one round only: every track takes its best eligible detection, chosen by another
 //                                            track or not
 //   -DH263MI_MUTATE_TRACKS_BIRTH_BEFORE_DEATH  the births do not see the slots that a cut or a death freed in the same call
+// ... and two of the background model (background_kernel.inl), which the CPU checker alone is built with (tests/test_sim_bg.py):
+//   -DH263MI_MUTATE_BG_STEP_FLOOR            bg_step is d >> shift alone: a word less than 2^shift below c << 7 never arrives
+//   -DH263MI_MUTATE_BG_JUDGE_AFTER           a pixel is judged against its word after the background-rate update, not before
 // Two parts.  The switches need nothing and are included by post_kernel.inl and recon_kernel.inl; the IDCT helper is included
 // by recon_kernel.inl (which defines H263MI_MUTANTS_WITH_IDCT) behind the definitions it uses (f32x2, splat2, BasisPtr,
 // basis_pair).
@@ -172,6 +175,16 @@ constexpr bool kTracksArgmax = false;
 constexpr bool kTracksBirthBeforeDeath = true;
 #else
 constexpr bool kTracksBirthBeforeDeath = false;
+#endif
+#if defined(H263MI_MUTATE_BG_STEP_FLOOR)
+constexpr bool kBgStepFloor = true;
+#else
+constexpr bool kBgStepFloor = false;
+#endif
+#if defined(H263MI_MUTATE_BG_JUDGE_AFTER)
+constexpr bool kBgJudgeAfter = true;
+#else
+constexpr bool kBgJudgeAfter = false;
 #endif
 
 }  // namespace mutants

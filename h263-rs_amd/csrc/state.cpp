@@ -259,6 +259,17 @@ int h263mi_change_last(const h263mi_state *s, const h263mi_plane_set *prev, cons
     return s->b->change_last(prev, c, d_cells, cells_bytes, d_summary, d_selected, d_count, nullptr);
 }
 
+int h263mi_background_last(const h263mi_state *s, const h263mi_background *bg, void *d_state, uint64_t state_bytes, const uint32_t *d_cut,
+                           const uint32_t *d_cut_count, const h263mi_plane_set *mask, uint32_t *d_cells, uint64_t cells_bytes,
+                           h263mi_change_summary *d_summary, uint32_t *d_selected, uint32_t *d_count)
+{
+    if (!s) return H263MI_ERR_INVALID_ARGUMENT;
+    if (!s->has_last || !s->b) return H263MI_ERR_NO_PICTURE;
+    DeviceGuard g(s->cfg.device_id);
+    return s->b->background_last(bg, d_state, state_bytes, d_cut, d_cut_count, mask, d_cells, cells_bytes, d_summary, d_selected, d_count,
+                                 nullptr);
+}
+
 int h263mi_hist_last(const h263mi_state *s, uint32_t plane, const h263mi_hist *h, uint32_t *d_hist, uint64_t hist_bytes, uint32_t *d_prev_hist,
                      uint64_t prev_bytes, h263mi_hist_stats *d_stats, uint32_t *d_selected, uint32_t *d_count)
 {

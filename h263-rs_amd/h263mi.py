@@ -116,6 +116,9 @@ EXPORTS = [
     "h263mi_regions_extent", "h263mi_regions_on", "h263mi_batch_regions",
     # ABI 7, additive: region tracks -- a table of ROI boxes matched from picture to picture, the tracks worth cropping as a table
     "h263mi_tracks_extent", "h263mi_tracks_on", "h263mi_batch_tracks",
+    # ABI 7, additive: background model -- a running average per pixel and stream, foreground pixels counted per cell
+    "h263mi_background_extent", "h263mi_background_on", "h263mi_batch_background", "h263mi_batch_background_last",
+    "h263mi_background_last",
 ]
 FILTER_AREA, FILTER_BILINEAR, FILTER_BICUBIC = 0, 1, 2
 FRAME_STRETCH, FRAME_LETTERBOX, FRAME_COVER, FRAME_WINDOW = 0, 1, 2, 3
@@ -635,6 +638,48 @@ def tracks(d_rois, n_rois, d_info_in, n_pictures, width, height, tracks, d_state
                                   d_cut, d_cut_count, d_out_rois, max_out, d_out_refs, d_info, d_count), "tracks")
 
 
+class Background(C.Structure):
+    """h263mi_background: cells as Change's; a pixel is foreground when it differs from its rounded background word by more than
+    pixel_threshold; the word moves towards the pixel by the difference >> learn_shift (fg_learn_shift for a foreground pixel, 255:
+    it keeps its word); nothing is foreground in the first `warmup` calls after an initialisation"""
+    _fields_ = [("cell_log2", C.c_uint8), ("learn_shift", C.c_uint8), ("fg_learn_shift", C.c_uint8), ("pixel_threshold", C.c_uint8),
+                ("warmup", C.c_uint16), ("reserved", C.c_uint16), ("cell_threshold", C.c_uint32), ("min_changed_cells", C.c_uint32)]
+
+
+class BackgroundHead(C.Structure):
+    _fields_ = [("age", C.c_uint32), ("mode", C.c_uint32), ("reserved", C.c_uint32 * 14)]
+
+
+BACKGROUND_HEAD_DTYPE = np.dtype([("age", np.uint32), ("mode", np.uint32), ("reserved", np.uint32, (14,))])
+BACKGROUND_VALID, BACKGROUND_INIT, BACKGROUND_WARM = 1, 2, 4
+BACKGROUND_KEEP = 255
+
+
+def make_background(cell_log2=4, learn_shift=4, fg_learn_shift=BACKGROUND_KEEP, pixel_threshold=24, warmup=0, cell_threshold=0,
+                    min_changed_cells=1):
+    return Background(cell_log2, learn_shift, fg_learn_shift, pixel_threshold, warmup, 0, cell_threshold, min_changed_cells)
+
+
+def background_extent(n_pictures, width, height, background):
+    """h263mi_background_extent -> (gw, gh, cells_bytes, state_bytes)"""
+    gw, gh, nb, sb = C.c_uint32(0), C.c_uint32(0), C.c_uint64(0), C.c_uint64(0)
+    _check(lib().h263mi_background_extent(n_pictures, width, height, _opt(background), C.byref(gw), C.byref(gh), C.byref(nb), C.byref(sb)),
+           "background_extent")
+    return gw.value, gh.value, nb.value, sb.value
+
+
+def background_on(cur, n_pictures, width, height, background, d_state, state_bytes, d_cells, cells_bytes, d_summary, d_selected=None,
+                  d_count=None, mask=None, d_cut=None, d_cut_count=None, device_id=0, stream=None):
+    """h263mi_background_on: queues the launches that judge every pixel of the PlaneSet cur against the n_pictures background
+    states at d_state (background_extent; zeros: empty; a multiple of 32) and update them -- foreground counts per cell to d_cells
+    (device, or None), a ChangeSummary per picture to d_summary, the list of the pictures with changed_cells >= min_changed_cells
+    to d_selected / d_count (both or None), 255 / 0 per pixel to the PlaneSet mask (or None); the pictures listed at d_cut /
+    d_cut_count (as hist writes d_selected / d_count; both or None) are initialised anew; does not wait."""
+    cfg = BackendCfg(device_id, 0, stream)
+    _check(lib().h263mi_background_on(C.byref(cfg), _opt(cur), n_pictures, width, height, _opt(background), d_state, state_bytes, d_cut,
+                                      d_cut_count, _opt(mask), d_cells, cells_bytes, d_summary, d_selected, d_count), "background_on")
+
+
 def _back_to_back(n_streams, picture_bytes):
     return [s * picture_bytes for s in range(n_streams)]
 
@@ -858,6 +903,11 @@ def lib():
         L.h263mi_batch_change_map.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, vp, vp, vp]
         L.h263mi_batch_change_last.argtypes = [vp, vp, vp, vp, C.c_uint64, vp, vp, vp, vp]
         L.h263mi_change_last.argtypes = [vp, vp, vp, vp, C.c_uint64, vp, vp, vp]
+        L.h263mi_background_extent.argtypes = [u32, u32, u32, vp, vp, vp, vp, vp]
+        L.h263mi_background_on.argtypes = [vp, vp, u32, u32, u32, vp, vp, C.c_uint64, vp, vp, vp, vp, C.c_uint64, vp, vp, vp]
+        L.h263mi_batch_background.argtypes = [vp, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, C.c_uint64, vp, vp, vp]
+        L.h263mi_batch_background_last.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, vp, vp, C.c_uint64, vp, vp, vp, vp]
+        L.h263mi_background_last.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, vp, vp, C.c_uint64, vp, vp, vp]
         L.h263mi_hist_extent.argtypes = [u32, u32, u32, vp, vp]
         L.h263mi_hist_on.argtypes = [vp, vp, u32, u32, u32, vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp]
         L.h263mi_batch_hist.argtypes = [vp, vp, vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp]
@@ -1035,6 +1085,13 @@ class H263State:
         """h263mi_change_last: change_map with the last picture's luma, read in place, as cur (one picture); queues and returns"""
         _check(lib().h263mi_change_last(self._h, _opt(prev), _opt(change), d_cells, cells_bytes, d_summary, d_selected, d_count),
                "change_last")
+
+    def background_last(self, background, d_state, state_bytes, d_cells, cells_bytes, d_summary, d_selected=None, d_count=None, mask=None,
+                        d_cut=None, d_cut_count=None):
+        """h263mi_background_last: background_on with the last picture's luma, read in place, as cur (one picture); queues and
+        returns"""
+        _check(lib().h263mi_background_last(self._h, _opt(background), d_state, state_bytes, d_cut, d_cut_count, _opt(mask), d_cells,
+                                            cells_bytes, d_summary, d_selected, d_count), "background_last")
 
     def hist_last(self, plane, hist, d_hist, hist_bytes, d_stats, d_prev_hist=None, prev_bytes=0, d_selected=None, d_count=None):
         """h263mi_hist_last: hist() over plane `plane` (0 Y, 1 Cb, 2 Cr) of the last picture, read in place (one picture); queues
@@ -1535,6 +1592,23 @@ class Batch:
         rcs = (C.c_int * self.n)() if stream_rc is not None else None
         _check(lib().h263mi_batch_change_last(self._h, _opt(prev), _opt(change), d_cells, cells_bytes, d_summary, d_selected, d_count,
                                               rcs), "batch_change_last")
+        return list(rcs) if rcs is not None else None
+
+    def background(self, cur, background, d_state, state_bytes, d_cells, cells_bytes, d_summary, d_selected=None, d_count=None, mask=None,
+                   d_cut=None, d_cut_count=None):
+        """h263mi_batch_background: sync, then background_on on the batch's device and stream with its picture size and stream
+        count -- for a d_deblocked buffer (planes_default_set)"""
+        _check(lib().h263mi_batch_background(self._h, _opt(cur), _opt(background), d_state, state_bytes, d_cut, d_cut_count, _opt(mask),
+                                             d_cells, cells_bytes, d_summary, d_selected, d_count), "batch_background")
+
+    def background_last(self, background, d_state, state_bytes, d_cells, cells_bytes, d_summary, d_selected=None, d_count=None, mask=None,
+                        d_cut=None, d_cut_count=None, stream_rc=True):
+        """h263mi_batch_background_last: background_on with the luma of every stream's last picture, read in place, as cur -- in
+        change_last's place in front of regions; queues and returns -> rcs (per stream 0 or ERR_NO_PICTURE).  stream_rc=None: a
+        stream without a picture raises ERR_NO_PICTURE"""
+        rcs = (C.c_int * self.n)() if stream_rc is not None else None
+        _check(lib().h263mi_batch_background_last(self._h, _opt(background), d_state, state_bytes, d_cut, d_cut_count, _opt(mask), d_cells,
+                                                  cells_bytes, d_summary, d_selected, d_count, rcs), "batch_background_last")
         return list(rcs) if rcs is not None else None
 
     def hist(self, plane_set, hist, d_hist, hist_bytes, d_stats, d_prev_hist=None, prev_bytes=0, d_selected=None, d_count=None):

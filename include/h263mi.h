@@ -1307,7 +1307,8 @@ int h263mi_batch_regions(h263mi_batch *b, const uint32_t *d_cells, uint64_t cell
  *              regions writes, {0xFFFFFFFF, 0, 0, 0, 0, reserved = 1}; the refs there are zero.  d_info[p].first and .written
  *              follow the regions definition, over the emitted counts.
  *   A picture without detections is not special -- still, a stream without a picture, a zero d_info_in: its tracks miss.  An
- *   object that stops moving leaves the change map, so behind regions its track dies after max_missed calls.
+ *   object that stops moving leaves the change map, so behind regions its track dies after max_missed calls -- unless the cells
+ *   come from the BACKGROUND MODEL below, which keeps a stopped object in the foreground.
  * Out of scope: motion prediction of a missed track's box; the optimal (Hungarian) assignment; merging boxes; re-identification
  * after death; sets of mixed sizes; more than 256 tracks or detections per picture.
  */
@@ -1374,6 +1375,110 @@ int h263mi_batch_tracks(h263mi_batch *b, const h263mi_roi *d_rois, uint32_t n_ro
                         const uint32_t *d_cut, const uint32_t *d_cut_count,
                         h263mi_roi *d_out_rois, uint32_t max_out, h263mi_track_ref *d_out_refs,
                         h263mi_track_info *d_info, uint32_t *d_count);
+
+/*
+ * BACKGROUND MODEL (additive, ABI 7): what is in front of the scene, not only what moved since the last picture.  A change map
+ * compares a picture with the one before, so it loses an object that stops or that moves less than a cell threshold per picture.
+ * Here every stream keeps a per-pixel background estimate that adapts slowly, every pixel is tested against it, and the foreground
+ * pixels are counted per cell into a grid and summaries that h263mi_regions_on / h263mi_batch_regions consume unchanged:
+ * decode -> h263mi_batch_background_last -> h263mi_batch_regions -> h263mi_batch_tracks -> h263mi_batch_roi_tensor.  Integers
+ * only: every result is exact and independent of thread order.  Pictures, cells and pixels(cell) as for the CHANGE MAPS.
+ *   State.     The caller owns it; it lives in DEVICE memory and persists between calls.  Picture p's state lies at
+ *              d_state + p * state_stride, state_stride = 64 + H * bpitch, bpitch = 32 * ceil(W/16) bytes: a 64-byte
+ *              h263mi_background_head, then H rows of uint16 background words in 8.7 fixed point, 0 .. 32640 (255 << 7).  A row is
+ *              32-byte aligned and padded to whole 16-pixel chunks.  The format is chosen so that (c << 7) - b fits a signed 16-bit
+ *              half.  d_state must be a multiple of 32.  All-zero memory is the valid empty state.  A state that is neither
+ *              all-zero nor what this call left gives unspecified numbers, but no access outside the buffers: nothing is addressed
+ *              by data.  The padding words (columns W and beyond) are written as 0 at an initialisation and stay 0.
+ *   One call, per valid picture p, in this order:
+ *   1. Mode.      INIT when head.age == 0, or when p is cut: with d_cut and d_cut_count (the layout of d_selected / d_count of
+ *                 h263mi_hist_on), p is cut when any of d_cut[0 .. min(d_cut_count[0], n_pictures)) equals p; entries >=
+ *                 n_pictures match nothing -- the rule of h263mi_tracks_on.  WARM when not INIT and head.age < warmup.
+ *   2. Pixel.     c is the current byte, b the stored word.  INIT: b' = c << 7, not foreground.  Otherwise r = (b + 64) >> 7 and
+ *                 fg = !WARM && |c - r| > pixel_threshold -- tested against b BEFORE the update.  s = fg ? fg_learn_shift :
+ *                 learn_shift.  s == 255: b' = b.  Otherwise d = (c << 7) - b, step = d >> s (arithmetic); step == 0 && d != 0:
+ *                 step = d > 0 ? 1 : -1; b' = b + step -- a constant input is reached exactly.  Bytes of cur outside the W x H
+ *                 rows never enter.
+ *   3. Cells.     count(p, cy, cx) = the foreground pixels of the cell, a uint32, in a grid laid out exactly as
+ *                 h263mi_change_map_on writes its SADs.  A cell is changed by the change maps' rule with count in the place of sad:
+ *                 (uint64)count * c*c > (uint64)cell_threshold * pixels(cell).  Summary per picture, a h263mi_change_summary: sad =
+ *                 the foreground pixels in all, changed_cells = the count of changed cells, max_cell_sad = the largest count.  An
+ *                 INIT or WARM picture writes all-zero cells and an all-zero summary.
+ *   4. Mask.      With `mask` (optional, a h263mi_plane_set) every W x H pixel becomes 255 where foreground, else 0; bytes outside
+ *                 the rows are untouched.
+ *   5. Head.      age' = INIT ? 1 : min(age + 1, 0xFFFFFFFF).  mode' = 1 (valid) | 2 (initialised in this call) | 4 (warm-up).  The
+ *                 reserved words are written as 0.
+ *   6. Selection. As for the change maps: the valid pictures with changed_cells >= min_changed_cells, ascending, and the count;
+ *                 d_selected and d_count: both or neither.
+ *   An INVALID picture -- a stream without a picture, in the batch call -- has nothing of its state, mask or cells read or
+ *   written; its summary is all zero; it is never selected.
+ * Out of scope: per-pixel variance or mixture models; shadow detection; chroma; sets of mixed sizes; morphological clean-up of
+ * the mask.
+ */
+typedef struct h263mi_background {
+    uint8_t  cell_log2;          /* 3..6, cells as in h263mi_change */
+    uint8_t  learn_shift;        /* 0..7: background pixels */
+    uint8_t  fg_learn_shift;     /* 0..7, or 255: a foreground pixel keeps its background word */
+    uint8_t  pixel_threshold;    /* 0..255 */
+    uint16_t warmup;             /* calls after an initialisation in which nothing is foreground */
+    uint16_t reserved;           /* 0 */
+    uint32_t cell_threshold;
+    uint32_t min_changed_cells;
+} h263mi_background;             /* 16 bytes */
+
+typedef struct h263mi_background_head {
+    uint32_t age;                /* calls since the initialisation, that call included; saturates; 0: empty */
+    uint32_t mode;               /* the last call: 1 valid | 2 initialised | 4 warm-up */
+    uint32_t reserved[14];       /* written as 0 */
+} h263mi_background_head;        /* 64 bytes */
+
+/* The grid, the bytes of n_pictures grids (n_pictures * gw * gh * 4) and of n_pictures states (n_pictures * (64 + height * 32 *
+ * ceil(width/16))); each output pointer may be NULL.  No device.  Also the validator of bg: H263MI_ERR_INVALID_ARGUMENT for bg
+ * NULL, reserved != 0, cell_log2 outside 3..6, learn_shift > 7, fg_learn_shift neither 0..7 nor 255, a zero size, a side above
+ * 65535, width*height >= 2^30 or n_pictures > 65535. */
+int h263mi_background_extent(uint32_t n_pictures, uint32_t width, uint32_t height, const h263mi_background *bg,
+                             uint32_t *gw, uint32_t *gh, uint64_t *cells_bytes, uint64_t *state_bytes);
+/* Queues its launches (k_bg_begin, which also clears the summaries, k_bg, k_change_select when a list is wanted) on cfg's device
+ * and stream (NULL: device 0, the null stream) and returns; it does not wait.  d_state, d_cut (n_pictures words are read at most)
+ * and d_cut_count (one word), d_cells (may be NULL: no grid wanted), d_summary (n_pictures records, required), d_selected (room for
+ * n_pictures indices) and d_count are DEVICE pointers; mask may be NULL.  cur is only read: its pictures may overlap.  Any
+ * alignment of cur and mask works; sets whose d_base, pitch and picture_stride are multiples of 16 take the fast path.
+ * H263MI_ERR_INVALID_ARGUMENT, decided on the host before any device call: anything h263mi_background_extent refuses; cur, d_state
+ * or d_summary NULL, or a set's d_base NULL, while n_pictures > 0; pitch < width with height > 1; a set whose last byte, computed
+ * without wrapping, lies behind `bytes`; state_bytes, or cells_bytes with d_cells given, below the extent; d_state not a multiple
+ * of 32; d_cut and d_cut_count not both set or both NULL, and the same for d_selected and d_count; mask pictures that overlap one
+ * another (n_pictures > 1 and picture_stride < (height-1) * pitch + width); the byte range of an output (state, mask, cells,
+ * summary, list, count) that intersects that of an input (cur, d_cut, d_cut_count) or of another output.  n_pictures == 0 is
+ * H263MI_OK with no launch, except that d_count, if given, still becomes 0.  Without a device: H263MI_ERR_NO_DEVICE, after the
+ * argument checks.  A failure of the HIP runtime is H263MI_ERR_HIP; the same call then succeeds. */
+int h263mi_background_on(const h263mi_backend_cfg *cfg, const h263mi_plane_set *cur, uint32_t n_pictures, uint32_t width,
+                         uint32_t height, const h263mi_background *bg, void *d_state, uint64_t state_bytes,
+                         const uint32_t *d_cut, const uint32_t *d_cut_count, const h263mi_plane_set *mask,
+                         uint32_t *d_cells, uint64_t cells_bytes, h263mi_change_summary *d_summary,
+                         uint32_t *d_selected, uint32_t *d_count);
+/* h263mi_batch_sync(b) -- which delivers a deferred rendering of H263MI_CFG_PIPELINE_POST and waits for the second stream of
+ * H263MI_CFG_OVERLAP_POST --, then the call above with the batch's device, stream and picture size and n_pictures = the batch's
+ * streams, over a d_deblocked buffer's luma planes (the set h263mi_batch_change_map documents).  An error of the sync is returned
+ * and nothing is queued. */
+int h263mi_batch_background(h263mi_batch *b, const h263mi_plane_set *cur, const h263mi_background *bg,
+                            void *d_state, uint64_t state_bytes, const uint32_t *d_cut, const uint32_t *d_cut_count,
+                            const h263mi_plane_set *mask, uint32_t *d_cells, uint64_t cells_bytes,
+                            h263mi_change_summary *d_summary, uint32_t *d_selected, uint32_t *d_count);
+/* cur is the luma of each stream's last decoded picture, read in place from the frame store, as in h263mi_batch_change_last, whose
+ * place in the chain this call takes: ordered behind the decodes already queued; an open timing bracket is closed first; the call
+ * queues its launches and returns.  A stream without a picture is INVALID (above) and stream_rc[s] = H263MI_ERR_NO_PICTURE (else
+ * 0); with stream_rc NULL the call returns that code after queuing the rest.  The refusals are those of h263mi_background_on
+ * without cur; no output may intersect the frame store. */
+int h263mi_batch_background_last(h263mi_batch *b, const h263mi_background *bg, void *d_state, uint64_t state_bytes,
+                                 const uint32_t *d_cut, const uint32_t *d_cut_count, const h263mi_plane_set *mask,
+                                 uint32_t *d_cells, uint64_t cells_bytes, h263mi_change_summary *d_summary,
+                                 uint32_t *d_selected, uint32_t *d_count, int *stream_rc);
+/* ... of one H263State: one picture.  Before the first picture nothing is queued and the call returns H263MI_ERR_NO_PICTURE,
+ * like h263mi_change_last. */
+int h263mi_background_last(const h263mi_state *s, const h263mi_background *bg, void *d_state, uint64_t state_bytes,
+                           const uint32_t *d_cut, const uint32_t *d_cut_count, const h263mi_plane_set *mask,
+                           uint32_t *d_cells, uint64_t cells_bytes, h263mi_change_summary *d_summary,
+                           uint32_t *d_selected, uint32_t *d_count);
 
 /* ======================================================================= */
 /* Device memory + synthetic macroblock records (bench / test support)      */
